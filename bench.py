@@ -2,10 +2,20 @@
 """bench.py -- env-steps/s of the batched Spriteworld step+render hot path on MI355X.
 
 Contract (one JSON line on rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1: launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
   (one process per GPU, RCCL barrier; environments are sharded across ranks with NO data-path
   collective -- weak scaling, 8192 environments per GPU).
+
+A plain run does what the headline needs and nothing more: it sets up, runs the clock ramp and the W warm-up steps, times
+exactly K steps and prints the line (`value`, `ms_per_step` = wall time of the timed region / K; `roofline` from the timed
+region's own HIP events and the committed PMC passes).  --full adds everything else, as before: the oracle check of sampled
+environments (`verified_envs`), each kernel's own duration (`roofline.kernels`, a pass in the engine's timing mode), the
+`extra` workloads and the `cpu_baseline`.
+--dump-outputs DIR: after the timed steps, the outputs of the last timed step as a caller of Engine.step() receives them,
+as DIR/<name>.npy, finite, in float32 / float64 (outputs_to_dump(): frames of a fixed, seeded sample of environments, a
+None as 0 beside a mask, 64 MB at most; rank 0's shard when N > 1).  The inputs are seeded: the same arguments give the same
+outputs from run to run.
 
 A "step" is one Environment.step() of every environment of the batch, including the 64x64 RGB
 render, with actions and state resident in HBM (reference: spriteworld/environment.py:88-108).
@@ -15,18 +25,18 @@ Clustering reward, 64x64 PILRenderer with anti_aliasing=5 (the COBRA renderer), 
 roofline:     a step is two kernels on one stream (cover: state + geometry + coverage -> run lists; resample: run
               lists -> frames).  `achieved` = algorithmic bytes per step (12 461 B/env-step)
               / the mean duration of BOTH kernels together, measured with HIP events on the launch stream, vs
-              8 TB/s HBM -- the conservative reading; `kernels` gives each kernel's own duration, and for the
+              8 TB/s HBM -- the conservative reading; `kernels` (--full) gives each kernel's own duration, and for the
               dominant one (resample, which writes the frames) the rate of its own bytes.  `kernel`, `metric`
               and `config` are derived from what ran (swb_variant / the lowered config); `traffic` and
               `instructions` come from the committed PMC passes of exactly this build
               (profiles/rNN_counters.json, keyed by the library's build id) or are null.
-cpu_baseline: kind "reference" -- the UNMODIFIED reference (Python + PIL + matplotlib + sklearn; on the GPU node the
+cpu_baseline: (--full) kind "reference" -- the UNMODIFIED reference (Python + PIL + matplotlib + sklearn; on the GPU node the
               sourceless bytecode of /root/reference under oracle/_ref, oracle/stage_ref.py) stepping a bounded sample
               of the headline scene on ALL host cores of rank 0 in this same run (tools/reference_cpu_baseline.py:
               one process per core, core count and CPU model in the block), with the C port of the same algorithm
               (oracle/sw_oracle.c, threads) beside it as `port`.  Falls back to kind "port" -- with the reason --
               only when the reference or one of its libraries cannot be imported.
-verified_envs: after the timed region the last step's positions, rewards, step types and frames of 64 sampled
+verified_envs: (--full) after the timed region the last step's positions, rewards, step types and frames of 64 sampled
               environments are compared with the oracle stepped through the same actions (outside the timed region).
 """
 import argparse
@@ -47,6 +57,41 @@ ENVS_PER_GPU = 8192
 WORKLOAD = 'cluster_s5'
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
 N_ACTION_SETS = 16
+DUMP_OBS_BYTES = 48 << 20       # --dump-outputs: the frames of at most this many bytes (float32) ...
+DUMP_ALL_ENVS_UP_TO = 1 << 18   # ... and the per-environment outputs of every environment up to this many (28 B each)
+DUMP_SEED = 12345
+
+
+def outputs_to_dump(eng, n_envs):
+  """The outputs of `eng`'s last step as a caller of Engine.step() receives them, as finite host arrays in float32 / float64
+  (exact for every value they hold): `reward` (f64), `discount`, `step_type`, `success` (f32) of every environment, and `obs`
+  (f32 [n, W, H, 3]) of a fixed, seeded sample of environments whose indices are `obs_env_index` (f64).  The engine returns
+  NaN for the reference's None (reward and discount of a FIRST step, include/swb.h); here such a value is 0 and
+  `reward_is_none` / `discount_is_none` (f32, 1 = None) say where.  A batch of more than DUMP_ALL_ENVS_UP_TO environments
+  gives the per-environment outputs of the sample as well.  64 MB at most in all."""
+  import torch
+  obs_bytes = 4 * int(np.prod(eng.obs_shape))
+  n_obs = max(1, min(n_envs, DUMP_OBS_BYTES // obs_bytes))
+  idx = np.arange(n_envs) if n_obs == n_envs else np.sort(np.random.default_rng(DUMP_SEED).choice(n_envs, n_obs, replace=False))
+  sel = torch.as_tensor(idx, device=eng.obs.device)
+  out = {'obs': eng.obs[sel].cpu().numpy().astype(np.float32), 'obs_env_index': idx.astype(np.float64)}
+  per_env = slice(None) if n_envs <= DUMP_ALL_ENVS_UP_TO else sel
+  for k, dtype in (('reward', np.float64), ('discount', np.float32)):
+    v = getattr(eng, k)[per_env].cpu().numpy().astype(dtype)
+    none = np.isnan(v)
+    out[k] = np.where(none, 0, v).astype(dtype)
+    out[k + '_is_none'] = none.astype(np.float32)
+  for k in ('step_type', 'success'):
+    out[k] = getattr(eng, k)[per_env].cpu().numpy().astype(np.float32)
+  return out
+
+
+def dump_outputs(directory, arrays):
+  """Writes `arrays` (outputs_to_dump()) as DIR/<name>.npy -> {name: shape}."""
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + '.npy'), a)
+  return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def handoff_bytes_per_env(variant, n_envs):
@@ -88,7 +133,7 @@ class TimedRun(object):
   """One timed run in three parts, so that several of them can be set up first and then run back to back on the device:
   build() puts the engine and its action sets on the device; go() does the warm-up steps and times exactly `steps` steps;
   finish() reads the error flags and (`verify` > 0) the final state / outputs of that many sampled environments for
-  verify_against_oracle(), times the two kernels of a step apart, and closes the engine.
+  verify_against_oracle(), (`time_kernels`) times the two kernels of a step apart, and closes the engine.
 
   Timers.  The timed region is bracketed by ONE pair of HIP events on the launch stream (and by the host clock behind a
   device synchronisation on either side): `kernel_ms` = the events' elapsed time = the kernels of `steps` steps and the
@@ -186,7 +231,9 @@ class TimedRun(object):
     except Exception:  # pylint: disable=broad-except
       pass
 
-  def finish(self):
+  def finish(self, time_kernels=True, dump=False):
+    """time_kernels: also time the two kernels apart (a pass in the engine's timing mode; otherwise cover_ms / resample_ms are None);
+    dump: also return the last timed step's outputs (outputs_to_dump()) as `outputs`."""
     eng, cfg, elapsed = self.eng, self.cfg, self.elapsed
     if self.run_error is not None:
       return dict(error=self.run_error, elapsed=elapsed, kernel_ms=0.0, cover_ms=0.0, resample_ms=0.0, launches=0, errors=-1)
@@ -196,6 +243,7 @@ class TimedRun(object):
       errors = int(eng.error.max().item())
       a_bytes = algorithmic_bytes(cfg)
       variant = eng.variant()
+      outputs = outputs_to_dump(eng, self.n_envs) if dump else None
       sample_out = None
       if self.verify:
         idx = np.sort(np.random.default_rng(99 + self.seed).choice(self.n_envs, size=min(self.verify, self.n_envs), replace=False))
@@ -204,18 +252,22 @@ class TimedRun(object):
                           actions=[np.ascontiguousarray(a[idx]) for a in self.acts_host],
                           got={k: got[k][idx].copy() for k in ('obs', 'reward', 'step_type', 'success', 'discount')},
                           state={k: st[k][idx].copy() for k in ('x', 'y', 'step_count', 'episode', 'n_sprites')})
-      # the two kernels apart: a pass in the engine's timing mode behind the timed region (its state is no longer needed)
-      split_steps = max(10, min(self.steps, 40))
-      eng.timing(True)
-      for i in range(split_steps):
-        eng.step(self.acts[i % N_ACTION_SETS])
-      torch.cuda.synchronize(eng.device)
-      split_total, k = eng.step_time_ms()
-      split_cover, split_second, _ = eng.kernel_times_ms()
-      eng.timing(False)
-      cover_ms, resample_ms = split_cover / max(k, 1) * launches, split_second / max(k, 1) * launches     # (per step x launches)
-      split = dict(steps=int(k), step_ms=split_total / max(k, 1), cover_ms=split_cover / max(k, 1), second_ms=split_second / max(k, 1))
-      errors = max(errors, int(eng.error.max().item()))
+      cover_ms = resample_ms = None
+      if time_kernels:
+        # the two kernels apart: a pass in the engine's timing mode behind the timed region (its state is no longer needed)
+        split_steps = max(10, min(self.steps, 40))
+        eng.timing(True)
+        for i in range(split_steps):
+          eng.step(self.acts[i % N_ACTION_SETS])
+        torch.cuda.synchronize(eng.device)
+        split_total, k = eng.step_time_ms()
+        split_cover, split_second, _ = eng.kernel_times_ms()
+        eng.timing(False)
+        cover_ms, resample_ms = split_cover / max(k, 1) * launches, split_second / max(k, 1) * launches     # (per step x launches)
+        split = dict(steps=int(k), step_ms=split_total / max(k, 1), cover_ms=split_cover / max(k, 1), second_ms=split_second / max(k, 1))
+        errors = max(errors, int(eng.error.max().item()))
+      else:
+        split = None
       facts = dict(sprites=cfg.max_sprites, image=[cfg.image_w, cfg.image_h], anti_aliasing=cfg.anti_aliasing,
                    action_space={0: 'SelectMove', 1: 'DragAndDrop', 2: 'Embodied'}[cfg.action_space],
                    task={0: 'NoReward', 1: 'FindGoalPosition', 2: 'Clustering'}[cfg.tasks[0].kind] if not cfg.is_meta
@@ -225,11 +277,11 @@ class TimedRun(object):
       return dict(error=repr(e), elapsed=elapsed, kernel_ms=0.0, cover_ms=0.0, resample_ms=0.0, launches=0, errors=-1)
     return dict(elapsed=elapsed, kernel_ms=kernel_ms, cover_ms=cover_ms, resample_ms=resample_ms, launches=launches,
                 a_bytes=a_bytes, errors=errors, variant=variant, facts=facts, sample=sample_out, error=None, split=split,
-                data=getattr(self, 'data', 'synthetic'))
+                data=getattr(self, 'data', 'synthetic'), outputs=outputs)
 
 
 def gpu_run(name, n_envs, steps, warmup, aa, device, barrier=None, seed=0, gate=None, verify=0, before=None, after_gate=None,
-            protocol_8d=None):
+            protocol_8d=None, time_kernels=True, dump=False):
   """One timed run, start to end.  `before(run)`: called once the engine and its action sets are on the device (builds the
   clock-ramp twin: see main()); `gate` (N > 1): every rank reports whether it could set up -- returns False when some rank could
   not, then nothing is timed and None is returned (every rank leaves together instead of hanging in a barrier); it also brings
@@ -244,7 +296,7 @@ def gpu_run(name, n_envs, steps, warmup, aa, device, barrier=None, seed=0, gate=
   if after_gate is not None:
     after_gate()
   run.go(barrier=barrier)
-  return run.finish()
+  return run.finish(time_kernels=time_kernels, dump=dump)
 
 
 def verify_against_oracle(sample):
@@ -454,7 +506,9 @@ def assemble_line(args, res, elapsed):
   value = total_envs * args.steps / elapsed
   n_launch = max(res['launches'], 1)
   kernel_s = res['kernel_ms'] / 1e3 / n_launch                       # both kernels of a step, HIP events on the launch stream
-  cover_s, resample_s = res.get('cover_ms', 0.0) / 1e3 / n_launch, res.get('resample_ms', 0.0) / 1e3 / n_launch
+  cover_s = resample_s = None            # the two kernels apart: timed by --full only (TimedRun.finish(time_kernels=True))
+  if res.get('cover_ms') is not None:
+    cover_s, resample_s = res['cover_ms'] / 1e3 / n_launch, res['resample_ms'] / 1e3 / n_launch
   achieved = res['a_bytes'] * args.envs_per_gpu / kernel_s / 1e9
   facts, variant = res['facts'], res['variant']
   image = '%dx%d' % (facts['image'][1], facts['image'][0])
@@ -477,14 +531,15 @@ def assemble_line(args, res, elapsed):
       # separate pass behind the timed region -- every kernel then carries its own completion event, as under rocprofv3's
       # kernel trace, and their sum exceeds kernel_ms (TimedRun)
       'kernels_source': ('engine timing mode, %d steps after the timed region (step %.4f ms with its three events)' %
-                         (res['split']['steps'], res['split']['step_ms'])) if res.get('split') else 'engine timing mode',
+                         (res['split']['steps'], res['split']['step_ms'])) if res.get('split') else
+                        ('engine timing mode' if cover_s is not None else 'not measured (bench.py --full times them apart)'),
       'kernels': [
-          {'name': first, 'ms': cover_s * 1e3, 'waves_per_simd': variant['waves_per_simd'],
+          {'name': first, 'ms': cover_s * 1e3 if cover_s is not None else None, 'waves_per_simd': variant['waves_per_simd'],
            'lds_bytes_per_wave': variant['lds_bytes_per_wave']},
-          {'name': second, 'ms': resample_s * 1e3, 'waves_per_simd': variant.get('resample_waves_per_simd'),
+          {'name': second, 'ms': resample_s * 1e3 if resample_s is not None else None, 'waves_per_simd': variant.get('resample_waves_per_simd'),
            'bands': variant.get('n_bands'), 'column_groups': variant.get('n_column_groups'),
-           'achieved_GBs_frames_only': (obs_bytes * args.envs_per_gpu / resample_s / 1e9) if resample_s > 0 else None,
-           'frac_frames_only': (obs_bytes * args.envs_per_gpu / resample_s / 1e9 / HBM_PEAK_GBS) if resample_s > 0 else None},
+           'achieved_GBs_frames_only': (obs_bytes * args.envs_per_gpu / resample_s / 1e9) if resample_s else None,
+           'frac_frames_only': (obs_bytes * args.envs_per_gpu / resample_s / 1e9 / HBM_PEAK_GBS) if resample_s else None},
       ],
       'lds_bytes_per_wave': variant['lds_bytes_per_wave'], 'waves_per_simd': variant['waves_per_simd'],
       # device memory of the hand-off lists between the two kernels (fixed parts + arena, after the engine's trim) per environment
@@ -559,15 +614,20 @@ def main():
   ap.add_argument('--envs-per-gpu', type=int, default=ENVS_PER_GPU)
   ap.add_argument('--workload', default=WORKLOAD)
   ap.add_argument('--aa', type=int, default=5)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-extra', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check everything beside the headline: the oracle check of sampled environments, each '
+                       "kernel's own duration, the extra workloads (N = 1) and the CPU baseline (N = 1)")
+  ap.add_argument('--dump-outputs', metavar='DIR',
+                  help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+  ap.add_argument('--no-extra', action='store_true', help='--full without the extra workloads')
   ap.add_argument('--protocol', choices=['8d', 'synthetic'], default='8d',
                   help="inputs of the timed run: '8d' = SURVEY 8d literally (reference generators seeded 1000 + env, actions "
                        "RandomState(2000 + step); rank 0 of cluster_s5 / goal_s5), 'synthetic' = the same distributions drawn with numpy")
   ap.add_argument('--ramp-ms', type=float, default=300.0,
                   help='milliseconds of device load (a twin engine of the same workload) in front of the --warmup steps, on every '
                        'rank at every N; 0: none')
-  ap.add_argument('--no-verify', action='store_true', help='skip the oracle check of 64 sampled environments after the timed region')
+  ap.add_argument('--no-verify', action='store_true', help='--full without the oracle check of 64 sampled environments')
   ap.add_argument('--gather-obs', action='store_true',
                   help='also all-gather the observation shards over RCCL every step (BASELINE configs[3])')
   args = ap.parse_args()
@@ -734,7 +794,8 @@ def main():
   try:
     res = gpu_run(args.workload, args.envs_per_gpu, args.steps, args.warmup, args.aa, device,
                   barrier=barrier, seed=rank, gate=gate_once if dist is not None else None,
-                  verify=64 if (rank == 0 and not args.no_verify) else 0,
+                  verify=64 if (rank == 0 and args.full and not args.no_verify) else 0,
+                  time_kernels=args.full, dump=rank == 0 and args.dump_outputs is not None,
                   before=clock_ramp_build, after_gate=clock_ramp_go,
                   protocol_8d=((rank * args.envs_per_gpu, args.gpus * args.envs_per_gpu)
                                if (args.protocol == '8d' and args.workload in ('cluster_s5', 'goal_s5')) else None))
@@ -759,7 +820,8 @@ def main():
     n_l = max(res['launches'], 1)
     dist.all_gather_object(per_rank, {'rank': rank, 'device': torch.cuda.get_device_name(device), 'local_device': device,
                                       'elapsed_s': res['elapsed'], 'kernel_ms': res['kernel_ms'] / n_l,
-                                      'cover_ms': res['cover_ms'] / n_l, 'resample_ms': res['resample_ms'] / n_l,
+                                      'cover_ms': res['cover_ms'] / n_l if res['cover_ms'] is not None else None,
+                                      'resample_ms': res['resample_ms'] / n_l if res['resample_ms'] is not None else None,
                                       'env_errors': res['errors'], 'error': res.get('error')})
     failed = [(r['rank'], r['error']) for r in per_rank if r.get('error')]
     if failed:                               # some rank failed inside the timed region: no value, one line with the errors
@@ -791,6 +853,9 @@ def main():
     return
 
   out = assemble_line(args, res, elapsed)
+  out['full'] = args.full
+  if res.get('outputs') is not None:
+    out['outputs_dumped'] = dump_outputs(args.dump_outputs, res.pop('outputs'))
   if res.get('sample') is not None:
     try:
       out.update(verify_against_oracle(res['sample']))
@@ -818,7 +883,7 @@ def main():
                    'ms_per_step': ramp_info['cold_ms_per_step'], 'wall_ms_per_step': ramp_info['cold_wall_ms_per_step'],
                    'what': 'the same W warm-up + K timed steps on the twin engine, first thing in the process (device out of '
                            'idle); rank 0, HIP events'}
-  if args.gpus == 1 and dist is None and not args.no_extra:
+  if args.full and args.gpus == 1 and dist is None and not args.no_extra:
     run_extras()
   if extra_error:
     out['extra_error'] = extra_error[0]
@@ -829,7 +894,7 @@ def main():
       out['extra_error'] = repr(e)
     out['extra'] = extra
     out['order'] = 'the extra workloads ran after the timed steps of this line, behind a clock ramp of their own'
-  if args.gpus == 1 and not args.no_cpu_baseline:
+  if args.full and args.gpus == 1 and not args.no_cpu_baseline:
     out['cpu_baseline'] = cpu_baseline(args.workload, args.aa)
   print(json.dumps(out))
   if dist is not None:

@@ -76,3 +76,17 @@ def check_against_golden(engine, cfg, z, get_state, step, what):
     assert zlib.crc32(frame.tobytes()) == int(z['ref_frame_crc'][t]), msg + ' frame crc'
     if t < z['frames'].shape[0]:
       assert np.array_equal(frame, z['frames'][t]), msg + ' frame'
+
+
+def check_dump_against(got, want, idx):
+  """`got`: the dumped arrays; `want`: the outputs of the same step (NaN = None) -> equal bit for bit, None as 0 + mask."""
+  assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+  assert np.array_equal(got['obs'], want['obs'][idx].astype(np.float32))
+  for k, dtype in (('reward', np.float64), ('discount', np.float32)):
+    w = want[k].astype(dtype)
+    none = np.isnan(w)
+    bits = np.dtype('u%d' % w.itemsize)
+    assert got[k].dtype == dtype and np.array_equal(got[k + '_is_none'], none.astype(np.float32)), k
+    assert np.array_equal(got[k][~none].view(bits), w[~none].view(bits)) and not got[k][none].any(), k
+  for k in ('step_type', 'success'):
+    assert np.array_equal(got[k], want[k].astype(np.float32)), k

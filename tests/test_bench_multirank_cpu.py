@@ -41,7 +41,7 @@ def _launch(extra_args=(), fault=None, fault_at=None, timeout=600):
 
 
 def test_two_ranks_print_one_line_of_the_contracts_shape():
-  proc, lines = _launch(['--ramp-ms', '1'])
+  proc, lines = _launch(['--ramp-ms', '1', '--full'])
   assert proc.returncode == 0, proc.stderr[-2000:]
   assert len(lines) == 1, proc.stdout[-2000:]
   d = json.loads(lines[0])

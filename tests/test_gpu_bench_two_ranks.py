@@ -33,7 +33,7 @@ def _launch(extra):
 
 
 def test_two_ranks_on_one_device_print_one_verified_line():
-  proc, lines = _launch([])
+  proc, lines = _launch(['--full'])
   assert proc.returncode == 0, proc.stderr[-2000:]
   assert len(lines) == 1, proc.stdout[-2000:]
   d = json.loads(lines[0])

@@ -22,6 +22,7 @@ def _overlay_build():
 @pytest.mark.parametrize('overlays', OVERLAYS, ids=['+'.join(o) for o in OVERLAYS])
 def test_overlay_applies_to_the_shipped_sources(overlays, tmp_path, monkeypatch):
   ob = _overlay_build()
+  monkeypatch.setattr(ob, 'WORK_ROOT', str(tmp_path))     # (not the tool's shared directory: another user's copies may be there)
   name = 'pytest_' + '_'.join(o.replace(':', '') for o in overlays)
   work, csrc = ob.make_copy(name, overlays)
   try:

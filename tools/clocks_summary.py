@@ -34,7 +34,7 @@ def main():
     first = next((t - t0 for t, c in v if c >= 2300), None)
     b = json.loads(open(os.path.join(src, bench)).readlines()[-1])
     lines.append('| `%s` | %d over %.0f s | %.1f s after the process started (import, pools, engines: device idle) | %d / %d / %d | %s | %.4f (%d steps after %d) | %.4f |' % (
-        'python bench.py' + (' --steps 20 --warmup 5' if 'driver' in tag else '') + ' --no-cpu-baseline', len(v), v[-1][0] - t0,
+        'python bench.py --full' + (' --steps 20 --warmup 5' if 'driver' in tag else '') + ' --no-cpu-baseline', len(v), v[-1][0] - t0,
         first if first is not None else -1, statistics.median(hot) if hot else 0, min(hot) if hot else 0, max(hot) if hot else 0,
         ('%d' % statistics.median(idle)) if idle else '-', b['ms_per_step'], b['steps'], b['warmup'], b['cold']['ms_per_step']))
   lines += ['',

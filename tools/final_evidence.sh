@@ -3,7 +3,7 @@
 #   1. the whole GPU test suite + smoke                                        -> $OUT/pytest_gpu.log
 #   2. headline workload: bench line + rocprofv3 kernel trace                   -> $OUT/default/
 #   3. PMC passes over the three judged workloads (one process per counter set) -> $OUT/<workload>/pmc_*.json
-#   4. the default `python bench.py` line (extras + cpu baseline)              -> $OUT/bench_default.json
+#   4. the default `python bench.py --full` line (extras + cpu baseline)       -> $OUT/bench_default.json
 #   5. kernel traces of the AA = 1 and the 12-sprite 128x128 workloads
 #   6. wave timelines of both kernels (experiment build)                       -> $OUT/timeline_*.json
 #   7. kernel time by phase (experiment builds cut short after a phase)        -> $OUT/phase_times.md
@@ -25,7 +25,7 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smo
 
 trace() {   # tag workload aa
   local D=$OUT/$1; mkdir -p $D
-  local ARGS="--steps 40 --warmup 5 --no-extra --no-cpu-baseline --workload $2 --aa $3"
+  local ARGS="--full --steps 40 --warmup 5 --no-extra --no-cpu-baseline --workload $2 --aa $3"
   python bench.py $ARGS > $D/bench_unprofiled.json 2> $D/bench.err
   rocprofv3 --kernel-trace --stats -d $D/trace -o t -- python bench.py $ARGS > $D/bench_trace.json 2> $D/trace.err
   python tools/rocprof_summary.py $D/summary.md "rocprofv3 summary ($ROUND, $1): python bench.py $ARGS" $(find $D/trace -name "*.db" | head -1) > /dev/null 2>> $D/trace.err
@@ -47,14 +47,14 @@ stamp "default bench line, the driver's command (device clocks sampled beside bo
 # (round-5 review: is the gap between the 20-step and the 200-step line the device's clocks?  rocm-smi sampled every 50 ms)
 clocks() { while true; do echo "$(date +%s.%N) $(rocm-smi --showclocks 2>/dev/null | grep -E 'sclk|mclk' | tr -s ' ' | tr '\n' ';')"; sleep 0.05; done; }
 clocks > $OUT/clocks_default.txt & CPID=$!
-python bench.py --no-cpu-baseline > $OUT/bench_default_nocpu.json 2> $OUT/bench_default.err
+python bench.py --full --no-cpu-baseline > $OUT/bench_default_nocpu.json 2> $OUT/bench_default.err
 kill $CPID; wait $CPID 2>/dev/null
 clocks > $OUT/clocks_driver_cmd.txt & CPID=$!
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd_nocpu.json 2>> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd_nocpu.json 2>> $OUT/bench_default.err
 kill $CPID; wait $CPID 2>/dev/null
-python bench.py > $OUT/bench_default.json 2>> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2>> $OUT/bench_default.err
 tail -c 700 $OUT/bench_default.json; echo
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2>> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2>> $OUT/bench_default.err
 python tools/launch_convergence.py cluster_s5 8192 5 64 > $OUT/convergence_headline.json 2> $OUT/convergence.err
 python tools/launch_convergence.py embodied_s12 8192 5 24 > $OUT/convergence_embodied.json 2>> $OUT/convergence.err
 rocm-smi --showclocks --showperflevel > $OUT/rocm_smi.txt 2>&1

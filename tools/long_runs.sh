@@ -4,10 +4,10 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=${1:-gpurun_out/long_runs.txt}
 mkdir -p $(dirname $OUT)
-echo "# long runs (python bench.py --steps 3000 --warmup 20 --no-extra --no-cpu-baseline --workload W --aa A): 8192 environments, 3020 steps each, the last step of 64 sampled environments compared with the oracle replayed through the same 3020 actions" > $OUT
+echo "# long runs (python bench.py --full --steps 3000 --warmup 20 --no-extra --no-cpu-baseline --workload W --aa A): 8192 environments, 3020 steps each, the last step of 64 sampled environments compared with the oracle replayed through the same 3020 actions" > $OUT
 for spec in "cluster_s5 1" "cluster_s5 5" "embodied_s12 5" "goal_s5 5"; do
   set -- $spec
-  python bench.py --steps 3000 --warmup 20 --no-extra --no-cpu-baseline --workload $1 --aa $2 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 3000 --warmup 20 --no-extra --no-cpu-baseline --workload $1 --aa $2 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('%s | build %s | %.2f M env-steps/s | verified %d mismatches %d frame bytes differing %d max abs diff %d steps replayed %d env_errors %d' % (

@@ -19,13 +19,16 @@ sys.path.insert(0, ROOT)
 from spriteworld_amd import build  # noqa: E402
 
 
+WORK_ROOT = '/tmp/swb_overlay'      # the patched copies, one directory per experiment name
+
+
 def replace_once(files, name, old, new, count=1):
   assert files[name].count(old) == count, '%s: anchor matches %d times (want %d): %r' % (name, files[name].count(old), count, old[:80])
   files[name] = files[name].replace(old, new)
 
 
 def make_copy(name, overlays):
-  work = os.path.join('/tmp/swb_overlay', name)
+  work = os.path.join(WORK_ROOT, name)
   shutil.rmtree(work, ignore_errors=True)
   csrc = os.path.join(work, 'csrc')
   shutil.copytree(build.CSRC, csrc, ignore=shutil.ignore_patterns('*.so', '*.o', '*.hash'))
