@@ -111,9 +111,12 @@ typedef struct swb_task {
 typedef struct swb_config {
   int32_t n_envs;             /* N                                                    */
   int32_t max_sprites;        /* S <= SWB_MAX_SPRITES (per-episode count may be less) */
-  int32_t image_h;            /* PILRenderer image_size[0]: a multiple of 4, <= 256   */
+  int32_t image_h;            /* PILRenderer image_size[0]: a multiple of 4, <= 1024  */
   int32_t image_w;            /* PILRenderer image_size[1]                            */
-  int32_t anti_aliasing;      /* PILRenderer anti_aliasing (>= 1; canvas width AA*image_size[0] <= 1023) */
+  int32_t anti_aliasing;      /* PILRenderer anti_aliasing (>= 1).  Canvas AA*image_size[0] x AA*image_size[1]:
+                               * the tuned kernels take canvases up to 640 px wide and images up to 256 columns;
+                               * larger frames (canvases up to 4096 px either way, images up to 1024 columns)
+                               * take the large-frame path (swb_variant_info::large_frames) */
   uint8_t bg_rgb[4];          /* PILRenderer bg_color (4th byte unused)               */
   int32_t action_space;       /* swb_action_space                                     */
   double action_scale;        /* SelectMove/DragAndDrop _scale ; Embodied _step_size  */
@@ -269,7 +272,8 @@ int swb_destroy(swb_handle h);
 int swb_upload_shapes(swb_handle h, const double* verts, const int32_t* offsets, int32_t n_shapes);
 
 /* PIL ImagingResample 8bpc coefficient tables for one axis (host-computed, see
- * spriteworld_amd/lanczos.py): bounds i32[out,2] (xmin,len), coeffs i32[out,ksize]. */
+ * spriteworld_amd/lanczos.py): bounds i32[out,2] (xmin,len), coeffs i32[out,ksize].  A large-frame handle keeps the
+ * tables as they are, with per-output prefix sums of the horizontal coefficients. */
 int swb_upload_resample(swb_handle h, int32_t axis /*0=horizontal,1=vertical*/, int32_t out_size,
                         int32_t ksize, const int32_t* bounds, const int32_t* coeffs);
 
@@ -318,7 +322,7 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream);
  * SWB_ENV_ERR_SPAN_OVERFLOW (never silent).  Results do not change.  Blocking (synchronises `stream`, reallocates); no-op when
  * called again.  swb_set_pool / swb_sample_pool restore the full reservation (the new pool may hold denser scenes).
  * run_cap_out (may be NULL): the units of a list's own part afterwards.  The Python engine calls it after its third
- * rendering step. */
+ * rendering step.  A large-frame handle (swb_variant_info::large_frames) has no run lists: a successful no-op, run_cap_out 0. */
 int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream);
 
 /* SpriteFactors observation (renderers/handcrafted.py:29-82): factors_dev f64[N,S,10] in
@@ -401,7 +405,10 @@ typedef struct swb_variant_info {
                                * itself and no second kernel is launched */
   int32_t arena_units;        /* units of the arena the run lists of all environments share for their overflow (0 until the first
                                * launch allocates it); a scene that finds it exhausted flags its environment */
-  int32_t reserved_;
+  int32_t large_frames;       /* 1: a frame the tuned kernels cannot take (canvas wider than 640 px, image wider than 256
+                               * columns; or SWB_LARGE_FRAMES=1 at swb_create): a step is the cover kernel's state phase
+                               * (nw = 2, obs = NULL) followed by swb_lf_raster_kernel (rasterisation + horizontal pass)
+                               * and swb_lf_vertical_kernel (vertical pass; not at anti_aliasing = 1); no run lists */
   int64_t run_list_bytes;     /* device memory of the hand-off lists: fixed parts + arena (0 until the first launch) */
 } swb_variant_info;
 int swb_variant(swb_handle h, swb_variant_info* out);

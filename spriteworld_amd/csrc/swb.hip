@@ -123,6 +123,14 @@ struct swb_engine {
   // read once at swb_create (never per launch): the device's compute units and the test / A-B switches of the environment
   int cus = 0;
   bool no_paint_in_cover = false, force_cover_order = false;
+  // large-frame path (canvases wider than the widest cover build, images wider than SWB_MAX_CG column groups; SWB_LARGE_FRAMES=1
+  // forces it): the cover kernel's state phase, then swb_lf_raster_kernel / swb_lf_vertical_kernel over a scratch buffer
+  bool large_frames = false;
+  size_t lf_scratch_budget = (size_t)256 << 20;   // bytes of horizontal-pass scratch: the batch is rendered in chunks that fit
+  int32_t *d_lf_hb = nullptr, *d_lf_hpo = nullptr, *d_lf_hp = nullptr, *d_lf_vb = nullptr, *d_lf_vk = nullptr;
+  int lf_vks = 0;
+  uint8_t* d_lf_tmp = nullptr;
+  size_t lf_tmp_bytes = 0;
   double timed_ms = 0.0, timed_cover_ms = 0.0;
   int64_t timed_launches = 0;
 };
@@ -316,7 +324,10 @@ int flush_timing(swb_engine* h) {
   return 0;
 }
 
+int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream);
+
 int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
+  if (h->large_frames) return launch_large(h, actions, out, render_only, stream);
   if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
   const swb_config& c = h->cfg;
@@ -432,6 +443,140 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Large-frame path (swb_engine::large_frames): the cover kernel of the narrowest build with obs = NULL -- its state phase
+// only, whose LDS does not depend on the canvas --, then the render kernels of swb_kernels.hip.inc on the state it left,
+// in chunks of environments whose horizontal-pass scratch fits lf_scratch_budget.
+// ---------------------------------------------------------------------------------------------------
+#define SWB_LF_MAX_CANVAS 4096        // canvas pixels in either direction
+#define SWB_LF_MAX_COLUMNS 1024       // image columns (image_size[0])
+
+int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
+  const size_t per_env = p.AA == 1 ? 0 : (size_t)p.Hc * p.Wo * 3;
+  long long chunk = per_env ? (long long)(h->lf_scratch_budget / per_env) : (long long)p.N;
+  chunk = std::max(1ll, std::min(chunk, std::min((long long)p.N, 65535ll)));       // (environments are a grid dimension)
+  if (per_env && h->lf_tmp_bytes < (size_t)chunk * per_env) {
+    if (h->d_lf_tmp) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(h->d_lf_tmp); h->d_lf_tmp = nullptr; h->lf_tmp_bytes = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_lf_tmp), (size_t)chunk * per_env));
+    h->lf_tmp_bytes = (size_t)chunk * per_env;
+  }
+  swb_lf_args a;
+  memset(&a, 0, sizeof(a));
+  a.hb = h->d_lf_hb; a.hpo = h->d_lf_hpo; a.hp = h->d_lf_hp; a.vb = h->d_lf_vb; a.vk = h->d_lf_vk; a.vks = h->lf_vks;
+  a.max_verts_env = std::max(p.max_edges, 4);
+  a.row_bytes = (p.Wc + 15) & ~15;
+  a.mask_words = p.Wc / 32 + 1;
+  a.rows_per_block = p.N >= 64 ? 64 : 16;        // (small batches: more workgroups per environment)
+  a.tmp = h->d_lf_tmp;
+  const size_t lds = swb_lf_head_bytes(a.max_verts_env) +
+                     (size_t)SWB_LF_WAVES * (a.row_bytes + 4 * (size_t)a.mask_words + 2 * 4 * SWB_LF_MAX_CROSS);
+  if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "large-frame raster kernel: LDS request %zu B exceeds 160 KiB", lds);
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(swb_lf_raster_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int nd = (p.Wo * 3) >> 2;
+  for (long long e0 = 0; e0 < p.N; e0 += chunk) {
+    a.e0 = (int32_t)e0;
+    a.ne = (int32_t)std::min(chunk, (long long)p.N - e0);
+    hipLaunchKernelGGL(swb_lf_raster_kernel, dim3((p.Hc + a.rows_per_block - 1) / a.rows_per_block, a.ne), dim3(SWB_WAVE * SWB_LF_WAVES),
+                       lds, stream, p, a);
+    HIP_TRY(hipGetLastError());
+    if (p.AA != 1) {
+      hipLaunchKernelGGL(swb_lf_vertical_kernel, dim3((nd + SWB_WAVE - 1) / SWB_WAVE, (p.Ho + SWB_LF_WAVES - 1) / SWB_LF_WAVES, a.ne),
+                         dim3(SWB_WAVE * SWB_LF_WAVES), 0, stream, p, a);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return 0;
+}
+
+int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
+  if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
+  if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
+  if (h->p.AA != 1 && !(h->have_h && h->have_v))
+    return fail(SWB_ERR_STATE, "swb_upload_resample (both axes) is required when anti_aliasing > 1");
+  if (!render_only && actions == nullptr) return fail(SWB_ERR_INVALID, "actions is NULL");
+  const variant* v = &kVariants[0];
+  swb_params p = h->p;
+  p.actions = actions;
+  p.obs = out ? out->obs : nullptr;
+  p.reward = out ? out->reward : nullptr;
+  p.discount = out ? out->discount : nullptr;
+  p.step_type = out ? out->step_type : nullptr;
+  p.success = out ? out->success : nullptr;
+  p.error = out ? out->error : nullptr;
+  p.render_only = render_only;
+  int cpath_in_masks = 0;
+  const size_t lds = lds_per_wave(h, v, &cpath_in_masks);
+  p.cpath_in_masks = cpath_in_masks;
+  p.lds_per_wave = (int32_t)lds;
+  p.outrow_bytes = (int32_t)v->outrow_bytes;
+  if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "LDS request %zu B exceeds 160 KiB", lds);
+  const kernel_fn fn = h->d_ov_flag ? v->fn_ov : v->fn;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  swb_engine::step_events ev = {nullptr, nullptr, nullptr};
+  if (h->timing) {
+    if (!h->event_pool.empty()) { ev = h->event_pool.back(); h->event_pool.pop_back(); }
+    else {
+      HIP_TRY(hipEventCreate(&ev.e0));
+      HIP_TRY(hipEventCreate(&ev.e1));
+      HIP_TRY(hipEventCreate(&ev.e2));
+    }
+    HIP_TRY(hipEventRecord(ev.e0, stream));
+  }
+  if (render_only != 1) {                      // the state phase (swb_render has no state to advance: the frame only)
+    swb_params pc = p;
+    pc.obs = nullptr;
+    hipLaunchKernelGGL(fn, dim3(p.N), dim3(SWB_WAVE), lds, stream, pc);
+    HIP_TRY(hipGetLastError());
+  }
+  if (h->timing) HIP_TRY(hipEventRecord(ev.e1, stream));
+  if (p.obs && render_only != 2)
+    if (int rc = lf_render(h, p, stream)) return rc;
+  if (h->timing) {
+    HIP_TRY(hipEventRecord(ev.e2, stream));
+    if (render_only == 2) { h->event_pool.push_back(ev); return 0; }     // (swb_evaluate: not a timed launch, as on the tuned path)
+    h->events.push_back(ev);
+    if (h->events.size() >= 4096) return flush_timing(h);
+  }
+  return 0;
+}
+
+// swb_upload_resample of a large-frame handle: the raw Pillow tables, and per output column the prefix sums of its
+// coefficients (the horizontal pass weighs a span of constant colour with one difference of two of them)
+int upload_resample_large(swb_engine* h, int axis, int out_size, int ksize, const int32_t* bounds, const int32_t* coeffs) {
+  const swb_params& p = h->p;
+  if (ksize < 1) return fail(SWB_ERR_INVALID, "ksize must be >= 1");
+  if (axis == 0) {
+    if (out_size != p.Wo) return fail(SWB_ERR_INVALID, "horizontal table has %d outputs, image width is %d", out_size, p.Wo);
+    std::vector<int32_t> hb(2 * (size_t)out_size), hpo(out_size), hp;
+    for (int o = 0; o < out_size; ++o) {
+      const int xmin = bounds[2 * o], cnt = bounds[2 * o + 1];
+      if (cnt < 0 || cnt > ksize || xmin < 0 || xmin + cnt > p.Wc) return fail(SWB_ERR_INVALID, "bad horizontal bounds at %d", o);
+      hb[2 * o] = xmin; hb[2 * o + 1] = cnt;
+      hpo[o] = (int32_t)hp.size();
+      int32_t acc = 0;
+      hp.push_back(0);
+      for (int j = 0; j < cnt; ++j) { acc += coeffs[(size_t)o * ksize + j]; hp.push_back(acc); }
+    }
+    if (upload(&h->d_lf_hb, hb.data(), hb.size()) || upload(&h->d_lf_hpo, hpo.data(), hpo.size()) || upload(&h->d_lf_hp, hp.data(), hp.size()))
+      return SWB_ERR_HIP;
+    h->have_h = true;
+  } else if (axis == 1) {
+    if (out_size != p.Ho) return fail(SWB_ERR_INVALID, "vertical table has %d outputs, image height is %d", out_size, p.Ho);
+    for (int r = 0; r < out_size; ++r) {
+      const int ymin = bounds[2 * r], cnt = bounds[2 * r + 1];
+      if (cnt < 0 || cnt > ksize || ymin < 0 || ymin + cnt > p.Hc) return fail(SWB_ERR_INVALID, "bad vertical bounds at %d", r);
+    }
+    if (upload(&h->d_lf_vb, bounds, 2 * (size_t)out_size) || upload(&h->d_lf_vk, coeffs, (size_t)out_size * ksize)) return SWB_ERR_HIP;
+    h->lf_vks = ksize;
+    h->have_v = true;
+  } else {
+    return fail(SWB_ERR_INVALID, "axis must be 0 or 1");
+  }
+  return SWB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -487,9 +632,24 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     for (int k = 1; k < tk.n_ycuts; ++k) if (!(tk.ycuts[k - 1] < tk.ycuts[k])) { delete h; return fail(SWB_ERR_INVALID, "task %d: ycuts must ascend", t); }
     if (tk.n_xcuts + tk.n_ycuts > 0) h->keyed = true;
   }
-  if (p.Wc > 1023 || p.Hc > 65535) { delete h; return fail(SWB_ERR_INVALID, "canvas %dx%d too large", p.Wc, p.Hc); }
-  if (!pick_variant(p.Wc)) { delete h; return fail(SWB_ERR_INVALID, "canvas width %d not supported", p.Wc); }
-  if (p.Wo > 64 * SWB_MAX_CG) { delete h; return fail(SWB_ERR_INVALID, "image width %d not supported (max %d)", p.Wo, 64 * SWB_MAX_CG); }
+  // frames the tuned kernels cannot take (a canvas wider than the widest cover build, more than SWB_MAX_CG column groups) go
+  // the large-frame path; SWB_LARGE_FRAMES=1 (tests) sends every geometry there
+  {
+    const char* lf = getenv("SWB_LARGE_FRAMES");
+    h->large_frames = !pick_variant(p.Wc) || p.Wo > 64 * SWB_MAX_CG || (lf && atoi(lf) != 0);
+    if (const char* x = getenv("SWB_LF_SCRATCH_BYTES")) h->lf_scratch_budget = (size_t)std::max(1ll, atoll(x));   // tests: force chunks
+  }
+  if (h->large_frames) {
+    if (p.Wc > SWB_LF_MAX_CANVAS || p.Hc > SWB_LF_MAX_CANVAS) {
+      delete h;
+      return fail(SWB_ERR_INVALID, "canvas %dx%d too large: at most %d px in either direction (anti_aliasing * image_size)", p.Wc, p.Hc,
+                  SWB_LF_MAX_CANVAS);
+    }
+    if (p.Wo > SWB_LF_MAX_COLUMNS) { delete h; return fail(SWB_ERR_INVALID, "image width %d too large: at most %d columns", p.Wo, SWB_LF_MAX_COLUMNS); }
+  } else if (p.Hc > 65535) {
+    delete h;
+    return fail(SWB_ERR_INVALID, "canvas %dx%d too large", p.Wc, p.Hc);
+  }
   // Bands of output rows per (environment, column group) in the second kernel: a band repeats the 25 canvas rows it
   // shares with the band above, so there are only as many as it takes to give every SIMD its eight waves (small
   // batches), in bands of at least 16 rows -- of 8 rows where those fill the SIMDs no more than once (measured, 64-px images:
@@ -509,7 +669,7 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   // costs 1 unit (one span), 2 (two or three) or more, and rows that repeat the row above nothing); the range they span is
   // fitted by every launch (cost_housekeeping), to begin with it is [0, 8 * canvas height)
   p.cost_range0 = std::max(8 * p.Hc, SWB_KEY_BUCKETS_FITTED);      // (a run and its units cost 5 .. 9; a launch later the range is a measured one)
-  if (!getenv("SWB_NO_COST_ORDER") && p.N < (1 << 24)) {
+  if (!getenv("SWB_NO_COST_ORDER") && p.N < (1 << 24) && !h->large_frames) {
     // Small batches in several bands: a task of the second kernel is one BAND of a list, filed under the band's own cost, once
     // the launch has four waves or more per SIMD to deal (measured, resample / fill kernel: 2048 environments in 4 bands -9.5 %,
     // 1024 -2 %, a 128x128 image at anti_aliasing = 1 -22 %; two waves per SIMD, 256 environments in 8 bands, +3 %:
@@ -604,7 +764,8 @@ int swb_destroy(swb_handle h) {
                   h->d_p_shape, h->d_p_rgb, h->d_p_label, h->d_p_cell_label, h->d_ov_cell_label, h->d_p_attr, h->d_pool_base, h->d_pool_len, h->d_x, h->d_y, h->d_nspr,
                   h->d_entry, h->d_step_count, h->d_episode, h->d_reset_next, h->d_ovf, h->d_ovf_bitmap, h->d_p_angle, h->d_p_color, h->d_sampler,
                   h->d_ov_flag, h->d_ov_shape, h->d_ov_scale, h->d_ov_angle, h->d_ov_cpath, h->d_ov_label,
-                  h->d_cost_cnt, h->d_cost_list, h->d_ccost_list, h->d_runs, h->d_rhdr, h->d_arena_head, h->d_env_state, h->d_band_y0, h->d_band_first, h->d_band_lo, h->d_cg_lo, h->d_cg_hi, h->d_v_break};
+                  h->d_cost_cnt, h->d_cost_list, h->d_ccost_list, h->d_runs, h->d_rhdr, h->d_arena_head, h->d_env_state, h->d_band_y0, h->d_band_first, h->d_band_lo, h->d_cg_lo, h->d_cg_hi, h->d_v_break,
+                  h->d_lf_hb, h->d_lf_hpo, h->d_lf_hp, h->d_lf_vb, h->d_lf_vk, h->d_lf_tmp};
   for (void* b : bufs) if (b) (void)hipFree(b);
   delete h;
   return SWB_OK;
@@ -653,6 +814,7 @@ int swb_upload_resample(swb_handle h, int32_t axis, int32_t out_size, int32_t ks
                         const int32_t* coeffs) {
   if (!h || !bounds || !coeffs) return fail(SWB_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(h->device));
+  if (h->large_frames) return upload_resample_large(h, axis, out_size, ksize, bounds, coeffs);
   const swb_params& p = h->p;
   if (axis == 0) {
     if (out_size != p.Wo) return fail(SWB_ERR_INVALID, "horizontal table has %d outputs, image width is %d", out_size, p.Wo);
@@ -999,6 +1161,10 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream) {
 int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   HIP_TRY(hipSetDevice(h->device));
+  if (h->large_frames) {                 // (no run lists on the large-frame path: nothing to trim)
+    if (run_cap_out) *run_cap_out = 0;
+    return SWB_OK;
+  }
   if (run_cap_out) *run_cap_out = h->p.run_cap;
   if (h->lists_trimmed || getenv("SWB_RUN_CAP") || getenv("SWB_NO_TRIM")) return SWB_OK;   // (done already / a test pinned the capacity)
   if (!h->d_runs && h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1) return SWB_OK;      // (the cover kernel paints the frame: no lists at all)
@@ -1312,6 +1478,21 @@ int swb_get_sprite(swb_handle h, int32_t env, int32_t sprite, int32_t* shape, do
 
 int swb_variant(swb_handle h, swb_variant_info* out) {
   if (!h || !out) return fail(SWB_ERR_INVALID, "null argument");
+  if (h->large_frames) {                 // the narrowest cover build (state phase only), then the large-frame render kernels
+    const variant* v0 = &kVariants[0];
+    out->nw = v0->nw; out->ncol = 1; out->vs = 0;
+    out->lds_bytes_per_wave = (int32_t)lds_per_wave(h, v0, nullptr);
+    out->waves_per_simd = SWB_COVER_WAVES(v0->nw);
+    out->resample_waves_per_simd = 0;
+    out->n_bands = 0;
+    out->n_column_groups = 0;
+    out->run_cap = 0;
+    out->paint_in_cover = 0;
+    out->arena_units = 0;
+    out->large_frames = 1;
+    out->run_list_bytes = 0;
+    return SWB_OK;
+  }
   const variant* v = pick_variant(h->p.Wc);
   if (!v) return fail(SWB_ERR_INVALID, "canvas %dx%d not supported", h->p.Wc, h->p.Hc);
   int vs = 0;
@@ -1325,7 +1506,7 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
   out->run_cap = h->p.run_cap;
   out->paint_in_cover = (h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1 && !h->no_paint_in_cover) ? 1 : 0;
   out->arena_units = h->d_runs ? h->p.arena_units : 0;
-  out->reserved_ = 0;
+  out->large_frames = 0;
   out->run_list_bytes = h->d_runs ? ((int64_t)h->p.arena_base + h->p.arena_units + 4) * 8 : 0;
   return SWB_OK;
 }

@@ -2432,4 +2432,332 @@ __global__ void swb_factors_kernel(const swb_params p, double* out) {
   o[7] = p.p_color ? p.p_color[3 * pe + 2] : 0.0;
   o[8] = p.p_xv[pe]; o[9] = p.p_yv[pe];
 }
+
+// --------------------------------------------------------------------------------------------
+// Large-frame path: canvases wider than the widest cover build (640 px) and images wider than SWB_MAX_CG column groups.
+// The cover kernel runs its state phase only (obs = NULL); then
+//   swb_lf_raster_kernel    one workgroup of SWB_LF_WAVES waves per (environment, block of canvas rows).  The workgroup
+//                           builds every sprite's Pillow edges once (LDS); a wave then takes one canvas row at a time:
+//                           polygon_generic of every sprite, back to front, paints sprite ids into a byte row in LDS, and
+//                           the horizontal LANCZOS pass walks the constant-colour spans of the row inside each output
+//                           column's window: colour x (prefix[end] - prefix[start]), exact integers.  uint8 result ->
+//                           scratch [envs of the chunk][Hc][Wo][3].  anti_aliasing = 1: the row is the image row, stored
+//                           flipped straight into obs.
+//   swb_lf_vertical_kernel  lanes = 4-byte words of an output row: the vertical pass over the scratch rows, flipped into obs.
+// Arithmetic is oracle/sw_oracle.c's draw_polygon / resample_lanczos, operation for operation.
+// --------------------------------------------------------------------------------------------
+#define SWB_LF_WAVES 4
+#define SWB_LF_MAX_CROSS (2 * SWB_MAX_SHAPE_VERTS)   // crossings of one sprite on one row (an edge may count twice)
+
+struct swb_lf_args {
+  const int32_t* hb;           // [Wo][2] horizontal windows (xmin, count)
+  const int32_t* hpo;          // [Wo] offset of output column o's prefix sums in hp
+  const int32_t* hp;           // per output column: count + 1 prefix sums of its coefficients
+  const int32_t* vb;           // [Ho][2] vertical windows (ymin, count)
+  const int32_t* vk;           // [Ho][vks] vertical coefficients
+  int32_t vks;
+  int32_t e0, ne;              // environments [e0, e0 + ne) of this chunk
+  int32_t rows_per_block;      // canvas rows per workgroup of the raster kernel
+  int32_t max_verts_env;       // vertex capacity of the workgroup's LDS tables (swb_params::max_edges)
+  int32_t row_bytes;           // LDS bytes of a wave's row buffer (Wc rounded up)
+  int32_t mask_words;          // ... of its span-boundary bit mask (Wc / 32 + 1: bit Wc is a sentinel)
+  uint8_t* tmp;                // [ne][Hc][Wo][3] horizontal pass (anti_aliasing > 1)
+};
+
+struct swb_lf_xy { int32_t x, y; };
+
+struct swb_lf_edge {           // Draw.c Edge (x0, y0 as given; ymin > ymax: not an edge)
+  int32_t x0, y0, xmin, xmax, ymin, ymax;
+  float dx;
+  int32_t pad;
+};
+
+struct swb_lf_block {          // workgroup-shared head of the raster kernel's LDS
+  uint32_t col[SWB_MAX_SPRITES + 1];   // 0: background, s + 1: sprite s
+  int32_t n, vtotal, err, pad0;
+  int32_t voff[SWB_MAX_SPRITES], nv[SWB_MAX_SPRITES], so[SWB_MAX_SPRITES];
+  int32_t ymin[SWB_MAX_SPRITES], ymax[SWB_MAX_SPRITES], ymaxc[SWB_MAX_SPRITES];
+  double px[SWB_MAX_SPRITES], py[SWB_MAX_SPRITES], sc[SWB_MAX_SPRITES], ca[SWB_MAX_SPRITES], sa[SWB_MAX_SPRITES];
+};
+
+__host__ __device__ __forceinline__ size_t swb_lf_head_bytes(int max_verts) {
+  return ((sizeof(swb_lf_block) + 15) & ~(size_t)15) + (size_t)max_verts * 8 + (size_t)max_verts * sizeof(swb_lf_edge);
+}
+
+// Index of the lowest set bit of a non-zero 64-bit mask.
+__device__ __forceinline__ int swb_lf_first_lane(unsigned long long m) {
+  const uint32_t lo = (uint32_t)m;
+  return lo ? __ffs((int)lo) - 1 : 31 + __ffs((int)(uint32_t)(m >> 32));
+}
+
+// Draw.c hline clipping: [x0, x1] on a row of W pixels; false when nothing is drawn.
+__device__ __forceinline__ bool swb_lf_clip(int& x0, int& x1, int W) {
+  if (x0 < 0) x0 = 0;
+  else if (x0 >= W) return false;
+  if (x1 < 0) return false;
+  if (x1 >= W) x1 = W - 1;
+  return x0 <= x1;
+}
+
+__global__ void __launch_bounds__(SWB_WAVE * SWB_LF_WAVES)
+swb_lf_raster_kernel(const swb_params p, const swb_lf_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x, l = lane_id(), wave = rfl(t >> 6);
+  const int env = a.e0 + (int)blockIdx.y, S = p.S;
+  const int Wc = p.Wc, Hc = p.Hc;
+  swb_lf_block* B = reinterpret_cast<swb_lf_block*>(smem);
+  swb_lf_xy* verts = reinterpret_cast<swb_lf_xy*>(smem + ((sizeof(swb_lf_block) + 15) & ~(size_t)15));
+  swb_lf_edge* edges = reinterpret_cast<swb_lf_edge*>(verts + a.max_verts_env);
+  unsigned char* wbase = smem + swb_lf_head_bytes(a.max_verts_env) +
+                         (size_t)wave * (a.row_bytes + 4 * a.mask_words + 2 * 4 * SWB_LF_MAX_CROSS);
+  unsigned char* row = wbase;                                            // sprite id + 1 per canvas pixel (0: background)
+  uint32_t* bmask = reinterpret_cast<uint32_t*>(wbase + a.row_bytes);  // bit x: pixel x starts a span (x = Wc: sentinel)
+  float* xs = reinterpret_cast<float*>(bmask + a.mask_words);          // crossings of a row, in edge order
+  float* srt = xs + SWB_LF_MAX_CROSS;                                  // ... sorted
+
+  // ---- the environment's sprites (the state the cover kernel's state phase left): pool entry or setter overrides
+  const bool ov = p.ov_flag != nullptr && p.ov_flag[env] != 0;
+  const int n = p.nspr[env];
+  const size_t pe = (size_t)p.entry[env] * S;
+  if (t == 0) { B->col[0] = p.bg; B->n = n; B->err = 0; }
+  if (t < n) {
+    int sh = ov ? p.ov_shape[(size_t)env * S + t] : p.p_shape[pe + t];
+    sh = min(max(sh, 0), SWB_MAX_SHAPES - 1);
+    B->so[t] = p.shape_off[sh];
+    B->nv[t] = p.shape_off[sh + 1] - p.shape_off[sh];
+    B->col[t + 1] = p.p_rgb[pe + t];
+    B->px[t] = p.x[(size_t)env * S + t]; B->py[t] = p.y[(size_t)env * S + t];
+    B->sc[t] = p.p_scale[pe + t]; B->ca[t] = p.p_ca[pe + t]; B->sa[t] = p.p_sa[pe + t];
+  }
+  __syncthreads();
+  if (t == 0) {
+    int tot = 0;
+    for (int s = 0; s < n; ++s) {
+      if (tot + B->nv[s] > a.max_verts_env) { B->n = s; B->err = SWB_ENV_ERR_SPAN_OVERFLOW; break; }   // (cannot happen: sized by the pool)
+      B->voff[s] = tot;
+      tot += B->nv[s];
+    }
+    B->vtotal = tot;
+  }
+  __syncthreads();
+  const int ns = B->n, vtotal = B->vtotal;
+  // vertices -> canvas ints: sprite.py:131-133 translate, then (int)(canvas size * v) (C truncation)
+  for (int k = t; k < vtotal; k += blockDim.x) {
+    int sid = 0;
+    for (int s = 1; s < ns; ++s) if (k >= B->voff[s]) sid = s;
+    const int i = k - B->voff[sid];
+    double cx, cy;
+    if (ov) {
+      const double* q = p.ov_cpath + (((size_t)env * S + sid) * SWB_MAX_SHAPE_VERTS + i) * 2;
+      cx = q[0]; cy = q[1];
+    } else {
+      centered_vertex(p, B->so[sid], i, B->sc[sid], B->ca[sid], B->sa[sid], cx, cy);
+    }
+    const double vx = __dadd_rn(__dadd_rn(__dmul_rn(1.0, cx), __dmul_rn(0.0, cy)), B->px[sid]);
+    const double vy = __dadd_rn(__dadd_rn(__dmul_rn(0.0, cx), __dmul_rn(1.0, cy)), B->py[sid]);
+    verts[k] = swb_lf_xy{(int)__dmul_rn((double)Wc, vx), (int)__dmul_rn((double)Hc, vy)};
+  }
+  __syncthreads();
+  // Draw.c add_edge: edge i joins vertex i and i + 1; the closing edge only if the last vertex differs from the first
+  for (int k = t; k < vtotal; k += blockDim.x) {
+    int sid = 0;
+    for (int s = 1; s < ns; ++s) if (k >= B->voff[s]) sid = s;
+    const int vb = B->voff[sid], nv = B->nv[sid], i = k - vb;
+    const swb_lf_xy f = verts[vb], g = verts[vb + nv - 1];
+    const int ne = (g.x != f.x || g.y != f.y) ? nv : nv - 1;
+    swb_lf_edge e;
+    e.pad = 0;
+    if (i < ne) {
+      const swb_lf_xy v0 = verts[k], v1 = verts[(i + 1 == nv) ? vb : k + 1];
+      e.x0 = v0.x; e.y0 = v0.y;
+      e.xmin = min(v0.x, v1.x); e.xmax = max(v0.x, v1.x);
+      e.ymin = min(v0.y, v1.y); e.ymax = max(v0.y, v1.y);
+      e.dx = (v0.y == v1.y) ? 0.0f : __fdiv_rn((float)(v1.x - v0.x), (float)(v1.y - v0.y));
+    } else {
+      e.x0 = e.y0 = e.xmin = e.xmax = 0; e.ymin = 1; e.ymax = 0; e.dx = 0.0f;
+    }
+    edges[k] = e;
+  }
+  __syncthreads();
+  // rows a sprite's scan visits: Draw.c starts ymin at ysize - 1 and ymax at 0, clamps ymin to 0 and ymax to ysize
+  // (the rows themselves are those with an edge on them: ymin only starts the loop, ymax also decides the duplicated crossing)
+  if (t < ns) {
+    int lo = 0x7fffffff, hi = -0x7fffffff;
+    for (int k = B->voff[t]; k < B->voff[t] + B->nv[t]; ++k) {
+      const swb_lf_edge e = edges[k];
+      if (e.ymin > e.ymax) continue;
+      lo = min(lo, e.ymin); hi = max(hi, e.ymax);
+    }
+    B->ymin[t] = lo; B->ymax[t] = hi;
+    B->ymaxc[t] = min(max(hi, 0), Hc);
+  }
+  __syncthreads();
+  if (t == 0 && blockIdx.x == 0 && B->err && p.error) p.error[env] |= (uint8_t)B->err;
+
+  const int y_lo = (int)blockIdx.x * a.rows_per_block, y_hi = min(y_lo + a.rows_per_block, Hc);
+  const int Wo = p.Wo, Ho = p.Ho;
+  const unsigned long long below = (1ull << l) - 1ull;
+  for (int y = y_lo + wave; y < y_hi; y += SWB_LF_WAVES) {
+    // canvas.paste(bg)
+    for (int w = l; w < (a.row_bytes >> 2); w += SWB_WAVE) reinterpret_cast<uint32_t*>(row)[w] = 0u;
+    wave_sync();
+    for (int s = 0; s < ns; ++s) {                            // back to front (pil_renderer.py:80-83)
+      if (y < B->ymin[s] || y > B->ymax[s]) continue;         // (wave-uniform) no edge of the sprite on this row
+      const int eo = B->voff[s], ne = B->nv[s], ymaxc = B->ymaxc[s];
+      const unsigned char id = (unsigned char)(s + 1);
+      // lane i = edge i of the sprite (at most SWB_MAX_SHAPE_VERTS)
+      swb_lf_edge cur;
+      cur.ymin = 1; cur.ymax = 0; cur.dx = 0.0f; cur.x0 = cur.y0 = cur.xmin = cur.xmax = 0;
+      if (l < ne) cur = edges[eo + l];
+      const bool horiz = cur.ymin == cur.ymax;
+      int hx0 = cur.xmin, hx1 = cur.xmax;
+      const bool hline_l = horiz && y == cur.ymin && swb_lf_clip(hx0, hx1, Wc);   // horizontal edges: drawn as they are
+      int cnt = 0;
+      float xx = 0.0f;
+      if (!horiz && y >= cur.ymin && y <= cur.ymax) {
+        xx = pil_cross(y, cur.y0, cur.dx, cur.x0);
+        cnt = 1;
+        if (y == cur.ymax && y < ymaxc) {
+          cnt = 2;                                            // "needed to draw consistent polygons"
+        } else if (cur.dx != 0.0f && (y == cur.ymin || y == cur.ymax)) {
+          // connect discontiguous corners: the first EARLIER edge of the table that also ends on this row
+          const int adj = (y == cur.ymax) ? y - 1 : y + 1;
+          for (int k = 0; k < l; ++k) {
+            const swb_lf_edge o = edges[eo + k];
+            if (o.ymin >= o.ymax) continue;                    // (horizontal edges are not in the table)
+            if ((y != o.ymin && y != o.ymax) || o.dx == 0.0f) continue;
+            if (roundf(xx) != roundf(pil_cross(y, o.y0, o.dx, o.x0))) continue;
+            if (adj < o.ymin || adj > o.ymax) continue;
+            const float ca = pil_cross(adj, cur.y0, cur.dx, cur.x0);
+            const float cb = pil_cross(adj, o.y0, o.dx, o.x0);
+            if (xx > __fadd_rn(ca, 1.0f) && xx > __fadd_rn(cb, 1.0f))
+              xx = __fadd_rn(roundf(fmaxf(ca, cb)), 1.0f);
+            else if (xx < __fsub_rn(ca, 1.0f) && xx < __fsub_rn(cb, 1.0f))
+              xx = __fsub_rn(roundf(fminf(ca, cb)), 1.0f);
+            break;
+          }
+        }
+      }
+      // crossings in edge order -> LDS, sorted by rank (ties keep their order: equal values are interchangeable)
+      const unsigned long long m1 = __ballot(cnt >= 1), m2 = __ballot(cnt == 2);
+      const int pos = __popcll(m1 & below) + __popcll(m2 & below);
+      const int j = __popcll(m1) + __popcll(m2);
+      if (cnt >= 1) xs[pos] = xx;
+      if (cnt == 2) xs[pos + 1] = xx;
+      wave_sync();
+      if (cnt >= 1) {
+        int r = 0;
+        for (int m = 0; m < j; ++m) {
+          const float v = xs[m];
+          r += (v < xx || (v == xx && m < pos)) ? 1 : 0;
+        }
+        srt[r] = xx;
+        if (cnt == 2) srt[r + 1] = xx;
+      }
+      wave_sync();
+      // pairs: hline(ROUND_UP(xx[2i]), y, ROUND_DOWN(xx[2i + 1]))
+      int fx0 = 0, fx1 = -1;
+      bool fill_l = false;
+      if (2 * l + 1 < j) {
+        fx0 = pil_round_up(srt[2 * l]);
+        fx1 = pil_round_down(srt[2 * l + 1]);
+        fill_l = swb_lf_clip(fx0, fx1, Wc);
+      }
+      for (int pass = 0; pass < 2; ++pass) {
+        unsigned long long m = __ballot(pass == 0 ? hline_l : fill_l);
+        while (m) {
+          const int src = swb_lf_first_lane(m);
+          const int x0 = __builtin_amdgcn_readlane(pass == 0 ? hx0 : fx0, src);
+          const int x1 = __builtin_amdgcn_readlane(pass == 0 ? hx1 : fx1, src);
+          for (int x = x0 + l; x <= x1; x += SWB_WAVE) row[x] = id;
+          m &= m - 1ull;
+        }
+      }
+      wave_sync();
+    }
+    if (p.AA == 1) {
+      // the canvas is the image (pil_renderer.py:84 resizes to the same size): np.flipud into obs, 4-byte words
+      const int nd = (Wo * 3) >> 2;
+      uint32_t* dst = reinterpret_cast<uint32_t*>(p.obs + ((size_t)env * Ho + (size_t)(Ho - 1 - y)) * (size_t)Wo * 3);
+      for (int d = l; d < nd; d += SWB_WAVE) {
+        uint32_t w = 0u;
+        for (int b = 0; b < 4; ++b) {
+          const int byte = 4 * d + b, px = byte / 3, ch = byte - 3 * px;
+          w |= ((B->col[row[px]] >> (8 * ch)) & 255u) << (8 * b);
+        }
+        dst[d] = w;
+      }
+      wave_sync();
+      continue;
+    }
+    // span starts of the row (bit x: pixel x differs from pixel x - 1; bit Wc ends the last span)
+    for (int w = l; w < a.mask_words; w += SWB_WAVE) {
+      uint32_t bits = 0u;
+      const int xb = 32 * w;
+      int prev = (xb >= 1 && xb - 1 < Wc) ? row[xb - 1] : -1;
+      for (int b = 0; b < 32; ++b) {
+        const int x = xb + b;
+        if (x > Wc) break;
+        if (x == Wc) { bits |= 1u << b; break; }
+        const int c = row[x];
+        if (x >= 1 && c != prev) bits |= 1u << b;
+        prev = c;
+      }
+      bmask[w] = bits;
+    }
+    wave_sync();
+    // horizontal pass (Resample.c, 8 bpc): output column o sums colour x coefficient over the spans inside its window
+    uint8_t* out_row = a.tmp + ((size_t)(env - a.e0) * Hc + (size_t)y) * (size_t)Wo * 3;
+    for (int o = l; o < Wo; o += SWB_WAVE) {
+      const int xmin = as_const(a.hb)[2 * o], xend = xmin + as_const(a.hb)[2 * o + 1];
+      cptr<int32_t> pf = as_const(a.hp) + as_const(a.hpo)[o];
+      int s0 = SWB_HALF, s1 = SWB_HALF, s2 = SWB_HALF;
+      int x = xmin, wlo = 0;
+      while (x < xend) {
+        // next span start after x (the sentinel at Wc bounds the search)
+        int wi = (x + 1) >> 5;
+        uint32_t bits = bmask[wi] & (0xffffffffu << ((x + 1) & 31));
+        while (bits == 0u && 32 * (wi + 1) < xend) bits = bmask[++wi];
+        int nx = bits ? 32 * wi + __ffs((int)bits) - 1 : xend;
+        nx = min(nx, xend);
+        const int whi = pf[nx - xmin];
+        const int k = whi - wlo;
+        const uint32_t c = B->col[row[x]];
+        s0 += (int)(c & 255u) * k; s1 += (int)((c >> 8) & 255u) * k; s2 += (int)((c >> 16) & 255u) * k;
+        wlo = whi;
+        x = nx;
+      }
+      out_row[3 * o] = (uint8_t)clip8_fix(s0);
+      out_row[3 * o + 1] = (uint8_t)clip8_fix(s1);
+      out_row[3 * o + 2] = (uint8_t)clip8_fix(s2);
+    }
+    wave_sync();
+  }
+}
+
+// Vertical pass + np.flipud: lanes = 4-byte words of output row r (wave-uniform), its window of scratch rows.
+__global__ void __launch_bounds__(SWB_WAVE * SWB_LF_WAVES)
+swb_lf_vertical_kernel(const swb_params p, const swb_lf_args a) {
+  const int wave = rfl(threadIdx.x >> 6);
+  const int r = (int)blockIdx.y * SWB_LF_WAVES + wave;
+  const int env = a.e0 + (int)blockIdx.z;
+  const int nd = (p.Wo * 3) >> 2;
+  const int d = (int)blockIdx.x * SWB_WAVE + lane_id();
+  if (r >= p.Ho || d >= nd) return;
+  const int ymin = as_const(a.vb)[2 * r], cnt = as_const(a.vb)[2 * r + 1];
+  cptr<int32_t> k = as_const(a.vk) + (size_t)r * a.vks;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tmp + (size_t)(env - a.e0) * p.Hc * (size_t)p.Wo * 3) +
+                        (size_t)ymin * nd + d;
+  int s0 = SWB_HALF, s1 = SWB_HALF, s2 = SWB_HALF, s3 = SWB_HALF;
+  for (int i = 0; i < cnt; ++i) {
+    const uint32_t w = src[(size_t)i * nd];
+    const int c = k[i];
+    s0 += (int)(w & 255u) * c; s1 += (int)((w >> 8) & 255u) * c;
+    s2 += (int)((w >> 16) & 255u) * c; s3 += (int)(w >> 24) * c;
+  }
+  const uint32_t out = (uint32_t)clip8_fix(s0) | ((uint32_t)clip8_fix(s1) << 8) | ((uint32_t)clip8_fix(s2) << 16) |
+                       ((uint32_t)clip8_fix(s3) << 24);
+  reinterpret_cast<uint32_t*>(p.obs + ((size_t)env * p.Ho + (size_t)(p.Ho - 1 - r)) * (size_t)p.Wo * 3)[d] = out;
+}
+
 #endif  // SWB_WIDE_TU
