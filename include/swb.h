@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define SWB_MAX_SPRITES 16   /* per environment                                 */
+#define SWB_MAX_SPRITES 64   /* per environment: one lane of a wave per sprite. Handles of up to 16 sprites run the tuned
+                              * kernels; more take the many-sprite path (swb_variant_info::many_sprites) */
 #define SWB_MAX_TASKS 8      /* sub-tasks of a MetaAggregated task              */
 #define SWB_MAX_SHAPES 32
 #define SWB_MAX_SHAPE_VERTS 64 /* per shape (reference max is 30, the "circle") */
@@ -110,7 +111,7 @@ typedef struct swb_task {
 
 typedef struct swb_config {
   int32_t n_envs;             /* N                                                    */
-  int32_t max_sprites;        /* S <= SWB_MAX_SPRITES (per-episode count may be less) */
+  int32_t max_sprites;        /* S <= SWB_MAX_SPRITES (per-episode count may be less); S > 16 takes the many-sprite path */
   int32_t image_h;            /* PILRenderer image_size[0]: a multiple of 4, <= 1024  */
   int32_t image_w;            /* PILRenderer image_size[1]                            */
   int32_t anti_aliasing;      /* PILRenderer anti_aliasing (>= 1).  Canvas AA*image_size[0] x AA*image_size[1]:
@@ -409,6 +410,10 @@ typedef struct swb_variant_info {
                                * columns; or SWB_LARGE_FRAMES=1 at swb_create): a step is the cover kernel's state phase
                                * (nw = 2, obs = NULL) followed by swb_lf_raster_kernel (rasterisation + horizontal pass)
                                * and swb_lf_vertical_kernel (vertical pass; not at anti_aliasing = 1); no run lists */
+  int32_t many_sprites;       /* 1: more than 16 sprites (or SWB_MANY_SPRITES=1 at swb_create): the state phase is
+                               * swb_ms_state_kernel (one wave per environment, lane s = sprite s), the frame is rendered by
+                               * the large-frame kernels (large_frames is 1 too); no run lists */
+  int32_t reserved_;
   int64_t run_list_bytes;     /* device memory of the hand-off lists: fixed parts + arena (0 until the first launch) */
 } swb_variant_info;
 int swb_variant(swb_handle h, swb_variant_info* out);

@@ -1,7 +1,8 @@
 """ctypes mirror of include/swb.h (struct layouts and enums of the C ABI)."""
 import ctypes as C
 
-SWB_MAX_SPRITES = 16
+SWB_MAX_SPRITES = 64
+SWB_TUNED_SPRITES = 16      # handles of more sprites take the many-sprite path (swb_variant_info::many_sprites)
 SWB_MAX_TASKS = 8
 SWB_MAX_SHAPES = 32
 SWB_MAX_SHAPE_VERTS = 64
@@ -117,7 +118,8 @@ class SwbVariantInfo(C.Structure):
   _fields_ = [('nw', C.c_int32), ('ncol', C.c_int32), ('vs', C.c_int32), ('lds_bytes_per_wave', C.c_int32),
               ('waves_per_simd', C.c_int32), ('resample_waves_per_simd', C.c_int32), ('n_bands', C.c_int32),
               ('n_column_groups', C.c_int32), ('run_cap', C.c_int32), ('paint_in_cover', C.c_int32),
-              ('arena_units', C.c_int32), ('large_frames', C.c_int32), ('run_list_bytes', C.c_int64)]
+              ('arena_units', C.c_int32), ('large_frames', C.c_int32), ('many_sprites', C.c_int32), ('reserved_', C.c_int32),
+              ('run_list_bytes', C.c_int64)]
 
 
 FACTOR_UNIFORM_F32, FACTOR_UNIFORM_INT, FACTOR_DISCRETE = 0, 1, 2

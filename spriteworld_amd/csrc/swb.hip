@@ -126,6 +126,9 @@ struct swb_engine {
   // large-frame path (canvases wider than the widest cover build, images wider than SWB_MAX_CG column groups; SWB_LARGE_FRAMES=1
   // forces it): the cover kernel's state phase, then swb_lf_raster_kernel / swb_lf_vertical_kernel over a scratch buffer
   bool large_frames = false;
+  // many-sprite path (more than SWB_TUNED_SPRITES sprites; SWB_MANY_SPRITES=1 forces it): swb_ms_state_kernel, then the
+  // large-frame render kernels (large_frames is set too)
+  bool many_sprites = false;
   size_t lf_scratch_budget = (size_t)256 << 20;   // bytes of horizontal-pass scratch: the batch is rendered in chunks that fit
   int32_t *d_lf_hb = nullptr, *d_lf_hpo = nullptr, *d_lf_hp = nullptr, *d_lf_vb = nullptr, *d_lf_vk = nullptr;
   int lf_vks = 0;
@@ -451,6 +454,24 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
 #define SWB_LF_MAX_CANVAS 4096        // canvas pixels in either direction
 #define SWB_LF_MAX_COLUMNS 1024       // image columns (image_size[0])
 
+// LDS of a workgroup of the raster kernel: the head (per-sprite tables), vertices and edges of `max_verts_env` polygon
+// vertices, and per wave a canvas row, its span mask and the crossings of a row
+size_t lf_lds_bytes(const swb_params& p, int max_verts_env) {
+  const size_t row_bytes = (size_t)((p.Wc + 15) & ~15), mask_words = (size_t)(p.Wc / 32 + 1);
+  return swb_lf_head_bytes(max_verts_env) + (size_t)SWB_LF_WAVES * (row_bytes + 4 * mask_words + 2 * 4 * SWB_LF_MAX_CROSS);
+}
+#define SWB_LF_MAX_LDS (160 * 1024)
+
+// Refuses a scene of `verts` polygon vertices whose tables would not fit the raster kernel's LDS (large-frame handles only):
+// a pool must fail where it is installed, not at its first launch.
+int lf_check_vertices(const swb_engine* h, int verts, const char* what) {
+  if (!h->large_frames || lf_lds_bytes(h->p, std::max(verts, 4)) <= SWB_LF_MAX_LDS) return 0;
+  int budget = 4;
+  while (lf_lds_bytes(h->p, budget + 1) <= SWB_LF_MAX_LDS) ++budget;
+  return fail(SWB_ERR_INVALID, "%s: a scene of %d polygon vertices exceeds the vertex budget of the large-frame raster kernel, %d vertices "
+              "per scene at a %d px canvas (160 KiB of LDS)", what, verts, budget, h->p.Wc);
+}
+
 int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
   const size_t per_env = p.AA == 1 ? 0 : (size_t)p.Hc * p.Wo * 3;
   long long chunk = per_env ? (long long)(h->lf_scratch_budget / per_env) : (long long)p.N;
@@ -468,9 +489,8 @@ int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
   a.mask_words = p.Wc / 32 + 1;
   a.rows_per_block = p.N >= 64 ? 64 : 16;        // (small batches: more workgroups per environment)
   a.tmp = h->d_lf_tmp;
-  const size_t lds = swb_lf_head_bytes(a.max_verts_env) +
-                     (size_t)SWB_LF_WAVES * (a.row_bytes + 4 * (size_t)a.mask_words + 2 * 4 * SWB_LF_MAX_CROSS);
-  if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "large-frame raster kernel: LDS request %zu B exceeds 160 KiB", lds);
+  const size_t lds = lf_lds_bytes(p, a.max_verts_env);
+  if (lds > SWB_LF_MAX_LDS) return fail(SWB_ERR_INVALID, "large-frame raster kernel: LDS request %zu B exceeds 160 KiB", lds);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(swb_lf_raster_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nd = (p.Wo * 3) >> 2;
@@ -505,15 +525,24 @@ int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int
   p.success = out ? out->success : nullptr;
   p.error = out ? out->error : nullptr;
   p.render_only = render_only;
-  int cpath_in_masks = 0;
-  const size_t lds = lds_per_wave(h, v, &cpath_in_masks);
-  p.cpath_in_masks = cpath_in_masks;
-  p.lds_per_wave = (int32_t)lds;
-  p.outrow_bytes = (int32_t)v->outrow_bytes;
-  if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "LDS request %zu B exceeds 160 KiB", lds);
-  const kernel_fn fn = h->d_ov_flag ? v->fn_ov : v->fn;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // the state phase: the cover kernel of the narrowest build with obs = NULL, or (many sprites) swb_ms_state_kernel, whose LDS
+  // does not depend on the scene
+  kernel_fn fn;
+  size_t lds;
+  if (h->many_sprites) {
+    fn = h->d_ov_flag ? swb_ms_state_kernel<true> : swb_ms_state_kernel<false>;
+    lds = sizeof(swb_ms_lds);
+  } else {
+    int cpath_in_masks = 0;
+    lds = lds_per_wave(h, v, &cpath_in_masks);
+    p.cpath_in_masks = cpath_in_masks;
+    p.lds_per_wave = (int32_t)lds;
+    p.outrow_bytes = (int32_t)v->outrow_bytes;
+    if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "LDS request %zu B exceeds 160 KiB", lds);
+    fn = h->d_ov_flag ? v->fn_ov : v->fn;
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
   swb_engine::step_events ev = {nullptr, nullptr, nullptr};
   if (h->timing) {
     if (!h->event_pool.empty()) { ev = h->event_pool.back(); h->event_pool.pop_back(); }
@@ -588,7 +617,7 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   if (!cfg || !out) return fail(SWB_ERR_INVALID, "null argument");
   if (cfg->n_envs < 1) return fail(SWB_ERR_INVALID, "n_envs must be >= 1");
   if (cfg->max_sprites < 1 || cfg->max_sprites > SWB_MAX_SPRITES)
-    return fail(SWB_ERR_INVALID, "max_sprites must be in [1, %d]", SWB_MAX_SPRITES);
+    return fail(SWB_ERR_INVALID, "max_sprites must be in [1, %d] (at most %d sprites per environment)", SWB_MAX_SPRITES, SWB_MAX_SPRITES);
   if (cfg->n_tasks < 1 || cfg->n_tasks > SWB_MAX_TASKS) return fail(SWB_ERR_INVALID, "n_tasks must be in [1, %d]", SWB_MAX_TASKS);
   if (cfg->anti_aliasing < 1) return fail(SWB_ERR_INVALID, "anti_aliasing must be >= 1");
   if (cfg->image_h < 1 || cfg->image_w < 1 || (cfg->image_h % 4) != 0)
@@ -636,7 +665,11 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   // the large-frame path; SWB_LARGE_FRAMES=1 (tests) sends every geometry there
   {
     const char* lf = getenv("SWB_LARGE_FRAMES");
-    h->large_frames = !pick_variant(p.Wc) || p.Wo > 64 * SWB_MAX_CG || (lf && atoi(lf) != 0);
+    const char* ms = getenv("SWB_MANY_SPRITES");
+    // (more sprites than the tuned kernels are built for: the many-sprite state kernel, then the large-frame render kernels;
+    // SWB_MANY_SPRITES=1, tests, sends every handle there)
+    h->many_sprites = p.S > SWB_TUNED_SPRITES || (ms && atoi(ms) != 0);
+    h->large_frames = !pick_variant(p.Wc) || p.Wo > 64 * SWB_MAX_CG || (lf && atoi(lf) != 0) || h->many_sprites;
     if (const char* x = getenv("SWB_LF_SCRATCH_BYTES")) h->lf_scratch_budget = (size_t)std::max(1ll, atoll(x));   // tests: force chunks
   }
   if (h->large_frames) {
@@ -908,6 +941,23 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
     if (pool->pool_len[i] < 1 || pool->pool_base[i] < 0 || pool->pool_base[i] + pool->pool_len[i] > P)
       return fail(SWB_ERR_INVALID, "env %d: pool range [%d, +%d) outside the pool of %d", i, pool->pool_base[i], pool->pool_len[i], P);
   const size_t PS = (size_t)P * S;
+  // polygon vertices of the largest episode: sizes the per-wave edge records and centred paths in LDS (checked before anything
+  // is installed: a pool the large-frame raster kernel cannot hold is refused here)
+  int most_verts = -1;
+  if (h->have_shapes) {
+    int most = 1;
+    for (int e = 0; e < P; ++e) {
+      int tot = 0;
+      for (int s2 = 0; s2 < pool->n_sprites[e]; ++s2) {
+        const int sh = pool->shape[(size_t)e * S + s2];
+        if (sh < 0 || sh >= (int)h->shape_nverts.size()) return fail(SWB_ERR_INVALID, "pool entry %d uses shape %d, %zu shapes uploaded", e, sh, h->shape_nverts.size());
+        tot += h->shape_nverts[sh];
+      }
+      most = std::max(most, tot);
+    }
+    most_verts = (most + 3) & ~3;
+    if (int rc = lf_check_vertices(h, most_verts, "swb_set_pool")) return rc;
+  }
   std::vector<uint32_t> rgb(PS);
   for (size_t i = 0; i < PS; ++i)
     rgb[i] = (uint32_t)pool->rgb[4 * i] | ((uint32_t)pool->rgb[4 * i + 1] << 8) | ((uint32_t)pool->rgb[4 * i + 2] << 16);
@@ -940,20 +990,7 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
   p.p_cell_label = h->keyed ? h->d_p_cell_label : nullptr;
   h->pool_entries = P;
   h->pool_sampled = false;
-  // polygon vertices of the largest episode: sizes the per-wave edge records and centred paths in LDS
-  if (h->have_shapes) {
-    int most = 1;
-    for (int e = 0; e < P; ++e) {
-      int tot = 0;
-      for (int s2 = 0; s2 < pool->n_sprites[e]; ++s2) {
-        const int sh = pool->shape[(size_t)e * S + s2];
-        if (sh >= (int)h->shape_nverts.size()) return fail(SWB_ERR_INVALID, "pool entry %d uses shape %d, %zu shapes uploaded", e, sh, h->shape_nverts.size());
-        tot += h->shape_nverts[sh];
-      }
-      most = std::max(most, tot);
-    }
-    h->p.max_edges = (most + 3) & ~3;
-  }
+  if (most_verts > 0) h->p.max_edges = most_verts;
   HIP_TRY(hipMemset(h->d_reset_next, 1, N));      // environment.py:70
   HIP_TRY(hipMemset(h->d_episode, 0, sizeof(int32_t) * N));
   HIP_TRY(hipMemset(h->d_step_count, 0, sizeof(int32_t) * N));
@@ -1035,6 +1072,7 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
     } else {
       for (int g = 0; g < spec->n_groups; ++g) most += group_verts(spec->groups[g]);
     }
+    if (int rc = lf_check_vertices(h, (std::max(most, 1) + 3) & ~3, "swb_sample_pool")) return rc;
     h->p.max_edges = (std::max(most, 1) + 3) & ~3;
   }
   for (int i = 0; i < N; ++i)
@@ -1428,6 +1466,7 @@ int swb_set_sprite_attr(swb_handle h, int32_t env, int32_t sprite, int32_t attr,
   // LDS of a wave is sized by the most polygon vertices an episode can have: a new shape may raise it
   int tot = 0;
   for (int s2 = 0; s2 < n; ++s2) tot += h->shape_nverts[r.shape[s2]];
+  if (int rc = lf_check_vertices(h, std::max(h->p.max_edges, (tot + 3) & ~3), "swb_set_sprite_attr")) return rc;
   h->p.max_edges = std::max(h->p.max_edges, (tot + 3) & ~3);
   if (int rc = ov_allocate(h)) return rc;
   if (!was_set && h->keyed) {                          // the episode's per-cell labels: from its pool entry, until
@@ -1490,6 +1529,13 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
     out->paint_in_cover = 0;
     out->arena_units = 0;
     out->large_frames = 1;
+    out->many_sprites = h->many_sprites ? 1 : 0;
+    out->reserved_ = 0;
+    if (h->many_sprites) {            // (no cover kernel: swb_ms_state_kernel, one wave per environment)
+      out->nw = 0;
+      out->lds_bytes_per_wave = (int32_t)sizeof(swb_ms_lds);
+      out->waves_per_simd = 0;
+    }
     out->run_list_bytes = 0;
     return SWB_OK;
   }
@@ -1507,6 +1553,8 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
   out->paint_in_cover = (h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1 && !h->no_paint_in_cover) ? 1 : 0;
   out->arena_units = h->d_runs ? h->p.arena_units : 0;
   out->large_frames = 0;
+  out->many_sprites = 0;
+  out->reserved_ = 0;
   out->run_list_bytes = h->d_runs ? ((int64_t)h->p.arena_base + h->p.arena_units + 4) * 8 : 0;
   return SWB_OK;
 }

@@ -63,6 +63,9 @@
 #define SWB_COVER_WAVES(NW) ((NW) <= 2 ? SWB_COVER_WAVES_PER_SIMD_NARROW : ((NW) <= 10 ? SWB_COVER_WAVES_PER_SIMD : SWB_COVER_WAVES_PER_SIMD_WIDE))
 #define SWB_RS_WAVES_PER_BLOCK 4          // ... in workgroups of 4 waves that share the horizontal prefix table in LDS
 #define SWB_VSLOTS 8          // in-flight output rows of the vertical pass
+// Sprites per environment the tuned kernels (cover, resample, fill) are built for: their LDS, prefix scans and task scratch
+// are sized by it.  Handles of more sprites (up to SWB_MAX_SPRITES) run swb_ms_state_kernel and the large-frame kernels.
+#define SWB_TUNED_SPRITES 16
 #define PRECISION_BITS 22
 
 struct swb_params {
@@ -356,20 +359,23 @@ __device__ __forceinline__ double dot2_lo(double a0, double a1, double b0, doubl
 // tasks.py:127-128: np.float64 ** 0.5 is libm pow(x, 0.5); see swb_pow.hip.inc.
 __device__ double swb_pow_half(double x);
 
-// Scratch (per wave, LDS) for the task evaluation.
-struct task_scratch {
-  double xs[SWB_MAX_SPRITES], ys[SWB_MAX_SPRITES];
-  double tmp[SWB_MAX_SPRITES];
-  double c0[SWB_MAX_SPRITES], c1[SWB_MAX_SPRITES], intra[SWB_MAX_SPRITES];
-  float tmpf[SWB_MAX_SPRITES];
+// Scratch (per wave, LDS) for the task evaluation of up to NS sprites.  The tuned cover kernel's (task_scratch) aliases
+// its span lists; the many-sprite state kernel has one of SWB_MAX_SPRITES entries.
+template <int NS>
+struct task_scratch_t {
+  double xs[NS], ys[NS];
+  double tmp[NS];
+  double c0[NS], c1[NS], intra[NS];
+  float tmpf[NS];
   double tr[SWB_MAX_TASKS];
   int tok[SWB_MAX_TASKS];
-  int8_t lab[SWB_MAX_SPRITES];
-  double px0[SWB_MAX_SPRITES];                         // member distances grouped by cluster (Davies-Bouldin)
-  int32_t cnt[SWB_MAX_SPRITES];                        // members per cluster
+  int8_t lab[NS];
+  double px0[NS];                                      // member distances grouped by cluster (Davies-Bouldin)
+  int32_t cnt[NS];                                     // members per cluster
   uint32_t pres[4];                                    // labels present (bit set), 128 label values
-  int8_t labels[SWB_MAX_TASKS * SWB_MAX_SPRITES];      // this episode's label[t][s], staged from the pool
+  int8_t labels[SWB_MAX_TASKS * NS];                   // this episode's label[t][s], staged from the pool
 };
+typedef task_scratch_t<SWB_TUNED_SPRITES> task_scratch;
 
 // the scratch aliases the LDS span lists: SWB_MIN_SPANS lists of 64 dwords must hold it
 #define SWB_MIN_SPANS ((int)((sizeof(task_scratch) + 255) / 256))
@@ -383,8 +389,9 @@ static_assert(sizeof(task_scratch) <= 6 * 256, "task_scratch outgrew the span li
 // s's position (px, py); results are wave-uniform.
 // --------------------------------------------------------------------------------------------
 // tasks.py:126-158 FindGoalPosition.
+template <typename SC>
 __device__ __forceinline__ void task_find_goal_wave(const swb_task& t, int n, double px, double py, const int8_t* label,
-                                                    task_scratch* sc, double* reward, int* success) {
+                                                    SC* sc, double* reward, int* success) {
   const int l = lane_id();
   const bool f = (l < n) && label[l < n ? l : 0] != 0;
   double r = 0.0;
@@ -411,8 +418,9 @@ __device__ __forceinline__ void task_find_goal_wave(const swb_task& t, int n, do
 }
 
 // scikit-learn 1.7.2 davies_bouldin_score (SURVEY A.8; oracle/sw_oracle.c davies_bouldin).
+template <typename SC>
 __device__ __forceinline__ int davies_bouldin_wave(int pos_f32, int n, double px, double py, const int8_t* label,
-                                                   task_scratch* sc, double* score_out) {
+                                                   SC* sc, double* score_out) {
   const int l = lane_id();
   const int lab_l = (l < n) ? (int)label[l] : -1;
   const bool has = lab_l >= 0;
@@ -483,7 +491,7 @@ __device__ __forceinline__ int davies_bouldin_wave(int pos_f32, int n, double px
   }
   wave_sync();
   // lanes = clusters: the members' distances in member order, their numpy mean
-  double* sorted_d = sc->px0;                                       // [16] doubles or floats
+  double* sorted_d = sc->px0;                                       // [NS] doubles or floats
   float* sorted_f = reinterpret_cast<float*>(sc->px0);
   if (l < k) {
     int off = 0;
@@ -509,7 +517,7 @@ __device__ __forceinline__ int davies_bouldin_wave(int pos_f32, int n, double px
   // (lanes = (a, b) pairs, A = 64 / k rows of the matrix per pass: the whole matrix at once for up to 8 clusters)
   int all_d_zero = 1;
   unsigned long long* best_bits = reinterpret_cast<unsigned long long*>(sc->tmp);
-  const int rows_per_pass = 64 / k;                                  // k <= SWB_MAX_SPRITES = 16
+  const int rows_per_pass = 64 / k;                                  // k < n <= 64
   const int ar = (int)(((uint32_t)l * (uint32_t)((65536 + k - 1) / k)) >> 16), b = l - ar * k;      // l / k, l % k (exact for l < 64)
   for (int a_base = 0; a_base < k; a_base += rows_per_pass) {
     const int a = a_base + ar;
@@ -538,8 +546,9 @@ __device__ __forceinline__ int davies_bouldin_wave(int pos_f32, int n, double px
 }
 
 // tasks.py:196-245 Clustering.
+template <typename SC>
 __device__ __forceinline__ int task_clustering_wave(const swb_task& t, int pos_f32, int n, double px, double py,
-                                                    const int8_t* label, task_scratch* sc, double* reward, int* success) {
+                                                    const int8_t* label, SC* sc, double* reward, int* success) {
   double score = 0.0;
   const int err = davies_bouldin_wave(pos_f32, n, px, py, label, sc, &score);
   if (err) { *reward = __longlong_as_double(0x7ff8000000000000ll); *success = 0; return err; }
@@ -555,8 +564,9 @@ __device__ __forceinline__ int task_clustering_wave(const swb_task& t, int pos_f
 }
 
 // task.reward + task.success incl. tasks.py:248-296 MetaAggregated; all lanes, uniform result.
+template <typename SC>
 __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double px, double py, const int8_t* label,
-                                              task_scratch* sc, double* reward, int* success) {
+                                              SC* sc, double* reward, int* success) {
   const int l = lane_id();
   int err = 0;
   double r0 = 0.0;
@@ -644,7 +654,7 @@ struct wave_lds {
   // masks[w][lane]: parity toggles T and crossing pixels Px for the current (batch, sprite, chunk)
   uint32_t T[SWB_NWA(NW)][SWB_WAVE];
   uint32_t Px[SWB_NWA(NW)][SWB_WAVE];
-  sprite_rec spr[SWB_MAX_SPRITES];
+  sprite_rec spr[SWB_TUNED_SPRITES];
   int32_t ovf_slot;                         // this wave's HBM overflow slot: -1 none yet, -2 none free
   int32_t pad_[3];
   uint32_t outrow[];                        // [outrow_bytes / 4] packed-byte staging of one output row; P1b scratch (132 ints)
@@ -691,7 +701,7 @@ __device__ __forceinline__ void corner_try(corner_end& c, int cx0, int cy0, floa
 // rowtab: SWB_ROWTAB_DWORDS dwords of scratch (the span lists, idle until P2) -- for the general scan, per sprite and per
 // canvas row modulo 8 the edges that have an end on such a row.
 #define SWB_ROWTAB_SLOTS 8
-#define SWB_ROWTAB_DWORDS (SWB_MAX_SPRITES * SWB_ROWTAB_SLOTS * 2)
+#define SWB_ROWTAB_DWORDS (SWB_TUNED_SPRITES * SWB_ROWTAB_SLOTS * 2)
 static_assert(SWB_ROWTAB_DWORDS * 4 <= SWB_MIN_SPANS * 256, "the row table borrows the span lists");
 template <int NW>
 __device__ __forceinline__ void build_all_edges(const swb_params& p, wave_lds<NW>* L, edge_rec* edges, const double2* cpath,
@@ -699,10 +709,10 @@ __device__ __forceinline__ void build_all_edges(const swb_params& p, wave_lds<NW
                                                 double dmin_l, double scale_l, uint32_t rgb_reg, uint32_t& err) {
   const int l = lane_id();
   double* posx = reinterpret_cast<double*>(L->outrow);                 // [16] sprite positions
-  double* posy = posx + SWB_MAX_SPRITES;                                // [16]
-  int* nvs = reinterpret_cast<int*>(posy + SWB_MAX_SPRITES);            // [16] vertex counts
-  int* flags = nvs + SWB_MAX_SPRITES;                                   // [16] 1: general corner scan
-  int* misc = flags + SWB_MAX_SPRITES;                                  // (4 dwords of padding)
+  double* posy = posx + SWB_TUNED_SPRITES;                              // [16]
+  int* nvs = reinterpret_cast<int*>(posy + SWB_TUNED_SPRITES);          // [16] vertex counts
+  int* flags = nvs + SWB_TUNED_SPRITES;                                 // [16] 1: general corner scan
+  int* misc = flags + SWB_TUNED_SPRITES;                                // (4 dwords of padding)
   uint32_t* umask = reinterpret_cast<uint32_t*>(misc + 4);              // [16][2] bit i: edge i of the sprite can be a partner
   if (l < nspr) {
     posx[l] = px; posy[l] = py; nvs[l] = nv_l;
@@ -711,7 +721,7 @@ __device__ __forceinline__ void build_all_edges(const swb_params& p, wave_lds<NW
     r.w0 = 0x7fffffff; r.w1 = -0x7fffffff; r.max_edge_rows = 0;        // w0/w1 hold min/max x until finalised
     L->spr[l] = r;
   }
-  if (l < 2 * SWB_MAX_SPRITES) umask[l] = 0u;
+  if (l < 2 * SWB_TUNED_SPRITES) umask[l] = 0u;
   // corner-rule mode of every sprite (see the header): can two of its vertices share a pixel?
   const bool nodup_l = __dmul_rn(__dmul_rn(dmin_l, scale_l), (double)min(p.Wc, p.Hc)) >= 2.9;
   if (l < nspr) flags[l] = nodup_l ? 0 : 1;
@@ -1795,8 +1805,8 @@ swb_cover_kernel(const swb_params p) {
   double dmin_l = (l < n) ? dmin_any : 0.0;              // P1b: can two vertices share a pixel?
   if constexpr (OV) { if (ov) dmin_l = 0.0; }           // an overridden path is arbitrary: always the general corner scan
   int voff_l = nv_l;                                    // inclusive prefix sum over lanes (sprites)
-  for (int o = 1; o < SWB_MAX_SPRITES; o <<= 1) { const int t = __shfl_up(voff_l, o, 64); if (l >= o) voff_l += t; }
-  const int vtotal = __builtin_amdgcn_readlane(voff_l, SWB_MAX_SPRITES - 1);
+  for (int o = 1; o < SWB_TUNED_SPRITES; o <<= 1) { const int t = __shfl_up(voff_l, o, 64); if (l >= o) voff_l += t; }
+  const int vtotal = __builtin_amdgcn_readlane(voff_l, SWB_TUNED_SPRITES - 1);
   voff_l -= nv_l;                                       // exclusive
   for (int base = 0; base < vtotal; base += 64) {
     const int k = base + l;
@@ -1973,8 +1983,8 @@ swb_cover_kernel(const swb_params p) {
     // lanes per edge of the edge-lane scatter: G = 64 / n_edges (1 .. 32), so that lane l serves edge l / G -- computed there as
     // (l * ceil(2^16 / G)) >> 16, which is exact for l < 64: the rounding adds less than 64 / 2^16 to l / G, and l / G is at
     // least 1 / G >= 1 / 32 below the next integer.  The reciprocal is 2^16 itself for G = 1 (shapes of 33 .. 64 edges): 17 bits,
-    // above the 12 bits of the edge slot (at most SWB_MAX_SPRITES * SWB_MAX_SHAPE_VERTS = 1024 slots).
-    static_assert(SWB_MAX_SPRITES * SWB_MAX_SHAPE_VERTS <= 4096 && SWB_MAX_SHAPE_VERTS <= 64, "packing of sp_e0 / lanes per edge");
+    // above the 12 bits of the edge slot (at most SWB_TUNED_SPRITES * SWB_MAX_SHAPE_VERTS = 1024 slots).
+    static_assert(SWB_TUNED_SPRITES * SWB_MAX_SHAPE_VERTS <= 4096 && SWB_MAX_SHAPE_VERTS <= 64, "packing of sp_e0 / lanes per edge");
     const int lanes_per_edge = max(64 / max(r.n_edges, 2), 1);
     sp_ymin = r.ymin; sp_ymax = r.ymax;
     sp_e0 = r.edge_off | (((65536 + lanes_per_edge - 1) / lanes_per_edge) << 12);
@@ -1984,11 +1994,11 @@ swb_cover_kernel(const swb_params p) {
   // the hand-off header: per sprite the colour's difference to the background as three signed 10-bit fields
   // (horizontal pass of the resample kernel) and the colour itself (fill kernel)
   uint32_t* hdr = p.rhdr + (size_t)env * SWB_RHDR_DWORDS;
-  if (l < SWB_MAX_SPRITES && !PAINT) {
+  if (l < SWB_TUNED_SPRITES && !PAINT) {
     hdr[l] = (uint32_t)(((int)(rgb_reg & 255) - (int)(p.bg & 255)) & 0x3ff) |
              ((uint32_t)(((int)((rgb_reg >> 8) & 255) - (int)((p.bg >> 8) & 255)) & 0x3ff) << 10) |
              ((uint32_t)(((int)((rgb_reg >> 16) & 255) - (int)((p.bg >> 16) & 255)) & 0x3ff) << 20);
-    hdr[SWB_MAX_SPRITES + l] = rgb_reg;
+    hdr[SWB_TUNED_SPRITES + l] = rgb_reg;
   }
   SWB_HOOK_PHASE_END(1)
   reprioritise();
@@ -2022,7 +2032,7 @@ swb_cover_kernel(const swb_params p) {
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x112, 0xf, 0xf, false));   // row_shr:2
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x114, 0xf, 0xf, false));   // row_shr:4
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x118, 0xf, 0xf, false));   // row_shr:8
-      yb = min(__builtin_amdgcn_readlane(v, SWB_MAX_SPRITES - 1), p.Hc);
+      yb = min(__builtin_amdgcn_readlane(v, SWB_TUNED_SPRITES - 1), p.Hc);
       for (; y_next < yb; ++y_next) { if (pack_store1) *reinterpret_cast<uint32_t*>(frame1 + off1) = bg_dw1; off1 -= row_bytes1; }    // rows above the batch
       if (yb >= p.Hc) break;
       row_spans rs;
@@ -2081,7 +2091,7 @@ swb_cover_kernel(const swb_params p) {
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x112, 0xf, 0xf, false));   // row_shr:2
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x114, 0xf, 0xf, false));   // row_shr:4
       v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x118, 0xf, 0xf, false));   // row_shr:8
-      yb = __builtin_amdgcn_readlane(v, SWB_MAX_SPRITES - 1);
+      yb = __builtin_amdgcn_readlane(v, SWB_TUNED_SPRITES - 1);
     }
     if (yb >= p.Hc) break;
     row_spans rs;
@@ -2197,7 +2207,7 @@ swb_resample_kernel(const swb_params p) {
   const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];
   if (o_lo >= o_hi) return;
   cptr<uint32_t> hdr = as_const(p.rhdr) + (size_t)env * SWB_RHDR_DWORDS;
-  const uint32_t dpk_reg = (l < SWB_MAX_SPRITES) ? p.rhdr[(size_t)env * SWB_RHDR_DWORDS + l] : 0u;   // lane s: sprite s
+  const uint32_t dpk_reg = (l < SWB_TUNED_SPRITES) ? p.rhdr[(size_t)env * SWB_RHDR_DWORDS + l] : 0u;   // lane s: sprite s
   uint32_t uo = 8u * hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + 1 + band];                           // byte offset of the next run
   // Wave priority by the list left to walk.  A SIMD issues from its oldest wave first, so the waves of a launch finish one after
   // the other and the last one alone, far below the SIMD's rate; with the priority (0..3) following the remaining work --
@@ -2351,7 +2361,7 @@ swb_fill_kernel(const swb_params p) {
   const int y_lo = as_const(p.band_lo)[band], y_hi = as_const(p.band_lo)[band + 1];
   if (y_lo >= y_hi) return;
   cptr<uint32_t> hdr = as_const(p.rhdr) + (size_t)env * SWB_RHDR_DWORDS;
-  const uint32_t rgb_reg = (l < SWB_MAX_SPRITES) ? p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_MAX_SPRITES + l] : 0u;
+  const uint32_t rgb_reg = (l < SWB_TUNED_SPRITES) ? p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_TUNED_SPRITES + l] : 0u;
   const int n_units = (int)hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE];       // (positions: see swb_params::run_cap)
   int u = (int)hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + 1 + band];
   cptr<uint32_t> runs = as_const(p.runs) + ((size_t)env * p.ncg + g) * p.run_cap * 2;
@@ -2761,3 +2771,228 @@ swb_lf_vertical_kernel(const swb_params p, const swb_lf_args a) {
 }
 
 #endif  // SWB_WIDE_TU
+
+// --------------------------------------------------------------------------------------------
+// Many-sprite path (handles of more than SWB_TUNED_SPRITES sprites, up to SWB_MAX_SPRITES = one lane per sprite): the
+// state phase of a step -- what the cover kernel's P0 does, with the same arithmetic and the same leaf helpers -- in a kernel
+// of its own, one wave per environment; the frame is then rendered by the large-frame kernels above.
+// Differences to P0: the scan of vertex offsets and the centred paths of the whole scene are not needed (P1 is not run here):
+// a hit test builds the centred path of the one sprite it visits on the fly (lanes = vertices, <= SWB_MAX_SHAPE_VERTS), so
+// the LDS is a wide task_scratch and one path, about 6 KB per wave whatever the scene.
+// --------------------------------------------------------------------------------------------
+struct swb_ms_lds {
+  task_scratch_t<SWB_MAX_SPRITES> ts;
+  double2 path[SWB_MAX_SHAPE_VERTS];                    // centred path of the sprite a hit test visits
+};
+static_assert(SWB_MAX_SPRITES <= SWB_WAVE && SWB_MAX_SHAPE_VERTS <= SWB_WAVE, "one lane per sprite / per vertex");
+
+template <bool OV>
+__global__ void __launch_bounds__(SWB_WAVE)
+swb_ms_state_kernel(const swb_params p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int l = lane_id();
+  const int env = blockIdx.x;
+  swb_ms_lds* M = reinterpret_cast<swb_ms_lds*>(smem);
+  task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
+  double2* cpath = M->path;
+  const int S = p.S;
+  double* gx = p.x + (size_t)env * S;
+  double* gy = p.y + (size_t)env * S;
+
+  uint32_t err = 0;
+  const int rn = p.render_only ? 0 : (int)p.reset_next[env];
+  const int ep = p.episode[env], pbase = as_const(p.pool_base)[env], plen = as_const(p.pool_len)[env];
+  const int en_old = p.entry[env], n_old = p.nspr[env], sc_old = p.step_count[env];
+  double px = 0.0, py = 0.0;      // lane s < n holds sprite s's position
+  if (l < S) { px = gx[l]; py = gy[l]; }
+  static_assert(SWB_MAX_SHAPES + 1 <= SWB_WAVE, "one lane per entry of the shape table");
+  const int shoff_tab_l = (l <= SWB_MAX_SHAPES) ? p.shape_off[l] : 0;
+  double act = 0.0;               // lanes 0..3: the action components
+  int acti = 0;
+  if (!p.render_only) {
+    if (p.action_space == SWB_ACTION_EMBODIED) { if (l < 2) acti = reinterpret_cast<const int32_t*>(p.actions)[2 * (size_t)env + l]; }
+    else if (l < 4) {
+      act = p.action_is_f32 ? (double)reinterpret_cast<const float*>(p.actions)[4 * (size_t)env + l]
+                            : reinterpret_cast<const double*>(p.actions)[4 * (size_t)env + l];
+    }
+  }
+  const bool first = rn != 0;                           // environment.py:90-91 -> reset() :74-78
+  bool ov = false;                                      // this episode's sprites carry setter overrides
+  if constexpr (OV) {
+    ov = rfl((int)p.ov_flag[env]) != 0;
+    if (ov && first) {                                  // a reset draws fresh sprites: the overrides end here
+      ov = false;
+      if (l == 0) p.ov_flag[env] = 0;
+    }
+  }
+  const int en = rfl(first ? pbase + (ep % plen) : en_old);
+  const size_t pe = (size_t)en * S;
+  int n = first ? as_const(p.p_n)[en] : n_old;
+  int shape_l = 0;
+  double scale_l = 1.0, ca_l = 1.0, sa_l = 0.0, xv_l = 0.0, yv_l = 0.0;
+  if (l < S) {
+    shape_l = p.p_shape[pe + l]; scale_l = p.p_scale[pe + l]; ca_l = p.p_ca[pe + l]; sa_l = p.p_sa[pe + l];
+    xv_l = p.p_xv[pe + l]; yv_l = p.p_yv[pe + l];
+    if (first) { px = p.p_x[pe + l]; py = p.p_y[pe + l]; gx[l] = px; gy[l] = py; }
+    if constexpr (OV) {
+      if (ov) { shape_l = p.ov_shape[(size_t)env * S + l]; scale_l = p.ov_scale[(size_t)env * S + l]; }
+    }
+  }
+  if (p.render_only != 1) {
+    const int8_t* lab_src = p.p_label + (size_t)en * p.n_tasks * S;
+    if constexpr (OV) { if (ov) lab_src = p.ov_label + (size_t)env * p.n_tasks * S; }
+    for (int i = l; i < p.n_tasks * S; i += SWB_WAVE) tscratch->labels[i] = lab_src[i];
+  }
+  n = rfl(n);
+  if (first && l == 0) { p.episode[env] = ep + 1; p.entry[env] = en; p.nspr[env] = n; p.step_count[env] = 0; p.reset_next[env] = 0; }
+
+  // lane s: vertex count and offset of sprite s in the shape table (cross-lane reads with every lane active)
+  const int sh_idx = (int)min((uint32_t)shape_l, (uint32_t)(SWB_MAX_SHAPES - 1));
+  const int so_any = __shfl(shoff_tab_l, sh_idx, 64), so_next = __shfl(shoff_tab_l, sh_idx + 1, 64);
+  const int so_l = (l < n) ? so_any : 0;
+  const int nv_l = (l < n) ? so_next - so_any : 0;
+  // sprite.py:113-115 contains_point of sprite s2 (wave-uniform): its centred path into LDS, lanes = vertices, then the
+  // even-odd test of contains_point_wave -- the values P1a of the cover kernel computes for the same sprite
+  auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
+    const int nv = __builtin_amdgcn_readlane(nv_l, s2), so = __builtin_amdgcn_readlane(so_l, s2);
+    const double sc = readlane_d(scale_l, s2), ca = readlane_d(ca_l, s2), sa = readlane_d(sa_l, s2);
+    wave_sync();                                        // (the previous sprite's test has read the path)
+    if (l < nv) {
+      double cx, cy;
+      bool from_table = true;
+      if constexpr (OV) {
+        if (ov) {                                       // the path the setters left (host arithmetic, swb.hip)
+          const double* q = p.ov_cpath + (((size_t)env * S + s2) * SWB_MAX_SHAPE_VERTS + l) * 2;
+          cx = q[0]; cy = q[1];
+          from_table = false;
+        }
+      }
+      if (from_table) centered_vertex(p, so, l, sc, ca, sa, cx, cy);
+      cpath[l] = make_double2(cx, cy);
+    }
+    wave_sync();
+    return contains_point_wave(cpath, nv, tx, ty);
+  };
+
+  double cost = 0.0;
+  float cost_f32 = 0.0f;
+  bool cost_is_f32 = false;
+  int step_count = 0;
+  if (!p.render_only && !first) {
+    step_count = sc_old + 1;                            // :93
+    int moved = -1;
+    double m0 = 0.0, m1 = 0.0;
+    if (p.action_space == SWB_ACTION_EMBODIED) {        // action_spaces.py:187-214
+      const int carry = __builtin_amdgcn_readlane(acti, 0), dir = __builtin_amdgcn_readlane(acti, 1);
+      const double st = p.action_scale;
+      if (dir == 0) m1 = st; else if (dir == 1) m0 = -st; else if (dir == 2) m1 = -st; else m0 = st;
+      if (n > 0) {
+        const int body = n - 1;
+        const double bx = readlane_d(px, body), by = readlane_d(py, body);
+        if (carry) {                                     // get_carried_sprite :180-185
+          for (int s2 = body - 1; s2 >= 0; --s2) {
+            const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
+            double tx, ty;
+            if (p.pos_is_f32) { tx = (double)__fsub_rn((float)bx, (float)sx); ty = (double)__fsub_rn((float)by, (float)sy); }
+            else { tx = __dsub_rn(bx, sx); ty = __dsub_rn(by, sy); }
+            if (hit(s2, tx, ty)) {
+              moved = s2;
+              break;
+            }
+          }
+        }
+        if (l == moved || l == body) {
+          px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
+          py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
+        }
+      }
+      cost = __dmul_rn(-p.motion_cost, st);             // :214
+    } else {                                             // action_spaces.py:83-104
+      const double a0 = readlane_d(act, 0), a1 = readlane_d(act, 1);
+      const double a2 = readlane_d(act, 2), a3 = readlane_d(act, 3);
+      // float32 actions (action_spec() dtype): as in the cover kernel, numpy's float32 arithmetic (NEP 50)
+      const bool af = p.action_is_f32 != 0;
+      if (af) {
+        const float f0 = (float)a0, f1 = (float)a1, f2 = (float)a2, f3 = (float)a3, sc = (float)p.action_scale;
+        float m0f, m1f;
+        if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { m0f = __fmul_rn(__fsub_rn(f2, f0), sc); m1f = __fmul_rn(__fsub_rn(f3, f1), sc); }
+        else { m0f = __fmul_rn(__fsub_rn(f2, 0.5f), sc); m1f = __fmul_rn(__fsub_rn(f3, 0.5f), sc); }
+        m0 = (double)m0f; m1 = (double)m1f;
+        cost_f32 = __fmul_rn((float)(-p.motion_cost), sqrtf(__fadd_rn(__fmul_rn(m0f, m0f), __fmul_rn(m1f, m1f))));
+        cost = (double)cost_f32;
+        cost_is_f32 = true;
+      } else if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { // :133-137
+        m0 = __dmul_rn(__dsub_rn(a2, a0), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, a1), p.action_scale);
+      } else {                                           // :65-67
+        m0 = __dmul_rn(__dsub_rn(a2, 0.5), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, 0.5), p.action_scale);
+      }
+      for (int s2 = n - 1; s2 >= 0; --s2) {              // sprites[::-1] :77-81
+        const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
+        double tx, ty;
+        if (af && p.pos_is_f32) { tx = (double)__fsub_rn((float)a0, (float)sx); ty = (double)__fsub_rn((float)a1, (float)sy); }
+        else { tx = __dsub_rn(a0, sx); ty = __dsub_rn(a1, sy); }
+        if (hit(s2, tx, ty)) {
+          moved = s2;
+          break;
+        }
+      }
+      if (l == moved) {
+        px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
+        py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
+      }
+      if (!af) cost = __dmul_rn(-p.motion_cost, __dsqrt_rn(dot2_hi(m0, m1, m0, m1)));   // :104
+    }
+    if (l < n) {                                         // update_position :98-99
+      px = move1(p.pos_is_f32, px, xv_l, p.keep_in_frame);
+      py = move1(p.pos_is_f32, py, yv_l, p.keep_in_frame);
+      gx[l] = px; gy[l] = py;
+    }
+  }
+  // task reward / success (spread over the lanes), out-of-frame, termination
+  if (p.render_only != 1) {
+    wave_sync();
+    // labels of tasks that key on position: the cell of the task's grid each sprite stands in now (lanes = sprites)
+    if (p.p_cell_label != nullptr) {
+      const int8_t* cells = p.p_cell_label + (size_t)en * p.n_tasks * S * SWB_MAX_CELLS;
+      if constexpr (OV) { if (ov && p.ov_cell_label) cells = p.ov_cell_label + (size_t)env * p.n_tasks * S * SWB_MAX_CELLS; }
+      for (int t = 0; t < p.n_tasks; ++t) {
+        const swb_task& tk = p.tasks[t];
+        if (tk.n_xcuts + tk.n_ycuts == 0) continue;
+        if (l < n) {
+          int cx = 0, cy = 0;
+          for (int k = 0; k < tk.n_xcuts; ++k) cx += (px >= tk.xcuts[k]) ? 1 : 0;
+          for (int k = 0; k < tk.n_ycuts; ++k) cy += (py >= tk.ycuts[k]) ? 1 : 0;
+          tscratch->labels[t * S + l] = cells[((size_t)t * S + l) * SWB_MAX_CELLS + cy * (tk.n_xcuts + 1) + cx];
+        }
+      }
+      wave_sync();
+    }
+    const bool oof_l = (l < n) && !(px >= 0. && py >= 0. && px <= 1. && py <= 1.);   // sprite.py:135-138
+    const int oof = __ballot(oof_l) != 0ull;
+    double tr = 0.0; int ok = 0;
+    const int terr = eval_task_wave(p, n, px, py, tscratch->labels, tscratch, &tr, &ok);
+    if (l == 0) {
+      err |= (uint32_t)terr;
+      if (p.success) p.success[env] = (uint8_t)ok;
+      if (p.render_only) {
+        // (swb_evaluate: environment.py:80-81 success() of the current sprites, no time step)
+      } else if (first) {
+        if (p.reward) p.reward[env] = __longlong_as_double(0x7ff8000000000000ll);
+        if (p.discount) p.discount[env] = __int_as_float(0x7fc00000);
+        if (p.step_type) p.step_type[env] = SWB_STEP_FIRST;
+      } else {
+        // :101 reward += task.reward (a float32 cost plus a Python-float task reward stays float32 under NEP 50)
+        const bool task_is_pyfloat = !p.is_meta && p.tasks[0].kind != SWB_TASK_FIND_GOAL;
+        const double rew = (cost_is_f32 && task_is_pyfloat) ? (double)__fadd_rn(cost_f32, (float)tr) : __dadd_rn(cost, tr);
+        if (p.reward) p.reward[env] = rew;
+        const int timeout = step_count >= p.max_episode_length;            // :84
+        const int last = ok || oof || timeout;                             // :104-106
+        p.step_count[env] = step_count;
+        if (last) p.reset_next[env] = 1;
+        if (p.step_type) p.step_type[env] = last ? SWB_STEP_LAST : SWB_STEP_MID;
+        if (p.discount) p.discount[env] = last ? 0.0f : 1.0f;
+      }
+      if (p.error && err) p.error[env] |= (uint8_t)err;                   // sticky: the caller clears
+    }
+  }
+}

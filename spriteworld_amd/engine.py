@@ -235,8 +235,12 @@ class Engine(object):
     _lib.check(self.lib.swb_variant(self._h, C.byref(info)))
     d = {k: getattr(info, k) for k, _ in _abi.SwbVariantInfo._fields_}
     d['cover_kernel'] = 'swb_cover_kernel<%d>' % info.nw
+    if info.many_sprites:                # (more than 16 sprites: no cover kernel, the state phase is a kernel of its own)
+      d['cover_kernel'] = 'none'
+      d['state_kernel'] = 'swb_ms_state_kernel'
     if info.large_frames:
-      d['cover_kernel'] += ' (state phase only)'
+      if not info.many_sprites:
+        d['cover_kernel'] += ' (state phase only)'
       d['kernel'] = 'swb_lf_raster_kernel' + ('' if self.cfg.anti_aliasing == 1 else ' + swb_lf_vertical_kernel')
     else:
       d['kernel'] = ('swb_resample_kernel<%d>' % info.vs if info.vs else

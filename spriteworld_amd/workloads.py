@@ -21,6 +21,7 @@ All use synthetic pools drawn with numpy (spriteworld_amd/synthetic.py).
 """
 import numpy as np
 
+from spriteworld_amd import _abi
 from spriteworld_amd import action_spaces
 from spriteworld_amd import lowering
 from spriteworld_amd import renderers
@@ -111,6 +112,51 @@ def build(name, num_envs, episodes_per_env=4, seed=0, anti_aliasing=5):
     pool.n_sprites[:] = rng.integers(0, 17, size=P)
     pool.n_sprites[:4] = (0, 16, 1, 0)
     cfg = lowering.lower_config(task, aspace, rend, True, 8, num_envs, 16, True)
+  elif name in ('ragged_s64', 'ragged_s64_embodied'):
+    # many-sprite path: episodes of 0..64 sprites (the engine's maximum), including empty and single-sprite ones
+    task = tasks.FindGoalPosition(filter_distrib=None, terminate_distance=0.15)
+    aspace = (action_spaces.Embodied(step_size=0.1) if name.endswith('embodied')
+              else action_spaces.SelectMove(scale=0.4))
+    rend = _renderers(64, aa)
+    labels = [[int(i % 3 == 0)] for i in range(64)]
+    pool = synthetic.make_pool(rng, P, 64, [(0.0, 1.0)] * 64, labels,
+                               shape_names=('square', 'triangle', 'circle', 'star_4'), scales=(0.05, 0.1), xy_range=(0.05, 0.95))
+    pool.n_sprites[:] = rng.integers(0, 65, size=P)
+    pool.n_sprites[:min(P, 5)] = (0, 64, 1, 0, 17)[:min(P, 5)]
+    cfg = lowering.lower_config(task, aspace, rend, True, 8, num_envs, 64, True)
+  elif name == 'cluster_s40':
+    # many-sprite path: Clustering of 40 sprites in 13 hue clusters of three (a 13 x 13 Davies-Bouldin ratio matrix) and one
+    # sprite in no cluster, float32 positions
+    task = tasks.Clustering([None] * 13, termination_threshold=1.5, terminate_bonus=1., reward_range=6.)
+    aspace = action_spaces.SelectMove(scale=0.25)
+    rend = _renderers(64, aa)
+    hues = [(0.07 * i, 0.07 * i + 0.04) for i in range(13) for _ in range(3)] + [(0.93, 1.0)]
+    labels = [[i] for i in range(13) for _ in range(3)] + [[-1]]
+    pool = synthetic.make_pool(rng, P, 40, hues, labels, scales=(0.04, 0.06))
+    cfg = lowering.lower_config(task, aspace, rend, True, 30, num_envs, 40, True)
+  elif name == 'meta_s24_f64':
+    # many-sprite path: MetaAggregated of four FindGoalPosition sub-tasks over 24 sprites, float64 positions with velocities;
+    # sub-task 0's filter also keys on position (x >= 0.5: the sprite's label is looked up in the cell it stands in)
+    goals = [(0.75, 0.75), (0.75, 0.25), (0.25, 0.75), (0.25, 0.25)]
+    subs = [tasks.FindGoalPosition(filter_distrib=None, goal_position=g, terminate_distance=0.1,
+                                   raw_reward_multiplier=20.) for g in goals]
+    task = tasks.MetaAggregated(subs, reward_aggregator='mean', termination_criterion='any', terminate_bonus=1.)
+    aspace = action_spaces.SelectMove(scale=0.3, motion_cost=0.5)
+    rend = _renderers(64, aa)
+    hues = [(0.9, 1.0), (0.55, 0.65), (0.27, 0.37), (0.73, 0.83)] * 6
+    labels = [[int(i % 4 == j) for j in range(4)] for i in range(24)]
+    pool = synthetic.make_pool(rng, P, 24, hues, labels, n_tasks=4, shape_names=('square', 'triangle', 'circle', 'star_5'),
+                               scales=(0.05, 0.08), angles=(0, 30, 45))
+    pool.x[:] = rng.uniform(0.05, 0.95, size=pool.x.shape)
+    pool.y[:] = rng.uniform(0.05, 0.95, size=pool.y.shape)
+    pool.x_vel[:] = rng.uniform(-0.01, 0.01, size=pool.x.shape)
+    pool.y_vel[:] = rng.uniform(-0.01, 0.01, size=pool.x.shape)
+    pool.n_sprites[:] = rng.integers(17, 25, size=P)
+    cfg = lowering.lower_config(task, aspace, rend, True, 25, num_envs, 24, False)
+    cfg.tasks[0].n_xcuts, cfg.tasks[0].n_ycuts = 1, 0
+    cfg.tasks[0].xcuts[0] = 0.5
+    pool.cell_label = np.zeros((P, 4, 24, _abi.SWB_MAX_CELLS), np.int8)
+    pool.cell_label[:, 0, :, 1] = pool.label[:, 0, :]           # cell 1 (x >= 0.5): the colour filter; cell 0: no sprite
   elif name.startswith('fuzz_'):
     # randomised configuration (seeded by the name): image geometry, anti-aliasing, sprite counts,
     # shapes / scales / angles, task, action space, position dtype, velocities, background

@@ -1,0 +1,147 @@
+"""The many-sprite path (handles of 17 to 64 sprites: swb_ms_state_kernel, then the large-frame render kernels) on the
+emulated library against the oracle, to the bar of the `-m gpu` parity tests: state, rewards, step types and discounts
+bit-exact, frames +-0.  SWB_MANY_SPRITES=1 sends existing workloads of up to 16 sprites down the same path.
+TEST INFRASTRUCTURE: the emulator proves the arithmetic and control flow of the kernel source, not its speed --
+tests/test_gpu_many_sprites.py runs the real thing."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from spriteworld_amd import _abi
+from spriteworld_amd import workloads
+from tests import _many_sprites_cases as cases
+
+
+def _emu(cfg, pool):
+  from tests import _emu_engine
+  return _emu_engine.EmuEngine(cfg, pool)
+
+
+def _emu_torch(cfg, pool):
+  from tests import _emu_engine
+  return _emu_engine.EmuTorchEngine(cfg, pool)
+
+
+@pytest.mark.parametrize('name,n_envs,steps,aa', [('ragged_s64', 4, 10, 5), ('ragged_s64', 3, 6, 1), ('ragged_s64_embodied', 3, 12, 5),
+                                                   ('cluster_s40', 3, 6, 5), ('cluster_s40_f32a', 2, 4, 2), ('meta_s24_f64', 4, 10, 3)])
+def test_emulated_many_sprite_workloads(name, n_envs, steps, aa):
+  firsts, most = cases.run_parity(_emu, name, n_envs, steps, aa)
+  assert firsts >= n_envs and most > _abi.SWB_TUNED_SPRITES
+
+
+def test_emulated_ragged_s64_holds_empty_single_and_full_episodes():
+  cfg, pool, _ = workloads.build('ragged_s64', 4, episodes_per_env=2)
+  assert {0, 1, 64} <= set(pool.n_sprites.tolist())
+  firsts, most = cases.run_parity(_emu, 'ragged_s64', 4, 20, 2)
+  assert most == 64 and firsts > 4
+
+
+@pytest.mark.parametrize('name,n_envs,steps,aa', [('ragged_s16', 4, 10, 5), ('ragged_s16_embodied', 3, 10, 5), ('embodied_s12', 2, 4, 2),
+                                                   ('cluster9_s16', 2, 4, 3), ('f64_drag', 3, 6, 3), ('f64_cluster', 3, 6, 3),
+                                                   ('fuzz_3', 3, 6, 5), ('fuzz_11', 3, 6, 5), ('fuzz_23', 3, 6, 5), ('fuzz_42', 3, 6, 5)])
+def test_emulated_many_sprite_path_forced(monkeypatch, name, n_envs, steps, aa):
+  """SWB_MANY_SPRITES=1: workloads the tuned kernels take, through the many-sprite state kernel instead (every task,
+  action space and position dtype the fuzz configurations draw)."""
+  monkeypatch.setenv('SWB_MANY_SPRITES', '1')
+  cases.run_parity(_emu, name, n_envs, steps, aa)
+
+
+def test_emulated_setters_on_sprites_beyond_sixteen():
+  cases.setters_case(_emu_torch)
+
+
+def test_emulated_render_and_evaluate():
+  cases.render_and_evaluate_case(_emu_torch)
+
+
+def test_emulated_factors_and_sprite_types_beyond_sixteen():
+  from oracle import oracle
+  cfg, pool, sample = workloads.build('cluster_s40', 2, episodes_per_env=2, seed=3, anti_aliasing=2)
+  eng = _emu(cfg, pool)
+  eng.step(sample(np.random.default_rng(0)))
+  f = eng.factors()
+  st = eng.state()
+  e = st['pool_entry']
+  assert f.shape == (2, 40, 10)
+  np.testing.assert_array_equal(f[:, :, 0], st['x'])
+  np.testing.assert_array_equal(f[:, :, 4], pool.scale[e])
+  np.testing.assert_array_equal(f[:, :, 2], pool.shape[e] + 1)
+  assert eng.sprite_types(1, 39) == (False, False)
+  eng.close()
+
+
+def test_emulated_variant_reports_the_many_sprite_path(monkeypatch):
+  cfg, pool, _ = workloads.build('meta_s24_f64', 2, episodes_per_env=1)
+  v = _emu(cfg, pool).variant()
+  assert v['many_sprites'] == 1 and v['large_frames'] == 1 and v['run_list_bytes'] == 0
+  cfg, pool, _ = workloads.build('ragged_s16', 2, episodes_per_env=2)
+  assert _emu(cfg, pool).variant()['many_sprites'] == 0
+  monkeypatch.setenv('SWB_MANY_SPRITES', '1')
+  assert _emu(cfg, pool).variant()['many_sprites'] == 1
+
+
+def test_emulated_refuses_more_than_64_sprites():
+  from tests import _emu_engine
+  cfg, pool, _ = workloads.build('ragged_s64', 1, episodes_per_env=1)
+  for s in (65, 99):
+    cfg.max_sprites = s
+    with pytest.raises(_emu_engine.EmuError, match='64'):
+      _emu(cfg, None)
+
+
+def test_emulated_refuses_a_pool_beyond_the_raster_vertex_budget():
+  """64 sprites of 64-gons (4096 vertices) do not fit the raster kernel's LDS: swb_set_pool says so, naming the budget,
+  instead of the first launch failing."""
+  from spriteworld_amd import shapes
+  from tests import _emu_engine
+  from tests import _util
+  with _util.swapped_shape('circle', shapes.polygon(64)):
+    cfg, pool, _ = workloads.build('ragged_s64', 2, episodes_per_env=1)
+    pool.shape[:] = shapes.shape_index('circle')
+    pool.n_sprites[:] = 64
+    with pytest.raises(_emu_engine.EmuError, match='vertex budget of the large-frame raster kernel, [0-9]+ vertices'):
+      _emu(cfg, pool)
+    pool.n_sprites[:] = 20                  # 1280 vertices fit
+    _emu(cfg, pool).close()
+
+
+def test_emulated_device_sampler_of_forty_sprites(monkeypatch):
+  """swb_sample_pool with groups that add up to 40 sprites (shuffled): the pool equals the wide-slot model bit for bit, and
+  the environment steps like the oracle on it."""
+  from oracle import oracle
+  from spriteworld_amd import device_sampler, environment, lowering, shapes, sprite as sprite_lib, tasks
+  from spriteworld_amd import action_spaces
+  from spriteworld_amd import factor_distributions as distribs
+  from spriteworld_amd import renderers as renderer_lib
+  from tests import _emu_engine
+  from tests import _sampler_model_wide
+  monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuTorchEngine)
+  common = [distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
+            distribs.Discrete('shape', ['square', 'triangle', 'circle']), distribs.Discrete('scale', [0.05]),
+            distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)]
+  target = distribs.Product(common + [distribs.Continuous('c0', 0., 0.4)])
+  distractor = distribs.Product(common + [distribs.Continuous('c0', 0.5, 0.9)])
+  sampler = device_sampler.DeviceSampler([(target, 10), (distractor, (20, 31))], shuffle=True, seed=11)
+  task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=0.1)
+  rend = {'image': renderer_lib.PILRenderer(image_size=(32, 32), anti_aliasing=3, color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
+  env = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25), renderers=rend,
+                                       init_sprites=sampler, max_episode_length=6, num_envs=4, episodes_per_env=3,
+                                       refresh_every=0)
+  assert env._max_sprites == 40
+  sampler._draws -= 1
+  seed = sampler.next_seed()
+  label_fns = [(lambda f, sub=sub: lowering._label_of(sub, sprite_lib.Sprite(**f))) for sub in lowering.subtasks_of(task)]
+  want = _sampler_model_wide.sample_pool(env._sampler_spec, 12, 40, seed, rend['image']._color_to_rgb, label_fns, shapes.SHAPE_NAMES)
+  got = env.engine.get_pool()
+  assert (got.n_sprites >= 30).all() and got.n_sprites.max() > 36
+  for name in ('n_sprites', 'x', 'y', 'x_vel', 'y_vel', 'scale', 'cos_a', 'sin_a', 'angle', 'shape', 'rgb', 'color', 'label'):
+    np.testing.assert_array_equal(getattr(got, name), want[name], err_msg=name)
+  ora = oracle.Engine(env.engine.cfg, got)
+  rng = np.random.default_rng(5)
+  for t in range(4):
+    a = rng.uniform(0, 1, size=(4, 4))
+    want_o = ora.step(a)
+    env.engine.step(a)
+    cases.compare(t, ora, env.engine, want_o, env.engine.outputs_host())
+  env.close()
