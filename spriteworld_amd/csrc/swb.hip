@@ -466,8 +466,8 @@ size_t lf_lds_bytes(const swb_params& p, int max_verts_env) {
 // a pool must fail where it is installed, not at its first launch.
 int lf_check_vertices(const swb_engine* h, int verts, const char* what) {
   if (!h->large_frames || lf_lds_bytes(h->p, std::max(verts, 4)) <= SWB_LF_MAX_LDS) return 0;
-  int budget = 4;
-  while (lf_lds_bytes(h->p, budget + 1) <= SWB_LF_MAX_LDS) ++budget;
+  int budget = 4;                      // (the tables are sized in steps of 4 vertices: the budget named is one a scene can reach)
+  while (lf_lds_bytes(h->p, budget + 4) <= SWB_LF_MAX_LDS) budget += 4;
   return fail(SWB_ERR_INVALID, "%s: a scene of %d polygon vertices exceeds the vertex budget of the large-frame raster kernel, %d vertices "
               "per scene at a %d px canvas (160 KiB of LDS)", what, verts, budget, h->p.Wc);
 }

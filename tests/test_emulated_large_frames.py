@@ -119,9 +119,15 @@ def test_emulated_large_frames_render_and_trim():
   eng.close()
 
 
-def test_emulated_limits_name_the_limit():
+def test_emulated_limits_name_the_limit(monkeypatch):
   from tests import _emu_engine
-  for name, aa, what in (('geom_256x256', 17, '4096'), ('geom_1028x16', 1, '1024')):
+  for name, aa, what in (('geom_256x256', 17, '4096'), ('geom_1028x16', 1, '1024'), ('geom_516x16', 8, '4128x128 too large: at most 4096')):
     cfg, pool, _ = workloads.build(name, 1, episodes_per_env=1, anti_aliasing=aa)
     with pytest.raises(_emu_engine.EmuError, match=what):
       _emu(cfg, pool)
+  # the height alone: a 256 px wide canvas of up to 16 sprites is a large frame only when sent there (the tuned kernels take
+  # 4100 rows; tests/_many_sprites_cases.refusals_case has the case with 20 sprites, unforced)
+  monkeypatch.setenv('SWB_LARGE_FRAMES', '1')
+  cfg, pool, _ = workloads.build('geom_64x1025', 1, episodes_per_env=1, anti_aliasing=4)
+  with pytest.raises(_emu_engine.EmuError, match='256x4100 too large: at most 4096'):
+    _emu(cfg, pool)

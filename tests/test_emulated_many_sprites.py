@@ -56,19 +56,7 @@ def test_emulated_render_and_evaluate():
 
 
 def test_emulated_factors_and_sprite_types_beyond_sixteen():
-  from oracle import oracle
-  cfg, pool, sample = workloads.build('cluster_s40', 2, episodes_per_env=2, seed=3, anti_aliasing=2)
-  eng = _emu(cfg, pool)
-  eng.step(sample(np.random.default_rng(0)))
-  f = eng.factors()
-  st = eng.state()
-  e = st['pool_entry']
-  assert f.shape == (2, 40, 10)
-  np.testing.assert_array_equal(f[:, :, 0], st['x'])
-  np.testing.assert_array_equal(f[:, :, 4], pool.scale[e])
-  np.testing.assert_array_equal(f[:, :, 2], pool.shape[e] + 1)
-  assert eng.sprite_types(1, 39) == (False, False)
-  eng.close()
+  cases.factors_case(_emu)
 
 
 def test_emulated_variant_reports_the_many_sprite_path(monkeypatch):
@@ -106,42 +94,20 @@ def test_emulated_refuses_a_pool_beyond_the_raster_vertex_budget():
     _emu(cfg, pool).close()
 
 
+def _sampler_on_the_emulator(monkeypatch):
+  from spriteworld_amd import environment
+  from tests import _emu_engine
+  monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuTorchEngine)
+
+
 def test_emulated_device_sampler_of_forty_sprites(monkeypatch):
   """swb_sample_pool with groups that add up to 40 sprites (shuffled): the pool equals the wide-slot model bit for bit, and
   the environment steps like the oracle on it."""
-  from oracle import oracle
-  from spriteworld_amd import device_sampler, environment, lowering, shapes, sprite as sprite_lib, tasks
-  from spriteworld_amd import action_spaces
-  from spriteworld_amd import factor_distributions as distribs
-  from spriteworld_amd import renderers as renderer_lib
-  from tests import _emu_engine
-  from tests import _sampler_model_wide
-  monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuTorchEngine)
-  common = [distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-            distribs.Discrete('shape', ['square', 'triangle', 'circle']), distribs.Discrete('scale', [0.05]),
-            distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)]
-  target = distribs.Product(common + [distribs.Continuous('c0', 0., 0.4)])
-  distractor = distribs.Product(common + [distribs.Continuous('c0', 0.5, 0.9)])
-  sampler = device_sampler.DeviceSampler([(target, 10), (distractor, (20, 31))], shuffle=True, seed=11)
-  task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=0.1)
-  rend = {'image': renderer_lib.PILRenderer(image_size=(32, 32), anti_aliasing=3, color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
-  env = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25), renderers=rend,
-                                       init_sprites=sampler, max_episode_length=6, num_envs=4, episodes_per_env=3,
-                                       refresh_every=0)
-  assert env._max_sprites == 40
-  sampler._draws -= 1
-  seed = sampler.next_seed()
-  label_fns = [(lambda f, sub=sub: lowering._label_of(sub, sprite_lib.Sprite(**f))) for sub in lowering.subtasks_of(task)]
-  want = _sampler_model_wide.sample_pool(env._sampler_spec, 12, 40, seed, rend['image']._color_to_rgb, label_fns, shapes.SHAPE_NAMES)
-  got = env.engine.get_pool()
-  assert (got.n_sprites >= 30).all() and got.n_sprites.max() > 36
-  for name in ('n_sprites', 'x', 'y', 'x_vel', 'y_vel', 'scale', 'cos_a', 'sin_a', 'angle', 'shape', 'rgb', 'color', 'label'):
-    np.testing.assert_array_equal(getattr(got, name), want[name], err_msg=name)
-  ora = oracle.Engine(env.engine.cfg, got)
-  rng = np.random.default_rng(5)
-  for t in range(4):
-    a = rng.uniform(0, 1, size=(4, 4))
-    want_o = ora.step(a)
-    env.engine.step(a)
-    cases.compare(t, ora, env.engine, want_o, env.engine.outputs_host())
-  env.close()
+  _sampler_on_the_emulator(monkeypatch)
+  cases.device_sampler_case(40)
+
+
+def test_emulated_device_sampler_of_sixty_four_sprites(monkeypatch):
+  """... that add up to 64: every slot of the kernel's slot[SWB_MAX_SPRITES] in use."""
+  _sampler_on_the_emulator(monkeypatch)
+  cases.device_sampler_case(64)

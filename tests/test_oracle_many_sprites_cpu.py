@@ -30,6 +30,16 @@ def _bits(v):
                                                  ('select', 'meta', False), ('drag', 'cluster', False), ('embodied', 'meta', True),
                                                  ('select', 'cluster', True)])
 def test_ragged_episodes_of_17_to_64_sprites(space, task_kind, f32):
+  _ragged_episodes(space, task_kind, f32)
+
+
+def test_ragged_episodes_of_17_to_64_sprites_on_a_1280_pixel_canvas():
+  """The reference's own renderer at 256 x 256, anti_aliasing 5: the scene the GPU tests of the many-sprite path on large frames
+  hold the kernels to."""
+  _ragged_episodes('select', 'goal', True, image_size=(256, 256), steps=24)
+
+
+def _ragged_episodes(space, task_kind, f32, image_size=(64, 64), steps=60):
   ref_harness.load_reference()
   from spriteworld import action_spaces, environment, renderers, sprite, tasks
   from spriteworld import factor_distributions as distribs
@@ -65,7 +75,7 @@ def test_ragged_episodes_of_17_to_64_sprites(space, task_kind, f32):
   if space == 'embodied':       # Embodied needs a body: the reference indexes sprites[-1] (action_spaces.py:195)
     counts = [c for c in counts if c]
   episodes = [gen(n) for n in counts]
-  rends = {'image': renderers.PILRenderer(image_size=(64, 64), anti_aliasing=5, color_to_rgb=renderers.color_maps.hsv_to_rgb),
+  rends = {'image': renderers.PILRenderer(image_size=image_size, anti_aliasing=5, color_to_rgb=renderers.color_maps.hsv_to_rgb),
            'success': renderers.Success()}
   cfg = lowering.lower_config(task, aspace, rends, True, 6, 1, 64, pos_is_f32=f32)
   pool = lowering.lower_episodes(episodes, task, rends, max_sprites=64).assign_round_robin(1)
@@ -75,7 +85,7 @@ def test_ragged_episodes_of_17_to_64_sprites(space, task_kind, f32):
                                 max_episode_length=6)
   arng = np.random.RandomState(3)
   most = 0
-  for t in range(60):
+  for t in range(steps):
     if space == 'embodied':
       a = np.array([arng.randint(0, 2), arng.randint(0, 4)])
       ts = env.step([int(a[0]), int(a[1])])
