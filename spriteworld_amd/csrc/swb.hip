@@ -237,13 +237,17 @@ int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
   blo.push_back(p.Ho);
   p.nbands = nb;
   std::vector<int32_t> y0(nb, 0), first(nb, 0), lo(p.ncg, 0), hi(p.ncg, 0);
-  std::vector<uint32_t> brk((size_t)(p.Hc + 31) / 32 + 3, 0u);      // (+3: a batch reads three words from its first row's word)
+  // two bit tables, one behind the other: the rows that start a new run, and those among them where a band starts (the run
+  // that starts there heads a band's part of the list: never a continuation run, see emit_runs)
+  const size_t brk_words = (size_t)(p.Hc + 31) / 32 + 3;            // (+3: a batch reads three words from its first row's word)
+  std::vector<uint32_t> brk(2 * brk_words, 0u);
   auto set_break = [&](int y) { if (y >= 0 && y < p.Hc) brk[y >> 5] |= 1u << (y & 31); };
   for (int b = 0; b < nb; ++b) {
     const int o_lo = blo[b];
     if (p.AA == 1) { y0[b] = o_lo; first[b] = o_lo; }
     else { y0[b] = h->v_ymin_host[o_lo]; first[b] = first_in_flight(o_lo); }
     set_break(y0[b]);
+    if (y0[b] >= 0 && y0[b] < p.Hc) brk[brk_words + (y0[b] >> 5)] |= 1u << (y0[b] & 31);
   }
   if (p.AA != 1)
     for (int o = 0; o < p.Ho; ++o) set_break(h->v_end_host[o] + 1);

@@ -128,9 +128,11 @@ struct swb_params {
                                // visible spans sets SWB_ENV_ERR_SPAN_OVERFLOW
   // ---- hand-off from the cover kernel (P0..P2) to the resample / fill kernel (P3, P4): per environment and per
   // group of 64 output columns a list of RUNS of identical canvas rows with their visible spans, in 8-byte units
-  //   unit 0: { row | (rows - 1) << 16 | spans << 24,  span 0 }      span = start | end << 10 | sprite << 20
+  //   unit 0: { row | (rows - 1) << 16 | continuation << 23 | spans << 24,  span 0 }      span = start | end << 10 | sprite << 20
   //   unit 1: { span 1, span 2 }   (when spans >= 2; an absent span is 0 = empty)
   //   unit k: { span 2k-1, span 2k }   (spans > 3)
+  // A CONTINUATION run (SWB_RUN_CONTINUES, anti_aliasing > 1 only) is unit 0 alone: its rows have the spans of the run before it in
+  // the list, the spans field repeats that run's count (at least 1), span 0 is not read.  Bit 22 is free.
   // and a header (SWB_RHDR_DWORDS dwords): [0,16) colour minus background of sprite s as three signed 10-bit fields,
   // [16,32) its colour r | g << 8 | b << 16, then per column group { units in the list, first unit of band b ... }
   uint32_t* runs;              // [N][ncg][2 * run_cap]
@@ -152,7 +154,7 @@ struct swb_params {
   const int32_t* band_y0;      // [nbands] first canvas row that feeds the band's first output row
   const int32_t* band_first;   // [nbands] oldest output row still in flight at that canvas row; band_lo is chosen so that
                                // band_first % VS == 0 (the band's first in-flight row accumulates in slot 0)
-  const uint32_t* v_break;     // [ceil(Hc / 32)] bit y set: canvas row y starts a new run (an output row ended on y - 1, or a band starts at y)
+  const uint32_t* v_break;     // [2][ceil(Hc / 32) + 3] bit y of table 0 set: canvas row y starts a new run (an output row ended on y - 1, or a band starts at y); of table 1: a band starts at y
   const int32_t* cg_lo;        // [ncg] canvas columns [cg_lo, cg_hi) are the ones a column group's resampling windows reach
   const int32_t* cg_hi;
   // ---- cost-ordered dispatch: the cover kernel files every environment under the length of its run list (a good
@@ -1454,6 +1456,25 @@ __device__ __forceinline__ int dealt_block(const swb_params& p, int j, int block
 #define SWB_RHDR_DWORDS (SWB_RHDR_GROUPS + SWB_MAX_CG * SWB_RHDR_GSTRIDE + 4)
 #define SWB_BST_STRIDE (SWB_MAX_BANDS + 1)   // band starts of a list + its end, in LDS (swb_params::band_tasks: see emit_runs)
 __device__ __forceinline__ int run_units(int spans) { return spans <= 1 ? 1 : 2 + (spans > 3 ? (spans - 2) >> 1 : 0); }
+// Bit 23 of a run's first dword: a CONTINUATION run (anti_aliasing > 1 only).  Its rows have the spans of the run before it in the
+// list, which ended only because an output row's window ended with it; the record is one unit whatever that run's span count
+// (the spans field repeats the count, at least 1; the span dword is not read).
+#define SWB_RUN_CONTINUES (1u << 23)
+// Pins a scalar load in front of the branches that follow it (an empty statement that "uses" the value).  Without it the compiler
+// sinks the resample loop's two table loads below the test for the kind of run and joins the paths again through a flag register:
+// three more scalar instructions and a second taken branch for every run.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SWB_LOADED_HERE(v) __asm__ volatile("" : "+s"(v))
+#else
+#define SWB_LOADED_HERE(v) ((void)0)
+#endif
+// d = a << SH | b as ONE v_lshl_or_b32 (the compiler renders the C expression of a three-byte pack as two shifts and a three-input
+// or).  For the device only: the host side of the compilation, and a build of these sources for the host, take the C meaning.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SWB_LSHL_OR(d, a, SH, b) __asm__("v_lshl_or_b32 %0, %1, " #SH ", %2" : "=v"(d) : "v"(a), "v"(b))
+#else
+#define SWB_LSHL_OR(d, a, SH, b) ((d) = ((a) << (SH)) | (b))
+#endif
 
 // Hook of the profiling builds under tools/overlays (kernel cut short after a phase): nothing in the product.
 #ifndef SWB_HOOK_PHASE_END
@@ -1510,6 +1531,10 @@ __device__ __forceinline__ uint2 list_room_or_move(const swb_params& p, int env,
 //   * a row whose spans equal those of the row above continues that row's run (vertical edges, flat tops: the
 //     horizontal pass gives the same result and the vertical pass is linear in it), unless an output row ends
 //     between them or a band of output rows starts there (swb_params::v_break);
+//   * where only the end of an output row's window stands between them (anti_aliasing > 1), the row starts a CONTINUATION run: one
+//     unit without spans (SWB_RUN_CONTINUES) -- the resample kernel keeps the horizontal pass of the run before it.  Never the
+//     first run of a batch of 64 rows or of a band (the wave that starts at a band has no row yet); a list that moves to the
+//     arena stays one contiguous array, so a continuation always follows its head;
 //   * with a black background a row without spans adds nothing and is not listed (anti_aliasing = 1: never
 //     listed, the fill kernel paints what no run covers with the background);
 //   * images wider than 64 columns: a column group lists only the spans its resampling windows reach, clipped to
@@ -1531,6 +1556,13 @@ __device__ __forceinline__ void emit_runs(const swb_params& p, const uint32_t* s
   const unsigned long long b01 = (unsigned long long)bw[0] | ((unsigned long long)bw[1] << 32);
   const int bp = (yb & 31) + l;                                         // 0 .. 94
   const bool brk = ((bp < 64 ? (uint32_t)(b01 >> bp) : (bw[2] >> (bp - 64))) & 1u) != 0u;
+  // ... and the same of the table behind it: rows where a band starts (no continuation run there: the band's wave has no row yet)
+  bool may_continue = false;
+  if (p.AA != 1) {
+    cptr<uint32_t> sw = bw + (((p.Hc + 31) >> 5) + 3);
+    const unsigned long long s01 = (unsigned long long)sw[0] | ((unsigned long long)sw[1] << 32);
+    may_continue = brk && ((bp < 64 ? (uint32_t)(s01 >> bp) : (sw[2] >> (bp - 64))) & 1u) == 0u;
+  }
   const int cnt = valid ? (int)rs.cnt : 0;
   // (the longest span list of the batch: only the slow paths below need it)
   const int maxc = (p.ncg != 1 || __ballot(cnt > SWB_REG_SPANS)) ? wave_max_i(cnt) : SWB_REG_SPANS;
@@ -1570,11 +1602,15 @@ __device__ __forceinline__ void emit_runs(const swb_params& p, const uint32_t* s
     const int p0 = __builtin_amdgcn_update_dpp(0, (int)f0, 0x138, 0xf, 0xf, false);
     const int p1 = __builtin_amdgcn_update_dpp(0, (int)f1, 0x138, 0xf, 0xf, false);
     const int p2 = __builtin_amdgcn_update_dpp(0, (int)f2, 0x138, 0xf, 0xf, false);
-    const bool cont = nonempty && l > 0 && !brk && fc == pc && fc <= SWB_REG_SPANS && (int)f0 == p0 && (int)f1 == p1 && (int)f2 == p2;
+    const bool same = nonempty && l > 0 && fc == pc && fc <= SWB_REG_SPANS && (int)f0 == p0 && (int)f1 == p1 && (int)f2 == p2;
+    const bool cont = same && !brk;
     const bool start = nonempty && !cont;
+    // a run that had to end only because an output row's window ends there: the rows below it with the same spans become a
+    // CONTINUATION run -- one unit without spans, the resample kernel keeps the horizontal pass of the run before
+    const bool contin = same && may_continue;
     const unsigned long long contm = __ballot(cont);
     const int len = 1 + __builtin_ctzll(~((contm >> 1) >> l));          // rows of the run that starts here (bit 63 of the shifted mask is 0)
-    const int units = start ? run_units(fc) : 0;
+    const int units = start ? (contin ? 1 : run_units(fc)) : 0;
     // inclusive prefix sum over the lanes: within rows of 16 lanes by DPP shifts, then the three row totals
     int incl = units;
     incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);   // row_shr:1
@@ -1598,8 +1634,8 @@ __device__ __forceinline__ void emit_runs(const swb_params& p, const uint32_t* s
     if (!room) err |= SWB_ENV_ERR_SPAN_OVERFLOW;
     uint32_t* dst = runs_env + (size_t)g * p.run_cap * 2 + 2 * ((long long)base_g + excl);
     if (start && room) {
-      *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)y | ((uint32_t)(len - 1) << 16) | ((uint32_t)fc << 24), f0);
-      if (fc >= 2) *reinterpret_cast<uint2*>(dst + 2) = make_uint2(f1, f2);
+      *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)y | ((uint32_t)(len - 1) << 16) | (contin ? SWB_RUN_CONTINUES | ((uint32_t)max(fc, 1) << 24) : (uint32_t)fc << 24), f0);
+      if (fc >= 2 && !contin) *reinterpret_cast<uint2*>(dst + 2) = make_uint2(f1, f2);
     }
     if (room && __ballot(start && fc > SWB_REG_SPANS)) {                // spans beyond three: units 2, 3, ...
       int j = 0;
@@ -1632,7 +1668,8 @@ __device__ __forceinline__ void emit_runs(const swb_params& p, const uint32_t* s
       ++next_band_g;
     }
     // what the batch adds to the cost of the list (the key it is filed under)
-    const int cost_g = SWB_RUN_COST * __popcll(__ballot(start)) + SWB_UNIT_COST * total;
+    // (a continuation run: the vertical pass of a run, no spans -- its unit is not charged)
+    const int cost_g = SWB_RUN_COST * __popcll(__ballot(start)) + SWB_UNIT_COST * (total - __popcll(__ballot(contin)));
     if (l == g) { base_l = room ? base_g + total : base_g; band_l = (int)((meta_g & ~15u) | (uint32_t)next_band_g); cost_l += room ? cost_g : 0; }
   }
 }
@@ -2178,6 +2215,10 @@ swb_cover_kernel(const swb_params p) {
 // and the table rows are 32-bit byte offsets of scalar loads, the accumulator slot of the row being finished is
 // a compile-time constant (the row loop is unrolled VS times; bands start on a multiple of VS rows in flight),
 // a slot that received nothing since its restart is recognised by the list position not having moved.
+// A run record is { row | rows-1 << 16 | continuation << 23 | spans << 24, span 0 } [{ span 1, span 2 } ...] (swb_params::runs).  A
+// continuation run -- the rows below a forced run end that have the spans of the run before it -- is one unit: the loop skips
+// from the two table loads straight to the vertical pass with the h[0..2] it holds (clipped, live across iterations); the
+// list position moves by one unit, so the "untouched slot" test above works as before.
 typedef uint32_t swb_u4 __attribute__((ext_vector_type(4), aligned(8)));      // a run record starts on an 8-byte unit
 typedef int32_t swb_i8 __attribute__((ext_vector_type(8), aligned(32)));
 template <int VS>
@@ -2264,6 +2305,7 @@ swb_resample_kernel(const swb_params p) {
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(h[2]) : "v"(w), "s"(d2), "v"(bgtot2));
   };
   swb_u4 rec = *reinterpret_cast<cptr<swb_u4>>(runs + uo);       // { row | rows-1 << 16 | spans << 24, span 0, span 1, span 2 }
+  int h[3] = {0, 0, 0};                                // the horizontal pass of the last run that carried spans, clipped
   bool more = true;
   while (more) {
 #pragma unroll
@@ -2272,24 +2314,31 @@ swb_resample_kernel(const swb_params p) {
       while ((int)(rec.x & 0xffffu) <= next_end) {
         const uint32_t ro = (rec.x & 0xffffu) << 5;                                      // SWB_VSLOTS * 4 bytes per table row
         const uint32_t eo = ro + ((rec.x >> 11) & (63u << 5));
-        const int ns = (int)(rec.x >> 24);
-        const swb_i8 ps = *reinterpret_cast<cptr<swb_i8>>(vpfx + ro);
-        const swb_i8 pe = *reinterpret_cast<cptr<swb_i8>>(vpfx + eo + 32);
+        swb_i8 ps = *reinterpret_cast<cptr<swb_i8>>(vpfx + ro);
+        swb_i8 pe = *reinterpret_cast<cptr<swb_i8>>(vpfx + eo + 32);
+        SWB_LOADED_HERE(ps); SWB_LOADED_HERE(pe);
         // horizontal pass of the run's row (Resample.c ImagingResampleHorizontal_8bpc).  The first span starts from
         // the background total, so h needs no separate initialisation; an absent span is empty (0..0).
-        int h[3];
-        first_span(rec.y, h);
-        if (ns >= 2) {
-          add_span(rec.z, h);
-          if (ns >= 3) {
-            add_span(rec.w, h);
-            for (int m = SWB_REG_SPANS; m < ns; ++m)
-              add_span(*reinterpret_cast<cptr<uint32_t>>(runs + uo + 8u * (uint32_t)(2 + ((m - 3) >> 1)) + 4u * (uint32_t)((m - 3) & 1)), h);
+        // A continuation run (SWB_RUN_CONTINUES: one unit) keeps the h of the run before it.  (Regions of if-then only: an
+        // if-else on the kind of run -- one span / several / continuation -- comes out of the compiler with a flag register
+        // and two more branches on the path of the one-span run.)
+        const uint32_t u0 = uo;
+        uo += 8u;                                                                        // a run of up to one span, a continuation: one unit
+        if (__builtin_expect(!(rec.x & SWB_RUN_CONTINUES), 1)) {
+          const int ns = (int)(rec.x >> 24);
+          first_span(rec.y, h);
+          if (ns >= 2) {
+            add_span(rec.z, h);
+            uo += (uint32_t)(ns >> 1) << 3;                                              // run_units(ns) * 8 in all
+            if (ns >= 3) {
+              add_span(rec.w, h);
+              for (int m = SWB_REG_SPANS; m < ns; ++m)
+                add_span(*reinterpret_cast<cptr<uint32_t>>(runs + u0 + 8u * (uint32_t)(2 + ((m - 3) >> 1)) + 4u * (uint32_t)((m - 3) & 1)), h);
+            }
           }
+          h[0] = clip8_fix(h[0]); h[1] = clip8_fix(h[1]); h[2] = clip8_fix(h[2]);
         }
-        uo += (uint32_t)((ns + 2) >> 1) << 3;                                            // run_units(ns) * 8
         rec = *reinterpret_cast<cptr<swb_u4>>(runs + uo);
-        h[0] = clip8_fix(h[0]); h[1] = clip8_fix(h[1]); h[2] = clip8_fix(h[2]);
         // vertical pass contribution (Resample.c ImagingResampleVertical_8bpc): coefficient sums of the run's rows
 #pragma unroll
         for (int j = 0; j < VS; ++j) {
@@ -2307,8 +2356,13 @@ swb_resample_kernel(const swb_params p) {
         if (r_first >= o_lo) {
           uint32_t dw = 0u;
           if (!untouched) {
-            const uint32_t px = (uint32_t)clip8_fix(acc[0][k]) | ((uint32_t)clip8_fix(acc[1][k]) << 8) | ((uint32_t)clip8_fix(acc[2][k]) << 16);
-            const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)px, 0xF9, 0xf, 0xf, false);   // quad_perm:[1,2,3,3]
+            // px = c0 | c1 << 8 | c2 << 16 in two shift-and-or instructions (written in C: two shifts and a three-input or);
+            // the DPP move with bound_ctrl, so that no register has to be zeroed for lanes the move does not reach (there are none)
+            const uint32_t c0 = (uint32_t)clip8_fix(acc[0][k]), c1 = (uint32_t)clip8_fix(acc[1][k]), c2 = (uint32_t)clip8_fix(acc[2][k]);
+            uint32_t px01, px;
+            SWB_LSHL_OR(px01, c1, 8, c0);
+            SWB_LSHL_OR(px, c2, 16, px01);
+            const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)px, 0xF9, 0xf, 0xf, true);    // quad_perm:[1,2,3,3]
             dw = __builtin_amdgcn_perm(nb, px, pack_sel);
           }
           if (pack_store) *reinterpret_cast<uint32_t*>(frame_bytes + dst_off) = dw;

@@ -15,8 +15,11 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from spriteworld_amd import workloads  # noqa: E402
-from tests import _emu_engine  # noqa: E402
-from tests.emu import build_emu  # noqa: E402
+from tests import _emu_counters, _emu_engine  # noqa: E402
+
+# the counting build of the emulator + the counters of the continuation runs (tests/_emu_counters.py)
+build_emu = _emu_counters.load()
+_emu_engine.build_emu = build_emu
 
 
 def main():
@@ -42,6 +45,7 @@ def main():
   if vals['p3_row_runs']:
     print('  rows per run %.2f, spans per run %.2f, 8-byte units per run %.2f' % (
         vals['p3_rows_in_runs'] / vals['p3_row_runs'], vals['p3_spans'] / vals['p3_row_runs'], vals['run_units'] / vals['p3_row_runs']))
+    print('  continuation runs: %.1f %% of the runs' % (100.0 * vals['p3_continuation_runs'] / vals['p3_row_runs']))
   return vals
 
 
@@ -54,7 +58,10 @@ def resample_valu_model(vals):
   is kept as it was, so that the figures of the rounds compare; a scene of many spans per run measures slightly below it.)"""
   runs, spans = vals['p3_row_runs'], vals['p3_spans']
   done, clean = vals['p3_completed_rows'], vals['p3_clean_rows']
-  return 33 * runs + 10 * (spans - runs) + 17 * (done - clean) + 1 * clean + 150
+  # a continuation run skips the horizontal pass: the 15 of the first span and the clip, and 10 per further span of its head
+  # (p3_spans counts a continuation's spans as its head's, so the terms above are what they were without continuations)
+  cruns, cspans = vals.get('p3_continuation_runs', 0), vals.get('p3_continuation_spans', 0)
+  return 33 * runs + 10 * (spans - runs) + 17 * (done - clean) + 1 * clean + 150 - 15 * cruns - 10 * (cspans - cruns)
 
 
 if __name__ == '__main__':

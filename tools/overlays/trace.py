@@ -41,8 +41,9 @@ def apply(files, arg, replace_once):
                '    t[5] = hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE];\n'
                '    t[6] = exp_runs; t[7] = exp_spans;\n'
                '  }\n' + '}\n')
-  replace_once(files, k, '        const int ns = (int)(rec.x >> 24);\n        const swb_i8 ps =',
-               '        const int ns = (int)(rec.x >> 24);\n        exp_runs += 1; exp_spans += (unsigned)ns;\n        const swb_i8 ps =')
+  # (a continuation run carries no spans: it keeps the horizontal pass of the run before it)
+  replace_once(files, k, '        swb_i8 ps =',
+               '        exp_runs += 1; exp_spans += (rec.x & SWB_RUN_CONTINUES) ? 0u : (unsigned)(rec.x >> 24);\n        swb_i8 ps =')
   replace_once(files, k, '  swb_u4 rec = *reinterpret_cast<cptr<swb_u4>>(runs + uo);       // { row',
                '  unsigned exp_runs = 0, exp_spans = 0;\n  swb_u4 rec = *reinterpret_cast<cptr<swb_u4>>(runs + uo);       // { row')
   h = 'swb.hip'
