@@ -626,6 +626,225 @@ __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double
 }
 
 // --------------------------------------------------------------------------------------------
+// The state phase of a step -- everything the reference environment does before a frame is drawn (environment.py step() /
+// reset(), action_spaces.py, tasks.py) -- in three pieces: load_env_state, act_and_move, finish_step.  The cover kernel (its P0)
+// and the many-sprite state kernel both run these, so there is one copy of the arithmetic.  One wave = one environment.
+// --------------------------------------------------------------------------------------------
+struct env_state {            // what load_env_state hands on; per lane, lane s < n = sprite s
+  bool first, ov;             // (uniform) this step resets the episode; the episode's sprites carry setter overrides
+  int en, n, sc_old;          // (uniform) pool entry, sprites, steps taken so far
+  double px, py;              // position
+  double scale_l, ca_l, sa_l, xv_l, yv_l;
+  int sh_idx, so_l, nv_l;     // entry of the shape tables; its path's offset and vertex count there (0 for lanes >= n)
+  double act;                 // lanes 0..3: the action components
+  int acti;                   // lanes 0..1: ... of the embodied action space
+};
+struct step_cost { double cost; float cost_f32; bool cost_is_f32; int step_count; };   // what act_and_move hands to finish_step
+
+// Round 1 of loads (independent of each other): the environment's scalars, its live positions
+// and its action.  Round 2 (needs the pool entry): the episode's static sprite columns.
+template <bool OV, typename SC>
+__device__ __forceinline__ env_state load_env_state(const swb_params& p, int env, SC* tscratch) {
+  const int l = lane_id();
+  const int S = p.S;
+  double* gx = p.x + (size_t)env * S;
+  double* gy = p.y + (size_t)env * S;
+  const int rn = p.render_only ? 0 : (int)p.reset_next[env];
+  const int ep = p.episode[env], pbase = as_const(p.pool_base)[env], plen = as_const(p.pool_len)[env];
+  const int en_old = p.entry[env], n_old = p.nspr[env], sc_old = p.step_count[env];
+  double px = 0.0, py = 0.0;      // lane s < n holds sprite s's position
+  if (l < S) { px = gx[l]; py = gy[l]; }
+  // (the small table of shape offsets whole, lane i = entry i: looked up below with cross-lane reads once the shapes are known)
+  static_assert(SWB_MAX_SHAPES + 1 <= SWB_WAVE, "one lane per entry of the shape table");
+  const int shoff_tab_l = (l <= SWB_MAX_SHAPES) ? p.shape_off[l] : 0;
+  double act = 0.0;               // lanes 0..3: the action components
+  int acti = 0;
+  if (!p.render_only) {
+    if (p.action_space == SWB_ACTION_EMBODIED) { if (l < 2) acti = reinterpret_cast<const int32_t*>(p.actions)[2 * (size_t)env + l]; }
+    else if (l < 4) {
+      act = p.action_is_f32 ? (double)reinterpret_cast<const float*>(p.actions)[4 * (size_t)env + l]
+                            : reinterpret_cast<const double*>(p.actions)[4 * (size_t)env + l];
+    }
+  }
+  const bool first = rn != 0;                           // environment.py:90-91 -> reset() :74-78
+  bool ov = false;                                      // this episode's sprites carry setter overrides
+  if constexpr (OV) {
+    ov = rfl((int)p.ov_flag[env]) != 0;
+    if (ov && first) {                                  // a reset draws fresh sprites: the overrides end here
+      ov = false;
+      if (l == 0) p.ov_flag[env] = 0;
+    }
+  }
+  const int en = rfl(first ? pbase + (ep % plen) : en_old);
+  const size_t pe = (size_t)en * S;
+  int n = first ? as_const(p.p_n)[en] : n_old;
+  int shape_l = 0;
+  double scale_l = 1.0, ca_l = 1.0, sa_l = 0.0, xv_l = 0.0, yv_l = 0.0;
+  if (l < S) {
+    shape_l = p.p_shape[pe + l]; scale_l = p.p_scale[pe + l]; ca_l = p.p_ca[pe + l]; sa_l = p.p_sa[pe + l];
+    xv_l = p.p_xv[pe + l]; yv_l = p.p_yv[pe + l];
+    if (first) { px = p.p_x[pe + l]; py = p.p_y[pe + l]; gx[l] = px; gy[l] = py; }
+    if constexpr (OV) {
+      if (ov) { shape_l = p.ov_shape[(size_t)env * S + l]; scale_l = p.ov_scale[(size_t)env * S + l]; }
+    }
+  }
+  if (p.render_only != 1) {
+    const int8_t* lab_src = p.p_label + (size_t)en * p.n_tasks * S;
+    if constexpr (OV) { if (ov) lab_src = p.ov_label + (size_t)env * p.n_tasks * S; }
+    for (int i = l; i < p.n_tasks * S; i += SWB_WAVE) tscratch->labels[i] = lab_src[i];
+  }
+  n = rfl(n);
+  if (first && l == 0) { p.episode[env] = ep + 1; p.entry[env] = en; p.nspr[env] = n; p.step_count[env] = 0; p.reset_next[env] = 0; }
+  // lane s: vertex count and offset of sprite s in the shape table
+  // (cross-lane reads with every lane active; shape ids are below SWB_MAX_SHAPES: swb_set_pool / the sampler / the setters check)
+  const int sh_idx = (int)min((uint32_t)shape_l, (uint32_t)(SWB_MAX_SHAPES - 1));
+  const int so_any = __shfl(shoff_tab_l, sh_idx, 64), so_next = __shfl(shoff_tab_l, sh_idx + 1, 64);
+  const int so_l = (l < n) ? so_any : 0;
+  const int nv_l = (l < n) ? so_next - so_any : 0;
+  return env_state{first, ov, en, n, sc_old, px, py, scale_l, ca_l, sa_l, xv_l, yv_l, sh_idx, so_l, nv_l, act, acti};
+}
+
+// Action decoding, the hit tests (hit(s2, tx, ty): sprite.py:113-115 contains_point of sprite s2 -- wave-uniform -- at the
+// offset (tx, ty) from its position), motion, velocities, keep_in_frame: positions move in `es` and in memory.
+template <typename HIT>
+__device__ __forceinline__ step_cost act_and_move(const swb_params& p, int env, env_state& es, HIT hit) {
+  const int l = lane_id(), n = es.n;
+  double &px = es.px, &py = es.py;
+  double* gx = p.x + (size_t)env * p.S;
+  double* gy = p.y + (size_t)env * p.S;
+  double cost = 0.0;
+  float cost_f32 = 0.0f;
+  bool cost_is_f32 = false;
+  int step_count = 0;
+  if (!p.render_only && !es.first) {
+    step_count = es.sc_old + 1;                         // :93
+    int moved = -1;
+    double m0 = 0.0, m1 = 0.0;
+    if (p.action_space == SWB_ACTION_EMBODIED) {        // action_spaces.py:187-214
+      const int carry = __builtin_amdgcn_readlane(es.acti, 0), dir = __builtin_amdgcn_readlane(es.acti, 1);
+      const double st = p.action_scale;
+      if (dir == 0) m1 = st; else if (dir == 1) m0 = -st; else if (dir == 2) m1 = -st; else m0 = st;
+      if (n > 0) {
+        const int body = n - 1;
+        const double bx = readlane_d(px, body), by = readlane_d(py, body);
+        if (carry) {                                     // get_carried_sprite :180-185
+          for (int s2 = body - 1; s2 >= 0; --s2) {
+            const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
+            double tx, ty;
+            if (p.pos_is_f32) { tx = (double)__fsub_rn((float)bx, (float)sx); ty = (double)__fsub_rn((float)by, (float)sy); }
+            else { tx = __dsub_rn(bx, sx); ty = __dsub_rn(by, sy); }
+            if (hit(s2, tx, ty)) {
+              moved = s2;
+              break;
+            }
+          }
+        }
+        if (l == moved || l == body) {
+          px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
+          py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
+        }
+      }
+      cost = __dmul_rn(-p.motion_cost, st);             // :214
+    } else {                                             // action_spaces.py:83-104
+      const double a0 = readlane_d(es.act, 0), a1 = readlane_d(es.act, 1);
+      const double a2 = readlane_d(es.act, 2), a3 = readlane_d(es.act, 3);
+      // float32 actions (action_spec() dtype): numpy keeps (a - 0.5) * scale, the motion norm and,
+      // against a float32 position, the click offset in float32 (NEP 50); `act` holds them exactly
+      const bool af = p.action_is_f32 != 0;
+      if (af) {
+        const float f0 = (float)a0, f1 = (float)a1, f2 = (float)a2, f3 = (float)a3, sc = (float)p.action_scale;
+        float m0f, m1f;
+        if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { m0f = __fmul_rn(__fsub_rn(f2, f0), sc); m1f = __fmul_rn(__fsub_rn(f3, f1), sc); }
+        else { m0f = __fmul_rn(__fsub_rn(f2, 0.5f), sc); m1f = __fmul_rn(__fsub_rn(f3, 0.5f), sc); }
+        m0 = (double)m0f; m1 = (double)m1f;
+        cost_f32 = __fmul_rn((float)(-p.motion_cost), sqrtf(__fadd_rn(__fmul_rn(m0f, m0f), __fmul_rn(m1f, m1f))));
+        cost = (double)cost_f32;
+        cost_is_f32 = true;
+      } else if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { // :133-137
+        m0 = __dmul_rn(__dsub_rn(a2, a0), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, a1), p.action_scale);
+      } else {                                           // :65-67
+        m0 = __dmul_rn(__dsub_rn(a2, 0.5), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, 0.5), p.action_scale);
+      }
+      for (int s2 = n - 1; s2 >= 0; --s2) {              // sprites[::-1] :77-81
+        const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
+        double tx, ty;
+        if (af && p.pos_is_f32) { tx = (double)__fsub_rn((float)a0, (float)sx); ty = (double)__fsub_rn((float)a1, (float)sy); }
+        else { tx = __dsub_rn(a0, sx); ty = __dsub_rn(a1, sy); }
+        if (hit(s2, tx, ty)) {
+          moved = s2;
+          break;
+        }
+      }
+      if (l == moved) {
+        px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
+        py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
+      }
+      if (!af) cost = __dmul_rn(-p.motion_cost, __dsqrt_rn(dot2_hi(m0, m1, m0, m1)));   // :104
+    }
+    if (l < n) {                                         // update_position :98-99
+      px = move1(p.pos_is_f32, px, es.xv_l, p.keep_in_frame);
+      py = move1(p.pos_is_f32, py, es.yv_l, p.keep_in_frame);
+      gx[l] = px; gy[l] = py;
+    }
+  }
+  return step_cost{cost, cost_f32, cost_is_f32, step_count};
+}
+
+// Task reward / success (spread over the lanes), out-of-frame, termination; the outputs of the step.  Returns the error
+// bits of the environment (lane 0; the caller stores them).
+template <bool OV, typename SC>
+__device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, const env_state& es, const step_cost& c, SC* tscratch) {
+  const int l = lane_id(), S = p.S, n = es.n;
+  const double px = es.px, py = es.py;
+  wave_sync();
+  // tasks.py:134-137, 196-205: `contains(sprite.factors)` is evaluated at every step and x / y are factors -- a task whose
+  // filter keys on position takes every sprite's label from the cell of the task's grid the sprite stands in NOW (lanes =
+  // sprites; swb_task::xcuts / ycuts: the comparisons are numpy's, the bounds already rounded to the position dtype)
+  if (p.p_cell_label != nullptr) {                     // (wave-uniform; no shipped configuration)
+    const int8_t* cells = p.p_cell_label + (size_t)es.en * p.n_tasks * S * SWB_MAX_CELLS;
+    if constexpr (OV) { if (es.ov && p.ov_cell_label) cells = p.ov_cell_label + (size_t)env * p.n_tasks * S * SWB_MAX_CELLS; }
+    for (int t = 0; t < p.n_tasks; ++t) {
+      const swb_task& tk = p.tasks[t];
+      if (tk.n_xcuts + tk.n_ycuts == 0) continue;
+      if (l < n) {
+        int cx = 0, cy = 0;
+        for (int k = 0; k < tk.n_xcuts; ++k) cx += (px >= tk.xcuts[k]) ? 1 : 0;
+        for (int k = 0; k < tk.n_ycuts; ++k) cy += (py >= tk.ycuts[k]) ? 1 : 0;
+        tscratch->labels[t * S + l] = cells[((size_t)t * S + l) * SWB_MAX_CELLS + cy * (tk.n_xcuts + 1) + cx];
+      }
+    }
+    wave_sync();
+  }
+  const bool oof_l = (l < n) && !(px >= 0. && py >= 0. && px <= 1. && py <= 1.);   // sprite.py:135-138
+  const int oof = __ballot(oof_l) != 0ull;
+  double tr = 0.0; int ok = 0;
+  const int terr = eval_task_wave(p, n, px, py, tscratch->labels, tscratch, &tr, &ok);
+  if (l == 0) {
+    if (p.success) p.success[env] = (uint8_t)ok;
+    if (p.render_only) {
+      // (swb_evaluate: environment.py:80-81 success() of the current sprites, no time step)
+    } else if (es.first) {
+      if (p.reward) p.reward[env] = __longlong_as_double(0x7ff8000000000000ll);
+      if (p.discount) p.discount[env] = __int_as_float(0x7fc00000);
+      if (p.step_type) p.step_type[env] = SWB_STEP_FIRST;
+    } else {
+      // :101 reward += task.reward.  A float32 cost plus a Python-float task reward (NoReward,
+      // Clustering) stays float32 under NEP 50; np.float64 rewards promote to float64.
+      const bool task_is_pyfloat = !p.is_meta && p.tasks[0].kind != SWB_TASK_FIND_GOAL;
+      const double rew = (c.cost_is_f32 && task_is_pyfloat) ? (double)__fadd_rn(c.cost_f32, (float)tr) : __dadd_rn(c.cost, tr);
+      if (p.reward) p.reward[env] = rew;
+      const int timeout = c.step_count >= p.max_episode_length;          // :84
+      const int last = ok || oof || timeout;                             // :104-106
+      p.step_count[env] = c.step_count;
+      if (last) p.reset_next[env] = 1;
+      if (p.step_type) p.step_type[env] = last ? SWB_STEP_LAST : SWB_STEP_MID;
+      if (p.discount) p.discount[env] = last ? 0.0f : 1.0f;
+    }
+  }
+  return l == 0 ? (uint32_t)terr : 0u;
+}
+
+// --------------------------------------------------------------------------------------------
 // LDS layout (per wave)
 // --------------------------------------------------------------------------------------------
 struct edge_rec {        // 16 bytes; canvas coordinates must fit int16 (else SWB_ENV_ERR_SPAN_OVERFLOW)
@@ -1767,8 +1986,6 @@ swb_cover_kernel(const swb_params p) {
   int32_t* ovf = &L->ovf_slot;
   if (l == 0) *ovf = -1;
   const int S = p.S;
-  double* gx = p.x + (size_t)env * S;
-  double* gy = p.y + (size_t)env * S;
 
   // Centred paths of all sprites (float64 pairs): in the mask area while it is idle (P0/P1), or
   // in their own region when the masks are too small (tiny canvases).
@@ -1778,69 +1995,21 @@ swb_cover_kernel(const swb_params p) {
   static_assert(sizeof(double2) == sizeof(edge_rec), "centred paths alias the edge records");
 
   // ------------------------------------------------------------------ P0: state
-  // Round 1 of loads (independent of each other): the environment's scalars, its live positions
-  // and its action.  Round 2 (needs the pool entry): the episode's static sprite columns.
+  // (with the state's two rounds of loads, the kernel's own: the shape table P1b looks up whole, lane i = entry i; the fill colours)
   uint32_t err = 0;
-  const int rn = p.render_only ? 0 : (int)p.reset_next[env];
-  const int ep = p.episode[env], pbase = as_const(p.pool_base)[env], plen = as_const(p.pool_len)[env];
-  const int en_old = p.entry[env], n_old = p.nspr[env], sc_old = p.step_count[env];
-  double px = 0.0, py = 0.0;      // lane s < n holds sprite s's position
-  if (l < S) { px = gx[l]; py = gy[l]; }
-  // (the two small shape tables whole, lane i = entry i: looked up below with cross-lane reads once the shapes are known)
-  static_assert(SWB_MAX_SHAPES + 1 <= SWB_WAVE, "one lane per entry of the shape tables");
-  const int shoff_tab_l = (l <= SWB_MAX_SHAPES) ? p.shape_off[l] : 0;
   const double shdmin_tab_l = (l < SWB_MAX_SHAPES) ? p.shape_dmin[l] : 0.0;
-  double act = 0.0;               // lanes 0..3: the action components
-  int acti = 0;
-  if (!p.render_only) {
-    if (p.action_space == SWB_ACTION_EMBODIED) { if (l < 2) acti = reinterpret_cast<const int32_t*>(p.actions)[2 * (size_t)env + l]; }
-    else if (l < 4) {
-      act = p.action_is_f32 ? (double)reinterpret_cast<const float*>(p.actions)[4 * (size_t)env + l]
-                            : reinterpret_cast<const double*>(p.actions)[4 * (size_t)env + l];
-    }
-  }
-  const bool first = rn != 0;                           // environment.py:90-91 -> reset() :74-78
-  bool ov = false;                                      // this episode's sprites carry setter overrides
-  if constexpr (OV) {
-    ov = rfl((int)p.ov_flag[env]) != 0;
-    if (ov && first) {                                  // a reset draws fresh sprites: the overrides end here
-      ov = false;
-      if (l == 0) p.ov_flag[env] = 0;
-    }
-  }
-  const int en = rfl(first ? pbase + (ep % plen) : en_old);
-  const size_t pe = (size_t)en * S;
-  int n = first ? as_const(p.p_n)[en] : n_old;
-  int shape_l = 0;
-  double scale_l = 1.0, ca_l = 1.0, sa_l = 0.0, xv_l = 0.0, yv_l = 0.0;
+  env_state es = load_env_state<OV>(p, env, tscratch);
+  const int n = es.n, nv_l = es.nv_l;
+  const double scale_l = es.scale_l;
   uint32_t rgb_reg = 0u;                                // lane s: fill colour of sprite s
-  if (l < S) {
-    shape_l = p.p_shape[pe + l]; scale_l = p.p_scale[pe + l]; ca_l = p.p_ca[pe + l]; sa_l = p.p_sa[pe + l];
-    xv_l = p.p_xv[pe + l]; yv_l = p.p_yv[pe + l]; rgb_reg = p.p_rgb[pe + l];
-    if (first) { px = p.p_x[pe + l]; py = p.p_y[pe + l]; gx[l] = px; gy[l] = py; }
-    if constexpr (OV) {
-      if (ov) { shape_l = p.ov_shape[(size_t)env * S + l]; scale_l = p.ov_scale[(size_t)env * S + l]; }
-    }
-  }
-  if (p.render_only != 1) {
-    const int8_t* lab_src = p.p_label + (size_t)en * p.n_tasks * S;
-    if constexpr (OV) { if (ov) lab_src = p.ov_label + (size_t)env * p.n_tasks * S; }
-    for (int i = l; i < p.n_tasks * S; i += SWB_WAVE) tscratch->labels[i] = lab_src[i];
-  }
-  n = rfl(n);
+  if (l < S) rgb_reg = p.p_rgb[(size_t)es.en * S + l];
   if (l >= n) rgb_reg = 0u;
-  if (first && l == 0) { p.episode[env] = ep + 1; p.entry[env] = en; p.nspr[env] = n; p.step_count[env] = 0; p.reset_next[env] = 0; }
 
   // ------------------------------------------------------------------ P1a: centred paths
-  // lane s: vertex count and offset of sprite s; then all vertices of all sprites, 64 per pass
-  // (cross-lane reads with every lane active; shape ids are below SWB_MAX_SHAPES: swb_set_pool / the sampler / the setters check)
-  const int sh_idx = (int)min((uint32_t)shape_l, (uint32_t)(SWB_MAX_SHAPES - 1));
-  const int so_any = __shfl(shoff_tab_l, sh_idx, 64), so_next = __shfl(shoff_tab_l, sh_idx + 1, 64);
-  const double dmin_any = __shfl(shdmin_tab_l, sh_idx, 64);
-  const int so_l = (l < n) ? so_any : 0;
-  const int nv_l = (l < n) ? so_next - so_any : 0;
+  // all vertices of all sprites, 64 per pass (cross-lane reads with every lane active)
+  const double dmin_any = __shfl(shdmin_tab_l, es.sh_idx, 64);
   double dmin_l = (l < n) ? dmin_any : 0.0;              // P1b: can two vertices share a pixel?
-  if constexpr (OV) { if (ov) dmin_l = 0.0; }           // an overridden path is arbitrary: always the general corner scan
+  if constexpr (OV) { if (es.ov) dmin_l = 0.0; }        // an overridden path is arbitrary: always the general corner scan
   int voff_l = nv_l;                                    // inclusive prefix sum over lanes (sprites)
   for (int o = 1; o < SWB_TUNED_SPRITES; o <<= 1) { const int t = __shfl_up(voff_l, o, 64); if (l >= o) voff_l += t; }
   const int vtotal = __builtin_amdgcn_readlane(voff_l, SWB_TUNED_SPRITES - 1);
@@ -1851,13 +2020,13 @@ swb_cover_kernel(const swb_params p) {
     for (int s2 = 1; s2 < n; ++s2) if (k >= __builtin_amdgcn_readlane(voff_l, s2)) sid = s2;
     // cross-lane reads with every lane active (a disabled source lane would read as 0)
     const int i = k - __shfl(voff_l, sid, 64);
-    const int so = __shfl(so_l, sid, 64);
-    const double sc = __shfl(scale_l, sid, 64), ca = __shfl(ca_l, sid, 64), sa = __shfl(sa_l, sid, 64);
+    const int so = __shfl(es.so_l, sid, 64);
+    const double sc = __shfl(scale_l, sid, 64), ca = __shfl(es.ca_l, sid, 64), sa = __shfl(es.sa_l, sid, 64);
     if (k < vtotal) {
       double cx, cy;
       bool from_table = true;
       if constexpr (OV) {
-        if (ov) {                                       // the path the setters left (host arithmetic, swb.hip)
+        if (es.ov) {                                    // the path the setters left (host arithmetic, swb.hip)
           const double* q = p.ov_cpath + (((size_t)env * S + sid) * SWB_MAX_SHAPE_VERTS + i) * 2;
           cx = q[0]; cy = q[1];
           from_table = false;
@@ -1870,131 +2039,16 @@ swb_cover_kernel(const swb_params p) {
   wave_sync();
   SWB_HOOK_PHASE_END(3)
 
-  double cost = 0.0;
-  float cost_f32 = 0.0f;
-  bool cost_is_f32 = false;
-  int step_count = 0;
-  if (!p.render_only && !first) {
-    step_count = sc_old + 1;                            // :93
-    int moved = -1;
-    double m0 = 0.0, m1 = 0.0;
-    if (p.action_space == SWB_ACTION_EMBODIED) {        // action_spaces.py:187-214
-      const int carry = __builtin_amdgcn_readlane(acti, 0), dir = __builtin_amdgcn_readlane(acti, 1);
-      const double st = p.action_scale;
-      if (dir == 0) m1 = st; else if (dir == 1) m0 = -st; else if (dir == 2) m1 = -st; else m0 = st;
-      if (n > 0) {
-        const int body = n - 1;
-        const double bx = readlane_d(px, body), by = readlane_d(py, body);
-        if (carry) {                                     // get_carried_sprite :180-185
-          for (int s2 = body - 1; s2 >= 0; --s2) {
-            const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
-            double tx, ty;
-            if (p.pos_is_f32) { tx = (double)__fsub_rn((float)bx, (float)sx); ty = (double)__fsub_rn((float)by, (float)sy); }
-            else { tx = __dsub_rn(bx, sx); ty = __dsub_rn(by, sy); }
-            if (contains_point_wave(cpath + __builtin_amdgcn_readlane(voff_l, s2), __builtin_amdgcn_readlane(nv_l, s2), tx, ty)) {
-              moved = s2;
-              break;
-            }
-          }
-        }
-        if (l == moved || l == body) {
-          px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
-          py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
-        }
-      }
-      cost = __dmul_rn(-p.motion_cost, st);             // :214
-    } else {                                             // action_spaces.py:83-104
-      const double a0 = readlane_d(act, 0), a1 = readlane_d(act, 1);
-      const double a2 = readlane_d(act, 2), a3 = readlane_d(act, 3);
-      // float32 actions (action_spec() dtype): numpy keeps (a - 0.5) * scale, the motion norm and,
-      // against a float32 position, the click offset in float32 (NEP 50); `act` holds them exactly
-      const bool af = p.action_is_f32 != 0;
-      if (af) {
-        const float f0 = (float)a0, f1 = (float)a1, f2 = (float)a2, f3 = (float)a3, sc = (float)p.action_scale;
-        float m0f, m1f;
-        if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { m0f = __fmul_rn(__fsub_rn(f2, f0), sc); m1f = __fmul_rn(__fsub_rn(f3, f1), sc); }
-        else { m0f = __fmul_rn(__fsub_rn(f2, 0.5f), sc); m1f = __fmul_rn(__fsub_rn(f3, 0.5f), sc); }
-        m0 = (double)m0f; m1 = (double)m1f;
-        cost_f32 = __fmul_rn((float)(-p.motion_cost), sqrtf(__fadd_rn(__fmul_rn(m0f, m0f), __fmul_rn(m1f, m1f))));
-        cost = (double)cost_f32;
-        cost_is_f32 = true;
-      } else if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { // :133-137
-        m0 = __dmul_rn(__dsub_rn(a2, a0), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, a1), p.action_scale);
-      } else {                                           // :65-67
-        m0 = __dmul_rn(__dsub_rn(a2, 0.5), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, 0.5), p.action_scale);
-      }
-      for (int s2 = n - 1; s2 >= 0; --s2) {              // sprites[::-1] :77-81
-        const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
-        double tx, ty;
-        if (af && p.pos_is_f32) { tx = (double)__fsub_rn((float)a0, (float)sx); ty = (double)__fsub_rn((float)a1, (float)sy); }
-        else { tx = __dsub_rn(a0, sx); ty = __dsub_rn(a1, sy); }
-        if (contains_point_wave(cpath + __builtin_amdgcn_readlane(voff_l, s2), __builtin_amdgcn_readlane(nv_l, s2), tx, ty)) {
-          moved = s2;
-          break;
-        }
-      }
-      if (l == moved) {
-        px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
-        py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
-      }
-      if (!af) cost = __dmul_rn(-p.motion_cost, __dsqrt_rn(dot2_hi(m0, m1, m0, m1)));   // :104
-    }
-    if (l < n) {                                         // update_position :98-99
-      px = move1(p.pos_is_f32, px, xv_l, p.keep_in_frame);
-      py = move1(p.pos_is_f32, py, yv_l, p.keep_in_frame);
-      gx[l] = px; gy[l] = py;
-    }
-  }
+  // sprite.py:113-115 contains_point of sprite s2 (wave-uniform): its centred path is in the table P1a built
+  auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
+    return contains_point_wave(cpath + __builtin_amdgcn_readlane(voff_l, s2), __builtin_amdgcn_readlane(nv_l, s2), tx, ty);
+  };
+  const step_cost sc = act_and_move(p, env, es, hit);
+  const double px = es.px, py = es.py;
   SWB_HOOK_PHASE_END(4)
-  // task reward / success (spread over the lanes), out-of-frame, termination
   if (p.render_only != 1) {
-    wave_sync();
-    // tasks.py:134-137, 196-205: `contains(sprite.factors)` is evaluated at every step and x / y are factors -- a task whose
-    // filter keys on position takes every sprite's label from the cell of the task's grid the sprite stands in NOW (lanes =
-    // sprites; swb_task::xcuts / ycuts: the comparisons are numpy's, the bounds already rounded to the position dtype)
-    if (p.p_cell_label != nullptr) {                     // (wave-uniform; no shipped configuration)
-      const int8_t* cells = p.p_cell_label + (size_t)en * p.n_tasks * S * SWB_MAX_CELLS;
-      if constexpr (OV) { if (ov && p.ov_cell_label) cells = p.ov_cell_label + (size_t)env * p.n_tasks * S * SWB_MAX_CELLS; }
-      for (int t = 0; t < p.n_tasks; ++t) {
-        const swb_task& tk = p.tasks[t];
-        if (tk.n_xcuts + tk.n_ycuts == 0) continue;
-        if (l < n) {
-          int cx = 0, cy = 0;
-          for (int k = 0; k < tk.n_xcuts; ++k) cx += (px >= tk.xcuts[k]) ? 1 : 0;
-          for (int k = 0; k < tk.n_ycuts; ++k) cy += (py >= tk.ycuts[k]) ? 1 : 0;
-          tscratch->labels[t * S + l] = cells[((size_t)t * S + l) * SWB_MAX_CELLS + cy * (tk.n_xcuts + 1) + cx];
-        }
-      }
-      wave_sync();
-    }
-    const bool oof_l = (l < n) && !(px >= 0. && py >= 0. && px <= 1. && py <= 1.);   // sprite.py:135-138
-    const int oof = __ballot(oof_l) != 0ull;
-    double tr = 0.0; int ok = 0;
-    const int terr = eval_task_wave(p, n, px, py, tscratch->labels, tscratch, &tr, &ok);
-    if (l == 0) {
-      err |= (uint32_t)terr;
-      if (p.success) p.success[env] = (uint8_t)ok;
-      if (p.render_only) {
-        // (swb_evaluate: environment.py:80-81 success() of the current sprites, no time step)
-      } else if (first) {
-        if (p.reward) p.reward[env] = __longlong_as_double(0x7ff8000000000000ll);
-        if (p.discount) p.discount[env] = __int_as_float(0x7fc00000);
-        if (p.step_type) p.step_type[env] = SWB_STEP_FIRST;
-      } else {
-        // :101 reward += task.reward.  A float32 cost plus a Python-float task reward (NoReward,
-        // Clustering) stays float32 under NEP 50; np.float64 rewards promote to float64.
-        const bool task_is_pyfloat = !p.is_meta && p.tasks[0].kind != SWB_TASK_FIND_GOAL;
-        const double rew = (cost_is_f32 && task_is_pyfloat) ? (double)__fadd_rn(cost_f32, (float)tr) : __dadd_rn(cost, tr);
-        if (p.reward) p.reward[env] = rew;
-        const int timeout = step_count >= p.max_episode_length;            // :84
-        const int last = ok || oof || timeout;                             // :104-106
-        p.step_count[env] = step_count;
-        if (last) p.reset_next[env] = 1;
-        if (p.step_type) p.step_type[env] = last ? SWB_STEP_LAST : SWB_STEP_MID;
-        if (p.discount) p.discount[env] = last ? 0.0f : 1.0f;
-      }
-    }
-    wave_sync();
+    err |= finish_step<OV>(p, env, es, sc, tscratch);
+    wave_sync();                                        // (the scratch aliases the span lists)
   }
   SWB_HOOK_PHASE_END(5)
   if (p.obs == nullptr) {
@@ -2828,10 +2882,10 @@ swb_lf_vertical_kernel(const swb_params p, const swb_lf_args a) {
 
 // --------------------------------------------------------------------------------------------
 // Many-sprite path (handles of more than SWB_TUNED_SPRITES sprites, up to SWB_MAX_SPRITES = one lane per sprite): the
-// state phase of a step -- what the cover kernel's P0 does, with the same arithmetic and the same leaf helpers -- in a kernel
-// of its own, one wave per environment; the frame is then rendered by the large-frame kernels above.
-// Differences to P0: the scan of vertex offsets and the centred paths of the whole scene are not needed (P1 is not run here):
-// a hit test builds the centred path of the one sprite it visits on the fly (lanes = vertices, <= SWB_MAX_SHAPE_VERTS), so
+// state phase of a step -- the three shared pieces the cover kernel's P0 runs (load_env_state, act_and_move, finish_step) -- in a
+// kernel of its own, one wave per environment; the frame is then rendered by the large-frame kernels above.
+// What is its own: the scan of vertex offsets and the centred paths of the whole scene are not needed (P1 is not run here), so
+// a hit test builds the centred path of the one sprite it visits on the fly (lanes = vertices, <= SWB_MAX_SHAPE_VERTS), and
 // the LDS is a wide task_scratch and one path, about 6 KB per wave whatever the scene.
 // --------------------------------------------------------------------------------------------
 struct swb_ms_lds {
@@ -2849,74 +2903,19 @@ swb_ms_state_kernel(const swb_params p) {
   swb_ms_lds* M = reinterpret_cast<swb_ms_lds*>(smem);
   task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
   double2* cpath = M->path;
-  const int S = p.S;
-  double* gx = p.x + (size_t)env * S;
-  double* gy = p.y + (size_t)env * S;
-
-  uint32_t err = 0;
-  const int rn = p.render_only ? 0 : (int)p.reset_next[env];
-  const int ep = p.episode[env], pbase = as_const(p.pool_base)[env], plen = as_const(p.pool_len)[env];
-  const int en_old = p.entry[env], n_old = p.nspr[env], sc_old = p.step_count[env];
-  double px = 0.0, py = 0.0;      // lane s < n holds sprite s's position
-  if (l < S) { px = gx[l]; py = gy[l]; }
-  static_assert(SWB_MAX_SHAPES + 1 <= SWB_WAVE, "one lane per entry of the shape table");
-  const int shoff_tab_l = (l <= SWB_MAX_SHAPES) ? p.shape_off[l] : 0;
-  double act = 0.0;               // lanes 0..3: the action components
-  int acti = 0;
-  if (!p.render_only) {
-    if (p.action_space == SWB_ACTION_EMBODIED) { if (l < 2) acti = reinterpret_cast<const int32_t*>(p.actions)[2 * (size_t)env + l]; }
-    else if (l < 4) {
-      act = p.action_is_f32 ? (double)reinterpret_cast<const float*>(p.actions)[4 * (size_t)env + l]
-                            : reinterpret_cast<const double*>(p.actions)[4 * (size_t)env + l];
-    }
-  }
-  const bool first = rn != 0;                           // environment.py:90-91 -> reset() :74-78
-  bool ov = false;                                      // this episode's sprites carry setter overrides
-  if constexpr (OV) {
-    ov = rfl((int)p.ov_flag[env]) != 0;
-    if (ov && first) {                                  // a reset draws fresh sprites: the overrides end here
-      ov = false;
-      if (l == 0) p.ov_flag[env] = 0;
-    }
-  }
-  const int en = rfl(first ? pbase + (ep % plen) : en_old);
-  const size_t pe = (size_t)en * S;
-  int n = first ? as_const(p.p_n)[en] : n_old;
-  int shape_l = 0;
-  double scale_l = 1.0, ca_l = 1.0, sa_l = 0.0, xv_l = 0.0, yv_l = 0.0;
-  if (l < S) {
-    shape_l = p.p_shape[pe + l]; scale_l = p.p_scale[pe + l]; ca_l = p.p_ca[pe + l]; sa_l = p.p_sa[pe + l];
-    xv_l = p.p_xv[pe + l]; yv_l = p.p_yv[pe + l];
-    if (first) { px = p.p_x[pe + l]; py = p.p_y[pe + l]; gx[l] = px; gy[l] = py; }
-    if constexpr (OV) {
-      if (ov) { shape_l = p.ov_shape[(size_t)env * S + l]; scale_l = p.ov_scale[(size_t)env * S + l]; }
-    }
-  }
-  if (p.render_only != 1) {
-    const int8_t* lab_src = p.p_label + (size_t)en * p.n_tasks * S;
-    if constexpr (OV) { if (ov) lab_src = p.ov_label + (size_t)env * p.n_tasks * S; }
-    for (int i = l; i < p.n_tasks * S; i += SWB_WAVE) tscratch->labels[i] = lab_src[i];
-  }
-  n = rfl(n);
-  if (first && l == 0) { p.episode[env] = ep + 1; p.entry[env] = en; p.nspr[env] = n; p.step_count[env] = 0; p.reset_next[env] = 0; }
-
-  // lane s: vertex count and offset of sprite s in the shape table (cross-lane reads with every lane active)
-  const int sh_idx = (int)min((uint32_t)shape_l, (uint32_t)(SWB_MAX_SHAPES - 1));
-  const int so_any = __shfl(shoff_tab_l, sh_idx, 64), so_next = __shfl(shoff_tab_l, sh_idx + 1, 64);
-  const int so_l = (l < n) ? so_any : 0;
-  const int nv_l = (l < n) ? so_next - so_any : 0;
+  env_state es = load_env_state<OV>(p, env, tscratch);
   // sprite.py:113-115 contains_point of sprite s2 (wave-uniform): its centred path into LDS, lanes = vertices, then the
   // even-odd test of contains_point_wave -- the values P1a of the cover kernel computes for the same sprite
   auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
-    const int nv = __builtin_amdgcn_readlane(nv_l, s2), so = __builtin_amdgcn_readlane(so_l, s2);
-    const double sc = readlane_d(scale_l, s2), ca = readlane_d(ca_l, s2), sa = readlane_d(sa_l, s2);
+    const int nv = __builtin_amdgcn_readlane(es.nv_l, s2), so = __builtin_amdgcn_readlane(es.so_l, s2);
+    const double sc = readlane_d(es.scale_l, s2), ca = readlane_d(es.ca_l, s2), sa = readlane_d(es.sa_l, s2);
     wave_sync();                                        // (the previous sprite's test has read the path)
     if (l < nv) {
       double cx, cy;
       bool from_table = true;
       if constexpr (OV) {
-        if (ov) {                                       // the path the setters left (host arithmetic, swb.hip)
-          const double* q = p.ov_cpath + (((size_t)env * S + s2) * SWB_MAX_SHAPE_VERTS + l) * 2;
+        if (es.ov) {                                    // the path the setters left (host arithmetic, swb.hip)
+          const double* q = p.ov_cpath + (((size_t)env * p.S + s2) * SWB_MAX_SHAPE_VERTS + l) * 2;
           cx = q[0]; cy = q[1];
           from_table = false;
         }
@@ -2927,126 +2926,9 @@ swb_ms_state_kernel(const swb_params p) {
     wave_sync();
     return contains_point_wave(cpath, nv, tx, ty);
   };
-
-  double cost = 0.0;
-  float cost_f32 = 0.0f;
-  bool cost_is_f32 = false;
-  int step_count = 0;
-  if (!p.render_only && !first) {
-    step_count = sc_old + 1;                            // :93
-    int moved = -1;
-    double m0 = 0.0, m1 = 0.0;
-    if (p.action_space == SWB_ACTION_EMBODIED) {        // action_spaces.py:187-214
-      const int carry = __builtin_amdgcn_readlane(acti, 0), dir = __builtin_amdgcn_readlane(acti, 1);
-      const double st = p.action_scale;
-      if (dir == 0) m1 = st; else if (dir == 1) m0 = -st; else if (dir == 2) m1 = -st; else m0 = st;
-      if (n > 0) {
-        const int body = n - 1;
-        const double bx = readlane_d(px, body), by = readlane_d(py, body);
-        if (carry) {                                     // get_carried_sprite :180-185
-          for (int s2 = body - 1; s2 >= 0; --s2) {
-            const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
-            double tx, ty;
-            if (p.pos_is_f32) { tx = (double)__fsub_rn((float)bx, (float)sx); ty = (double)__fsub_rn((float)by, (float)sy); }
-            else { tx = __dsub_rn(bx, sx); ty = __dsub_rn(by, sy); }
-            if (hit(s2, tx, ty)) {
-              moved = s2;
-              break;
-            }
-          }
-        }
-        if (l == moved || l == body) {
-          px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
-          py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
-        }
-      }
-      cost = __dmul_rn(-p.motion_cost, st);             // :214
-    } else {                                             // action_spaces.py:83-104
-      const double a0 = readlane_d(act, 0), a1 = readlane_d(act, 1);
-      const double a2 = readlane_d(act, 2), a3 = readlane_d(act, 3);
-      // float32 actions (action_spec() dtype): as in the cover kernel, numpy's float32 arithmetic (NEP 50)
-      const bool af = p.action_is_f32 != 0;
-      if (af) {
-        const float f0 = (float)a0, f1 = (float)a1, f2 = (float)a2, f3 = (float)a3, sc = (float)p.action_scale;
-        float m0f, m1f;
-        if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { m0f = __fmul_rn(__fsub_rn(f2, f0), sc); m1f = __fmul_rn(__fsub_rn(f3, f1), sc); }
-        else { m0f = __fmul_rn(__fsub_rn(f2, 0.5f), sc); m1f = __fmul_rn(__fsub_rn(f3, 0.5f), sc); }
-        m0 = (double)m0f; m1 = (double)m1f;
-        cost_f32 = __fmul_rn((float)(-p.motion_cost), sqrtf(__fadd_rn(__fmul_rn(m0f, m0f), __fmul_rn(m1f, m1f))));
-        cost = (double)cost_f32;
-        cost_is_f32 = true;
-      } else if (p.action_space == SWB_ACTION_DRAG_AND_DROP) { // :133-137
-        m0 = __dmul_rn(__dsub_rn(a2, a0), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, a1), p.action_scale);
-      } else {                                           // :65-67
-        m0 = __dmul_rn(__dsub_rn(a2, 0.5), p.action_scale); m1 = __dmul_rn(__dsub_rn(a3, 0.5), p.action_scale);
-      }
-      for (int s2 = n - 1; s2 >= 0; --s2) {              // sprites[::-1] :77-81
-        const double sx = readlane_d(px, s2), sy = readlane_d(py, s2);
-        double tx, ty;
-        if (af && p.pos_is_f32) { tx = (double)__fsub_rn((float)a0, (float)sx); ty = (double)__fsub_rn((float)a1, (float)sy); }
-        else { tx = __dsub_rn(a0, sx); ty = __dsub_rn(a1, sy); }
-        if (hit(s2, tx, ty)) {
-          moved = s2;
-          break;
-        }
-      }
-      if (l == moved) {
-        px = move1(p.pos_is_f32, px, m0, p.keep_in_frame);
-        py = move1(p.pos_is_f32, py, m1, p.keep_in_frame);
-      }
-      if (!af) cost = __dmul_rn(-p.motion_cost, __dsqrt_rn(dot2_hi(m0, m1, m0, m1)));   // :104
-    }
-    if (l < n) {                                         // update_position :98-99
-      px = move1(p.pos_is_f32, px, xv_l, p.keep_in_frame);
-      py = move1(p.pos_is_f32, py, yv_l, p.keep_in_frame);
-      gx[l] = px; gy[l] = py;
-    }
-  }
-  // task reward / success (spread over the lanes), out-of-frame, termination
+  const step_cost sc = act_and_move(p, env, es, hit);
   if (p.render_only != 1) {
-    wave_sync();
-    // labels of tasks that key on position: the cell of the task's grid each sprite stands in now (lanes = sprites)
-    if (p.p_cell_label != nullptr) {
-      const int8_t* cells = p.p_cell_label + (size_t)en * p.n_tasks * S * SWB_MAX_CELLS;
-      if constexpr (OV) { if (ov && p.ov_cell_label) cells = p.ov_cell_label + (size_t)env * p.n_tasks * S * SWB_MAX_CELLS; }
-      for (int t = 0; t < p.n_tasks; ++t) {
-        const swb_task& tk = p.tasks[t];
-        if (tk.n_xcuts + tk.n_ycuts == 0) continue;
-        if (l < n) {
-          int cx = 0, cy = 0;
-          for (int k = 0; k < tk.n_xcuts; ++k) cx += (px >= tk.xcuts[k]) ? 1 : 0;
-          for (int k = 0; k < tk.n_ycuts; ++k) cy += (py >= tk.ycuts[k]) ? 1 : 0;
-          tscratch->labels[t * S + l] = cells[((size_t)t * S + l) * SWB_MAX_CELLS + cy * (tk.n_xcuts + 1) + cx];
-        }
-      }
-      wave_sync();
-    }
-    const bool oof_l = (l < n) && !(px >= 0. && py >= 0. && px <= 1. && py <= 1.);   // sprite.py:135-138
-    const int oof = __ballot(oof_l) != 0ull;
-    double tr = 0.0; int ok = 0;
-    const int terr = eval_task_wave(p, n, px, py, tscratch->labels, tscratch, &tr, &ok);
-    if (l == 0) {
-      err |= (uint32_t)terr;
-      if (p.success) p.success[env] = (uint8_t)ok;
-      if (p.render_only) {
-        // (swb_evaluate: environment.py:80-81 success() of the current sprites, no time step)
-      } else if (first) {
-        if (p.reward) p.reward[env] = __longlong_as_double(0x7ff8000000000000ll);
-        if (p.discount) p.discount[env] = __int_as_float(0x7fc00000);
-        if (p.step_type) p.step_type[env] = SWB_STEP_FIRST;
-      } else {
-        // :101 reward += task.reward (a float32 cost plus a Python-float task reward stays float32 under NEP 50)
-        const bool task_is_pyfloat = !p.is_meta && p.tasks[0].kind != SWB_TASK_FIND_GOAL;
-        const double rew = (cost_is_f32 && task_is_pyfloat) ? (double)__fadd_rn(cost_f32, (float)tr) : __dadd_rn(cost, tr);
-        if (p.reward) p.reward[env] = rew;
-        const int timeout = step_count >= p.max_episode_length;            // :84
-        const int last = ok || oof || timeout;                             // :104-106
-        p.step_count[env] = step_count;
-        if (last) p.reset_next[env] = 1;
-        if (p.step_type) p.step_type[env] = last ? SWB_STEP_LAST : SWB_STEP_MID;
-        if (p.discount) p.discount[env] = last ? 0.0f : 1.0f;
-      }
-      if (p.error && err) p.error[env] |= (uint8_t)err;                   // sticky: the caller clears
-    }
+    const uint32_t err = finish_step<OV>(p, env, es, sc, tscratch);
+    if (l == 0 && p.error && err) p.error[env] |= (uint8_t)err;         // sticky: the caller clears
   }
 }

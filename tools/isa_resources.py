@@ -29,6 +29,9 @@ def kernels_of(asm):
       m = re.search(r'swb_resample_kernelILi(\d+)E', name)
       key = 'swb_resample_kernel<%s>' % m.group(1) if m else re.sub(r'^_Z\d+', '', name).split('1')[0] if False else None
       if key is None:
+        m = re.search(r'swb_ms_state_kernelILb([01])E', name)
+        key = 'swb_ms_state_kernel' + ('<OV>' if m.group(1) == '1' else '') if m else None
+      if key is None:
         m = re.search(r'_Z\d+(swb_\w+?_kernel)', name)
         key = m.group(1) if m else name
     f = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))

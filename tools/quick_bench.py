@@ -33,8 +33,8 @@ def run(name, n, aa, bands, steps=40, warmup=10):
   v = eng.variant()
   err = int(eng.error.max().item())
   eng.close()
-  print('%-14s N=%-6d AA=%d bands=%d  step %.4f ms  cover %.4f  %s %.4f   (%.1f M env-steps/s, errors %d)' %
-        (name, n, aa, v['n_bands'], tot / k, a / k, v['kernel'], b / k, n / (tot / k) / 1e3, err), flush=True)
+  print('%-14s N=%-6d AA=%d bands=%d  step %.4f ms  %s %.4f  %s %.4f   (%.1f M env-steps/s, errors %d)' %
+        (name, n, aa, v['n_bands'], tot / k, v['cover_kernel'], a / k, v['kernel'], b / k, n / (tot / k) / 1e3, err), flush=True)
 
 
 if __name__ == '__main__':
