@@ -314,6 +314,33 @@ int swb_render(swb_handle h, uint8_t* obs_dev, void* stream);
  * task (tasks.py:153-158, :239-245, :289-296) in the cover kernel's state phase; no state change, no time step, no frame. */
 int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream);
 
+/* Rollouts: from where every environment is NOW, what would M candidate action sequences of K steps earn?
+ * actions_dev is [K, N, M, 4] f64 (f32 when cfg.action_is_f32) for SelectMove / DragAndDrop, or [K, N, M, 2] i32 for Embodied.
+ * For environment n and candidate m, out->*[k, n, m] holds exactly what swb_step number k + 1 would have written for
+ * environment n had the next K steps been taken with actions[k, n, m]: the same bits of reward (NaN on FIRST), discount, step
+ * type and success, and the same auto-reset -- a candidate that reaches LAST plays FIRST on the next step, from pool entry
+ * pool_base + (episode mod pool_len), as the live environment would (it is not stopped at its first LAST).
+ * The handle is left as it was: positions, step counts, episodes, entries, reset flags, the pool, and the run lists and
+ * dispatch bookkeeping of the render path; nothing is rendered.  N * M virtual environments step on a scratch copy of the
+ * state (N * M * (16 * max_sprites + 32) bytes, owned by the handle, grown on demand); two kernels, asynchronous on `stream`
+ * -- only growing the scratch (or, when K grows, the K per-step parameter blocks of 2 KB kept beside it) blocks.
+ * Limits: M, K >= 1, N * M <= 2^24, K <= 65536; SWB_ERR_INVALID beyond them.
+ * The scratch belongs to the handle: ONE stream at a time per handle.  A rollout must not be issued on another stream while an
+ * earlier rollout of the same handle may still run (order the streams with an event first); calls on one stream need nothing.
+ * SWB_ERR_STATE on a handle on which swb_set_sprite_attr has been called (the override buffers exist): the state phase indexes
+ * overrides by environment, and replicating the 1 KiB centred paths per candidate is out of scope. */
+typedef struct swb_rollout_outputs {   /* device memory, caller-owned; any pointer may be NULL */
+  double* reward;      /* f64[K,N,M]  as swb_outputs::reward                                          */
+  float* discount;     /* f32[K,N,M]                                                                   */
+  uint8_t* step_type;  /* u8 [K,N,M]                                                                   */
+  uint8_t* success;    /* u8 [K,N,M]                                                                   */
+  uint8_t* error;      /* u8 [N,M]    swb_env_error bits of the K steps, ORed INTO the buffer (sticky) */
+  double* x;           /* f64[N,M,S]  positions after step K                                           */
+  double* y;           /* f64[N,M,S]                                                                   */
+  int32_t* n_sprites;  /* i32[N,M]    sprites of the episode the candidate ends in                     */
+} swb_rollout_outputs;
+int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream);
+
 /* Memory of the hand-off lists (what the cover kernel hands the resample / fill kernel: swb_variant_info::run_list_bytes).
  * A handle starts with a list of max(4, max_sprites + 1) units of 8 bytes per canvas row for every environment and group of 64
  * output columns -- enough for ANY scene of convex sprites, about ten times what the usual scene needs (133 KB per environment

@@ -102,6 +102,19 @@ class SwbOutputs(C.Structure):
   ]
 
 
+class SwbRolloutOutputs(C.Structure):
+  _fields_ = [
+      ('reward', C.c_void_p),
+      ('discount', C.c_void_p),
+      ('step_type', C.c_void_p),
+      ('success', C.c_void_p),
+      ('error', C.c_void_p),
+      ('x', C.c_void_p),
+      ('y', C.c_void_p),
+      ('n_sprites', C.c_void_p),
+  ]
+
+
 class SwbState(C.Structure):
   _fields_ = [
       ('x', C.c_void_p),

@@ -19,7 +19,7 @@ EXPORTS = (
     'swb_upload_resample', 'swb_set_pool', 'swb_sample_pool', 'swb_resample_pool', 'swb_get_pool', 'swb_reset_all', 'swb_step', 'swb_render', 'swb_evaluate', 'swb_factors',
     'swb_get_state', 'swb_set_positions', 'swb_variant', 'swb_build_id', 'swb_timing_enable', 'swb_step_time_ms',
     'swb_set_sprite_attr', 'swb_get_sprite', 'swb_sprite_path_op', 'swb_kernel_times_ms', 'swb_get_env_state',
-    'swb_get_sprite_types', 'swb_trim_run_lists', 'swb_set_sprite_cell_labels',
+    'swb_get_sprite_types', 'swb_trim_run_lists', 'swb_set_sprite_cell_labels', 'swb_rollout',
 )
 
 _lib = None
@@ -60,6 +60,8 @@ def load():
   if hasattr(lib, 'swb_evaluate') or not os.environ.get('SWB_LIBRARY'):     # (A/B builds of older revisions lack it)
     lib.swb_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
   lib.swb_factors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+  if hasattr(lib, 'swb_rollout') or not os.environ.get('SWB_LIBRARY'):
+    lib.swb_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_abi.SwbRolloutOutputs), C.c_void_p]
   if hasattr(lib, 'swb_trim_run_lists') or not os.environ.get('SWB_LIBRARY'):
     lib.swb_trim_run_lists.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
   if hasattr(lib, 'swb_set_sprite_cell_labels') or not os.environ.get('SWB_LIBRARY'):

@@ -136,6 +136,11 @@ struct swb_engine {
   size_t lf_tmp_bytes = 0;
   double timed_ms = 0.0, timed_cover_ms = 0.0;
   int64_t timed_launches = 0;
+  // swb_rollout: the scratch state of the virtual environments (one allocation, grown on demand)
+  unsigned char* d_rollout = nullptr;
+  size_t rollout_bytes = 0;
+  swb_params* d_rollout_steps = nullptr;   // ... and the K per-step copies of swb_params swb_rollout_fork_kernel writes
+  int rollout_steps = 0;
 };
 
 namespace {
@@ -802,7 +807,7 @@ int swb_destroy(swb_handle h) {
                   h->d_entry, h->d_step_count, h->d_episode, h->d_reset_next, h->d_ovf, h->d_ovf_bitmap, h->d_p_angle, h->d_p_color, h->d_sampler,
                   h->d_ov_flag, h->d_ov_shape, h->d_ov_scale, h->d_ov_angle, h->d_ov_cpath, h->d_ov_label,
                   h->d_cost_cnt, h->d_cost_list, h->d_ccost_list, h->d_runs, h->d_rhdr, h->d_arena_head, h->d_env_state, h->d_band_y0, h->d_band_first, h->d_band_lo, h->d_cg_lo, h->d_cg_hi, h->d_v_break,
-                  h->d_lf_hb, h->d_lf_hpo, h->d_lf_hp, h->d_lf_vb, h->d_lf_vk, h->d_lf_tmp};
+                  h->d_lf_hb, h->d_lf_hpo, h->d_lf_hp, h->d_lf_vb, h->d_lf_vk, h->d_lf_tmp, h->d_rollout, h->d_rollout_steps};
   for (void* b : bufs) if (b) (void)hipFree(b);
   delete h;
   return SWB_OK;
@@ -1198,6 +1203,63 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream) {
   memset(&out, 0, sizeof(out));
   out.success = success_dev;
   return launch(h, nullptr, &out, 2, (hipStream_t)stream);
+}
+
+// Rollouts (include/swb.h): swb_rollout_fork_kernel copies the live state into the scratch of N * M virtual environments,
+// swb_rollout_kernel steps them K times.  Neither touches the live state, the run lists or the dispatch bookkeeping of launch().
+#define SWB_ROLLOUT_MAX_VENVS (1 << 24)      // N * M: one workgroup each, and N * M * S fits an int
+#define SWB_ROLLOUT_MAX_STEPS (1 << 16)      // K: one copy of swb_params each
+int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "swb_rollout: M and K must be positive (M = %d, K = %d)", M, K);
+  if (!actions_dev) return fail(SWB_ERR_INVALID, "swb_rollout: actions is NULL");
+  const swb_params& p = h->p;
+  if ((long long)p.N * M > SWB_ROLLOUT_MAX_VENVS)
+    return fail(SWB_ERR_INVALID, "swb_rollout: %d environments x %d candidates exceed the grid limit of %d virtual environments", p.N, M,
+                SWB_ROLLOUT_MAX_VENVS);
+  if (K > SWB_ROLLOUT_MAX_STEPS) return fail(SWB_ERR_INVALID, "swb_rollout: K = %d exceeds the limit of %d steps", K, SWB_ROLLOUT_MAX_STEPS);
+  if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
+  if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
+  if (h->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_rollout: sprite setters have been called on this handle; rollouts under live overrides are not supported");
+  HIP_TRY(hipSetDevice(h->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t NV = (size_t)p.N * M, S = (size_t)p.S;
+  const size_t bytes = NV * (16 * S + 32);
+  if (bytes > h->rollout_bytes || K > h->rollout_steps) {   // (the one blocking case: an earlier rollout may still use the old scratch)
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bytes > h->rollout_bytes) {
+      if (h->d_rollout) { (void)hipFree(h->d_rollout); h->d_rollout = nullptr; h->rollout_bytes = 0; }
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rollout), bytes));
+      h->rollout_bytes = bytes;
+    }
+    if (K > h->rollout_steps) {
+      if (h->d_rollout_steps) { (void)hipFree(h->d_rollout_steps); h->d_rollout_steps = nullptr; h->rollout_steps = 0; }
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rollout_steps), (size_t)K * sizeof(swb_params)));
+      h->rollout_steps = K;
+    }
+  }
+  swb_rollout_args a;
+  memset(&a, 0, sizeof(a));
+  a.M = M; a.K = K;
+  a.x = reinterpret_cast<double*>(h->d_rollout);
+  a.y = a.x + NV * S;
+  a.nspr = reinterpret_cast<int32_t*>(a.y + NV * S);
+  a.entry = a.nspr + NV; a.step_count = a.entry + NV; a.episode = a.step_count + NV;
+  a.pool_base = a.episode + NV; a.pool_len = a.pool_base + NV;
+  a.reset_next = reinterpret_cast<uint8_t*>(a.pool_len + NV);      // (NV bytes of the last 8 NV)
+  a.steps = h->d_rollout_steps;
+  a.actions = actions_dev;
+  if (out) {
+    a.reward = out->reward; a.discount = out->discount; a.step_type = out->step_type; a.success = out->success;
+    a.error = out->error; a.out_x = out->x; a.out_y = out->y; a.out_n = out->n_sprites;
+  }
+  const size_t threads = std::max(NV * S, (size_t)K);
+  hipLaunchKernelGGL(swb_rollout_fork_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(swb_rollout_kernel, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
 }
 
 int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream) {

@@ -2932,3 +2932,116 @@ swb_ms_state_kernel(const swb_params p) {
     if (l == 0 && p.error && err) p.error[env] |= (uint8_t)err;         // sticky: the caller clears
   }
 }
+
+// --------------------------------------------------------------------------------------------
+// Rollouts (swb_rollout): what would M candidate action sequences of K steps earn from where every environment is NOW?
+// N * M virtual environments (v = n * M + m) step K times on a private copy of the state; the live state is only read.
+//   swb_rollout_fork_kernel  copies the live per-environment state into the scratch arrays of the virtual environments,
+//                            replicates pool_base / pool_len (one thread per (v, sprite)), and writes the K copies of
+//                            swb_params the steps run with: state pointers = the scratch, actions = step k's block, outputs =
+//                            step k's [N * M] slice, no frame, no overrides.
+//   swb_rollout_kernel       one wave per virtual environment, built like swb_ms_state_kernel (the wide task scratch and one
+//                            centred path in LDS, whatever the handle: tuned and many-sprite handles alike).  It runs the three
+//                            shared pieces of the state phase K times, iteration k with copy k -- so a candidate auto-resets
+//                            from pool_base + (episode mod pool_len) exactly as the live environment would.
+// Why the copies are made by the fork launch and not in the wave: the pieces index swb_params::tasks with a loop variable, and a
+// copy on the wave's stack that is indexed so stays in scratch memory (measured: 1936 bytes per lane).  Written by an earlier
+// launch, copy k is read the way kernel arguments are -- constant address space, scalar loads.
+// Between two iterations the wave re-reads what its own lanes stored (lane 0: step_count, reset_next, entry, nspr, episode;
+// lanes < S: positions): wave_sync() orders them, and all of those words are read with plain global loads (THE RULE above:
+// nothing written in this launch goes through as_const; pool_base / pool_len and the copies do, the fork launch wrote them).
+// --------------------------------------------------------------------------------------------
+#ifndef SWB_WIDE_TU
+struct swb_rollout_args {
+  int32_t M, K;
+  // ---- scratch: the state of the N * M virtual environments
+  double *x, *y;                 // [N * M][S]
+  int32_t *nspr, *entry, *step_count, *episode, *pool_base, *pool_len;   // [N * M]
+  uint8_t* reset_next;           // [N * M]
+  swb_params* steps;             // [K] the virtual environments' view of the engine at step k
+  // ---- io of the call (swb_rollout_outputs; any output may be NULL)
+  const void* actions;           // [K][N * M][4] f64 / f32, or [K][N * M][2] i32
+  double* reward;                // [K][N * M]
+  float* discount;
+  uint8_t *step_type, *success;
+  uint8_t* error;                // [N * M] sticky
+  double *out_x, *out_y;         // [N * M][S]
+  int32_t* out_n;                // [N * M]
+};
+static_assert(sizeof(swb_params) + sizeof(swb_rollout_args) <= 4096, "kernel arguments of the rollout kernels");
+
+__global__ void __launch_bounds__(256)
+swb_rollout_fork_kernel(const swb_params p, const swb_rollout_args a) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);         // (N * M * S < 2^31: swb_rollout checks)
+  if (idx < a.K) {
+    const size_t o = (size_t)idx * p.N * a.M;
+    const size_t action_bytes = p.action_space == SWB_ACTION_EMBODIED ? 2 * sizeof(int32_t) : (p.action_is_f32 ? 4 * sizeof(float) : 4 * sizeof(double));
+    swb_params q = p;
+    q.x = a.x; q.y = a.y; q.nspr = a.nspr; q.entry = a.entry; q.step_count = a.step_count; q.episode = a.episode;
+    q.reset_next = a.reset_next; q.pool_base = a.pool_base; q.pool_len = a.pool_len;
+    q.obs = nullptr; q.error = nullptr; q.render_only = 0;
+    q.actions = reinterpret_cast<const unsigned char*>(a.actions) + o * action_bytes;
+    q.reward = a.reward ? a.reward + o : nullptr;
+    q.discount = a.discount ? a.discount + o : nullptr;
+    q.step_type = a.step_type ? a.step_type + o : nullptr;
+    q.success = a.success ? a.success + o : nullptr;
+    a.steps[idx] = q;
+  }
+  if (idx >= p.N * a.M * p.S) return;
+  const int v = idx / p.S, s = idx - v * p.S, n = v / a.M;
+  a.x[idx] = p.x[(size_t)n * p.S + s];
+  a.y[idx] = p.y[(size_t)n * p.S + s];
+  if (s == 0) {
+    a.nspr[v] = p.nspr[n]; a.entry[v] = p.entry[n]; a.step_count[v] = p.step_count[n]; a.episode[v] = p.episode[n];
+    a.reset_next[v] = p.reset_next[n];
+    a.pool_base[v] = p.pool_base[n]; a.pool_len[v] = p.pool_len[n];
+  }
+}
+
+// Register budget: the state phase is latency-bound (dependent loads, LDS round trips), so more resident waves win although the
+// kernel then spills: measured at N = 1024, M = 64, K = 16 (goal_s5 / embodied_s12), 4 waves per SIMD (105 VGPRs, no spills)
+// 1.430 / 1.338 ms, 5 waves (94 VGPRs, 2 spilled) 1.259 / 1.179 ms, 6 waves (80 VGPRs, 16 spilled) 1.194 / 1.121 ms.
+// (profiles/r09_rollouts.md, section 2)
+#ifndef SWB_ROLLOUT_WAVES_PER_SIMD
+#define SWB_ROLLOUT_WAVES_PER_SIMD 6
+#endif
+__global__ void __launch_bounds__(SWB_WAVE, SWB_ROLLOUT_WAVES_PER_SIMD)
+swb_rollout_kernel(const swb_rollout_args a, int S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int l = lane_id();
+  const int v = blockIdx.x;
+  swb_ms_lds* M = reinterpret_cast<swb_ms_lds*>(smem);
+  task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
+  double2* cpath = M->path;
+  uint32_t err = 0;
+  for (int k = 0; k < a.K; ++k) {
+    const swb_params& q = *(const swb_params*)as_const(a.steps + k);
+    env_state es = load_env_state<false>(q, v, tscratch);
+    // sprite.py:113-115 contains_point of sprite s2 (wave-uniform), as in swb_ms_state_kernel: its centred path into LDS,
+    // lanes = vertices, then the even-odd test
+    auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
+      const int nv = __builtin_amdgcn_readlane(es.nv_l, s2), so = __builtin_amdgcn_readlane(es.so_l, s2);
+      const double sc = readlane_d(es.scale_l, s2), ca = readlane_d(es.ca_l, s2), sa = readlane_d(es.sa_l, s2);
+      wave_sync();                                      // (the previous sprite's test has read the path)
+      if (l < nv) {
+        double cx, cy;
+        centered_vertex(q, so, l, sc, ca, sa, cx, cy);
+        cpath[l] = make_double2(cx, cy);
+      }
+      wave_sync();
+      return contains_point_wave(cpath, nv, tx, ty);
+    };
+    const step_cost sc = act_and_move(q, v, es, hit);
+    err |= finish_step<false>(q, v, es, sc, tscratch);
+    wave_sync();                                        // the next iteration reads what this one stored (state words, LDS scratch)
+  }
+  if (l < S) {
+    if (a.out_x) a.out_x[(size_t)v * S + l] = a.x[(size_t)v * S + l];
+    if (a.out_y) a.out_y[(size_t)v * S + l] = a.y[(size_t)v * S + l];
+  }
+  if (l == 0) {
+    if (a.out_n) a.out_n[v] = a.nspr[v];
+    if (a.error && err) a.error[v] |= (uint8_t)err;     // sticky: the caller clears
+  }
+}
+#endif  // SWB_WIDE_TU

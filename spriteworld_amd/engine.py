@@ -141,6 +141,40 @@ class Engine(object):
       if self._rendered == self.TRIM_AFTER:
         self.trim()
 
+  def rollout(self, actions, positions=False):
+    """Scores M candidate action sequences of K steps per environment from the CURRENT state without stepping it
+    (swb_rollout: two kernels, asynchronous, the live state untouched).  actions: [K, N, M, 4] float (f32 if
+    cfg.action_is_f32) or [K, N, M, 2] int32 (Embodied).  Returns a dict of fresh device tensors in the C layout: reward
+    f64, discount f32, step_type u8, success u8 -- all [K, N, M], entry [k, n, m] what step k + 1 of environment n would
+    return under actions[k, n, m] -- and error u8[N, M] (swb_env_error bits of the K steps); with `positions`, also x, y
+    f64[N, M, S] and n_sprites i32[N, M] after step K.  The scratch state belongs to the handle: issue the rollouts of one
+    engine on one stream (or order the streams yourself)."""
+    if self.cfg.action_space == _abi.ACTION_EMBODIED:
+      want, width = torch.int32, 2
+    else:
+      want, width = (torch.float32 if self.cfg.action_is_f32 else torch.float64), 4
+    if not isinstance(actions, torch.Tensor):
+      actions = torch.as_tensor(np.ascontiguousarray(actions), device=self.device)
+    if actions.dim() != 4 or actions.shape[1] != self.N or actions.shape[3] != width:
+      raise ValueError('rollout actions must be [K, %d, M, %d], got %s' % (self.N, width, tuple(actions.shape)))
+    if actions.dtype != want or actions.device != self.device or not actions.is_contiguous():
+      actions = actions.to(device=self.device, dtype=want).contiguous()
+    K, _, M, _ = actions.shape
+    with torch.cuda.device(self.device):
+      new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+      res = {'reward': new((K, self.N, M), torch.float64), 'discount': new((K, self.N, M), torch.float32),
+             'step_type': new((K, self.N, M), torch.uint8), 'success': new((K, self.N, M), torch.uint8),
+             'error': torch.zeros((self.N, M), dtype=torch.uint8, device=self.device)}
+      if positions:
+        res.update(x=new((self.N, M, self.S), torch.float64), y=new((self.N, M, self.S), torch.float64),
+                   n_sprites=new((self.N, M), torch.int32))
+    o = _abi.SwbRolloutOutputs()
+    for k, t in res.items():
+      setattr(o, k, t.data_ptr())
+    self._last_rollout_actions = actions  # keep alive until the launch is consumed
+    _lib.check(self.lib.swb_rollout(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), self._stream()))
+    return res
+
   def trim(self):
     """Cuts the hand-off lists between the two kernels of a step from their start-up reservation (any scene of convex sprites:
     133 KB per environment on 12 sprites at 128x128) down to 1.25 x what the launches so far needed, plus a shared arena for the

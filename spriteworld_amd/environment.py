@@ -49,6 +49,21 @@ BatchedTimeStep = collections.namedtuple('BatchedTimeStep',
                                          ['step_type', 'reward', 'discount', 'observation'])
 
 
+class Rollout(collections.namedtuple('Rollout', ['step_type', 'reward', 'discount', 'success', 'x', 'y', 'n_sprites', 'error'])):
+  """What `BatchedEnvironment.rollout` returns, device tensors: step_type u8, reward f64 (NaN on FIRST steps), discount f32,
+  success u8 -- [N, M, K] views, entry [n, m, k] what step k + 1 of environment n would return under candidate m -- then
+  x, y f64[N, M, S] and n_sprites i32[N, M] after step K, and error u8[N, M] (swb_env_error bits of the K steps)."""
+  __slots__ = ()
+
+  def episode_return(self):
+    """f64[N, M]: the sum of rewards from step 0 through the candidate's first LAST step (all K steps when it never ends);
+    the NaN of FIRST steps is left out.  Torch operations on the device, no synchronisation."""
+    last = (self.step_type == _abi.STEP_LAST).to(torch.int32)
+    ended_before = torch.cumsum(last, dim=2) - last          # LAST steps strictly before step k
+    keep = (ended_before == 0) & (self.step_type != _abi.STEP_FIRST)
+    return torch.where(keep, self.reward, torch.zeros_like(self.reward)).sum(dim=2)
+
+
 class EnvironmentError_(RuntimeError):
   pass
 
@@ -264,6 +279,24 @@ class BatchedEnvironment(object):
         self._steps_since_refresh = 0
         self.refresh_pool()
     return self._timestep()
+
+  def rollout(self, actions):
+    """Scores candidate action sequences from where every environment is now, without stepping: actions is [N, M, K, A]
+    (tensor or array; A = 4, or 2 for Embodied) -- M candidates of K steps per environment.  Returns a `Rollout` whose
+    [n, m, k] entries are exactly what step k + 1 of environment n would return had the next K steps been actions[n, m, :]
+    (auto-resets included: a candidate that ends plays FIRST on its next step; `Rollout.episode_return()` sums up to the
+    first LAST).  One permute to the engine's [K, N, M, A] layout, two kernels (swb_rollout), no host synchronisation; the
+    live environments, their error flags and the pool are untouched.
+    A rollout is of the NOISELESS dynamics: a SelectMove `noise_scale` is not applied to the candidates (`step()` draws its
+    noise per call; the candidates are scored as given)."""
+    e = self._engine
+    if not isinstance(actions, torch.Tensor):
+      actions = torch.as_tensor(np.ascontiguousarray(actions))
+    if actions.dim() != 4 or actions.shape[0] != self._num_envs:
+      raise ValueError('rollout actions must be [N, M, K, A] with N = %d, got %s' % (self._num_envs, tuple(actions.shape)))
+    res = e.rollout(actions.to(device=e.device).permute(2, 0, 1, 3), positions=True)
+    per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
+    return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']]))
 
   def observation(self):
     """environment.py:136-142: every renderer's view of the sprites AS THEY ARE NOW -- the frame is rendered now (swb_render)
