@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -43,15 +44,32 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(SWB_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
+// A device allocation and its owner: freed with the handle that holds it, used wherever a T* is.  It never synchronises: whoever
+// re-makes a buffer that work in flight may still use waits for that work first, at the call site.
 template <typename T>
-int upload(T** dst, const T* src, size_t count) {
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  if (count == 0) count = 1;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), count * sizeof(T)));
-  if (src) HIP_TRY(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(*dst, 0, count * sizeof(T)));
-  return 0;
-}
+struct dev_buf {
+  T* ptr = nullptr;
+  size_t count = 0;                  // elements allocated
+  dev_buf() = default;
+  dev_buf(const dev_buf&) = delete;
+  dev_buf& operator=(const dev_buf&) = delete;
+  ~dev_buf() { release(); }
+  operator T*() const { return ptr; }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr; count = 0;
+  }
+  // a new allocation of n elements (none: one) holding src[0 .. n), or zeros when src is NULL
+  int fill(const T* src, size_t n) {
+    release();
+    if (n == 0) n = 1;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
+    count = n;
+    if (src) HIP_TRY(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemset(ptr, 0, n * sizeof(T)));
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -68,53 +86,51 @@ struct swb_engine {
   int ovf_lds_bytes = 0;             // LDS footprint the overflow slots were sized with
   void (*ovf_fn)(const swb_params) = nullptr;   // ... and the cover kernel (plain or override build)
   size_t lds_block = 0;
-  // owned device buffers
-  double* d_shape_verts = nullptr;
-  double* d_shape_dmin = nullptr;
-  int32_t* d_shape_off = nullptr;
-  int32_t *d_h_xmin = nullptr, *d_h_cnt = nullptr, *d_h_tbl = nullptr, *d_h_pfx = nullptr;
-  int32_t *d_v_tab = nullptr, *d_v_end = nullptr, *d_v_pfx = nullptr;
-  int32_t* d_p_n = nullptr;
-  double *d_p_x = nullptr, *d_p_y = nullptr, *d_p_xv = nullptr, *d_p_yv = nullptr, *d_p_scale = nullptr,
-         *d_p_ca = nullptr, *d_p_sa = nullptr;
-  int32_t* d_p_shape = nullptr;
-  uint32_t* d_p_rgb = nullptr;
-  int8_t* d_p_label = nullptr;
-  int8_t* d_p_cell_label = nullptr;  // swb_pool::cell_label (tasks that key on position)
+  // owned device buffers (dev_buf: freed with the handle)
+  dev_buf<double> d_shape_verts, d_shape_dmin;
+  dev_buf<int32_t> d_shape_off;
+  dev_buf<int32_t> d_h_xmin, d_h_cnt, d_h_tbl, d_h_pfx;
+  dev_buf<int32_t> d_v_tab, d_v_end, d_v_pfx;
+  dev_buf<int32_t> d_p_n;
+  dev_buf<double> d_p_x, d_p_y, d_p_xv, d_p_yv, d_p_scale, d_p_ca, d_p_sa;
+  dev_buf<int32_t> d_p_shape;
+  dev_buf<uint32_t> d_p_rgb;
+  dev_buf<int8_t> d_p_label;
+  dev_buf<int8_t> d_p_cell_label;    // swb_pool::cell_label (tasks that key on position)
   bool keyed = false;                // some task's filter keys on position (swb_task::n_xcuts / n_ycuts)
-  uint8_t* d_p_attr = nullptr;       // swb_pool::attr_f32
-  int32_t *d_pool_base = nullptr, *d_pool_len = nullptr;
-  double *d_p_angle = nullptr, *d_p_color = nullptr;
-  swb_sampler* d_sampler = nullptr;
+  dev_buf<uint8_t> d_p_attr;         // swb_pool::attr_f32
+  dev_buf<int32_t> d_pool_base, d_pool_len;
+  dev_buf<double> d_p_angle, d_p_color;
+  dev_buf<swb_sampler> d_sampler;
   int pool_entries = 0;
   bool pool_sampled = false, pool_uniform = false;   // pool came from swb_sample_pool / env-major fixed-length layout
-  double *d_x = nullptr, *d_y = nullptr;
-  int32_t *d_nspr = nullptr, *d_entry = nullptr, *d_step_count = nullptr, *d_episode = nullptr;
-  uint8_t* d_reset_next = nullptr;
-  uint32_t *d_ovf = nullptr, *d_ovf_bitmap = nullptr;
+  dev_buf<double> d_x, d_y;
+  dev_buf<int32_t> d_nspr, d_entry, d_step_count, d_episode;
+  dev_buf<uint8_t> d_reset_next;
+  dev_buf<uint32_t> d_ovf, d_ovf_bitmap;
   int ovf_slots = 0;
   // cost-ordered dispatch (swb_params::cost_cnt)
-  uint32_t* d_cost_cnt = nullptr;
-  int32_t* d_cost_list = nullptr;
-  int32_t* d_ccost_list = nullptr;   // ... and the environments in order of the cover kernel's cost (swb_params::cover_order)
+  dev_buf<uint32_t> d_cost_cnt;
+  dev_buf<int32_t> d_cost_list;
+  dev_buf<int32_t> d_ccost_list;     // ... and the environments in order of the cover kernel's cost (swb_params::cover_order)
   bool cover_lists_filed = false;    // the previous launch filed every environment (it rendered)
   int launch_phase = 0;              // launch count % 3 (swb_params::cphase)
   int launch_parity = 0;
   // hand-off cover -> resample
-  uint32_t *d_runs = nullptr, *d_rhdr = nullptr, *d_arena_head = nullptr;
-  int32_t* d_env_state = nullptr;    // swb_get_env_state's 20-byte record
+  dev_buf<uint32_t> d_runs, d_rhdr, d_arena_head;
+  dev_buf<int32_t> d_env_state;      // swb_get_env_state's 20-byte record
   int arena_override = -1;           // SWB_ARENA_UNITS (tests): units of the shared arena; -1: sized from the batch
   int run_cap_worst = 0;             // (max(4, S + 1) canvas heights + 1: what a list reserves until swb_trim_run_lists)
   bool lists_trimmed = false;        // the lists have been cut down to what the launches so far needed
   bool lists_valid = false;          // the last launch wrote them (it rendered through the second kernel)
-  int32_t *d_band_y0 = nullptr, *d_band_first = nullptr, *d_band_lo = nullptr, *d_cg_lo = nullptr, *d_cg_hi = nullptr;
-  uint32_t* d_v_break = nullptr;
+  dev_buf<int32_t> d_band_y0, d_band_first, d_band_lo, d_cg_lo, d_cg_hi;
+  dev_buf<uint32_t> d_v_break;
   // live sprite overrides (swb_set_sprite_attr), allocated at the first call
-  uint8_t* d_ov_flag = nullptr;
-  int32_t* d_ov_shape = nullptr;
-  double *d_ov_scale = nullptr, *d_ov_angle = nullptr, *d_ov_cpath = nullptr;
-  int8_t* d_ov_label = nullptr;
-  int8_t* d_ov_cell_label = nullptr;
+  dev_buf<uint8_t> d_ov_flag;
+  dev_buf<int32_t> d_ov_shape;
+  dev_buf<double> d_ov_scale, d_ov_angle, d_ov_cpath;
+  dev_buf<int8_t> d_ov_label;
+  dev_buf<int8_t> d_ov_cell_label;
   // timing
   bool timing = false;
   struct step_events { hipEvent_t e0, e1, e2; };     // before cover, between the kernels, after resample / fill
@@ -130,17 +146,14 @@ struct swb_engine {
   // large-frame render kernels (large_frames is set too)
   bool many_sprites = false;
   size_t lf_scratch_budget = (size_t)256 << 20;   // bytes of horizontal-pass scratch: the batch is rendered in chunks that fit
-  int32_t *d_lf_hb = nullptr, *d_lf_hpo = nullptr, *d_lf_hp = nullptr, *d_lf_vb = nullptr, *d_lf_vk = nullptr;
+  dev_buf<int32_t> d_lf_hb, d_lf_hpo, d_lf_hp, d_lf_vb, d_lf_vk;
   int lf_vks = 0;
-  uint8_t* d_lf_tmp = nullptr;
-  size_t lf_tmp_bytes = 0;
+  dev_buf<uint8_t> d_lf_tmp;                      // ... that scratch (grown on demand)
   double timed_ms = 0.0, timed_cover_ms = 0.0;
   int64_t timed_launches = 0;
   // swb_rollout: the scratch state of the virtual environments (one allocation, grown on demand)
-  unsigned char* d_rollout = nullptr;
-  size_t rollout_bytes = 0;
-  swb_params* d_rollout_steps = nullptr;   // ... and the K per-step copies of swb_params swb_rollout_fork_kernel writes
-  int rollout_steps = 0;
+  dev_buf<unsigned char> d_rollout;
+  dev_buf<swb_params> d_rollout_steps;     // ... and the K per-step copies of swb_params swb_rollout_fork_kernel writes
 };
 
 namespace {
@@ -191,7 +204,7 @@ size_t lds_per_wave(const swb_engine* h, const variant* v, int* cpath_in_masks) 
 // launch with / without an observation buffer switches to: the slots are sized once for the more demanding of the two)
 int ensure_overflow_slots(swb_engine* h, kernel_fn fn, kernel_fn fn_alt, size_t lds_bytes) {
   if (h->d_ovf) return 0;
-  int per_cu = 0, cus = 0;
+  int per_cu = 0;
   for (kernel_fn f : {fn, fn_alt}) {
     int n = 0;
     if (!f) continue;
@@ -199,13 +212,11 @@ int ensure_overflow_slots(swb_engine* h, kernel_fn fn, kernel_fn fn_alt, size_t 
       n = 32;
     per_cu = std::max(per_cu, n);
   }
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-  long long slots = (long long)per_cu * cus;
+  long long slots = (long long)per_cu * h->cus;
   slots = std::min<long long>(2 * slots, (long long)h->p.N);              // the bitmap stays at most half full: few retries
   slots = (slots + 31) / 32 * 32;
   h->ovf_slots = (int)slots;
-  if (upload(&h->d_ovf, (const uint32_t*)nullptr, (size_t)slots * 64 * h->p.ovf_cap)) return SWB_ERR_HIP;
-  if (upload(&h->d_ovf_bitmap, (const uint32_t*)nullptr, (size_t)slots / 32)) return SWB_ERR_HIP;
+  if (h->d_ovf.fill(nullptr, (size_t)slots * 64 * h->p.ovf_cap) || h->d_ovf_bitmap.fill(nullptr, (size_t)slots / 32)) return SWB_ERR_HIP;
   h->p.ovf = h->d_ovf; h->p.ovf_bitmap = h->d_ovf_bitmap; h->p.ovf_slots = h->ovf_slots;
   return 0;
 }
@@ -218,7 +229,6 @@ int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
   if (!h->tables_dirty && (h->d_runs || !need_lists)) return 0;
   swb_params& p = h->p;
   int nb = h->nbands;
-  p.ncg = (p.Wo + 63) / 64;
   // Bands: about Ho / nb rows each; for the resample kernel the first row of a band is moved so that the number of
   // output rows in flight at its first canvas row is a multiple of VS (the band's oldest row then sits in slot 0).
   int vs = 0;
@@ -264,10 +274,9 @@ int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
       hi[g] = std::max(hi[g], h->h_xmin_host[o] + h->h_cnt_host[o]);
     }
   }
-  if (upload(&h->d_band_y0, y0.data(), y0.size()) || upload(&h->d_band_first, first.data(), first.size()) ||
-      upload(&h->d_band_lo, blo.data(), blo.size()) ||
-      upload(&h->d_v_break, brk.data(), brk.size()) || upload(&h->d_cg_lo, lo.data(), lo.size()) ||
-      upload(&h->d_cg_hi, hi.data(), hi.size()))
+  if (h->d_band_y0.fill(y0.data(), y0.size()) || h->d_band_first.fill(first.data(), first.size()) ||
+      h->d_band_lo.fill(blo.data(), blo.size()) || h->d_v_break.fill(brk.data(), brk.size()) ||
+      h->d_cg_lo.fill(lo.data(), lo.size()) || h->d_cg_hi.fill(hi.data(), hi.size()))
     return SWB_ERR_HIP;
   p.band_lo = h->d_band_lo;
   p.band_y0 = h->d_band_y0; p.band_first = h->d_band_first; p.v_break = h->d_v_break; p.cg_lo = h->d_cg_lo; p.cg_hi = h->d_cg_hi;
@@ -288,9 +297,8 @@ int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && units * 8 + (size_t)p.N * SWB_RHDR_DWORDS * 4 > free_b)
       return fail(SWB_ERR_HIP, "run lists need %zu MB of device memory (%d environments x %d column groups x %d units of 8 bytes + an "
                   "arena of %zu units), %zu MB are free", units * 8 >> 20, p.N, p.ncg, p.run_cap, arena, free_b >> 20);
-    if (upload(&h->d_runs, (const uint32_t*)nullptr, units * 2)) return SWB_ERR_HIP;
-    if (upload(&h->d_rhdr, (const uint32_t*)nullptr, (size_t)p.N * SWB_RHDR_DWORDS)) return SWB_ERR_HIP;
-    if (upload(&h->d_arena_head, (const uint32_t*)nullptr, 2)) return SWB_ERR_HIP;
+    if (h->d_runs.fill(nullptr, units * 2) || h->d_rhdr.fill(nullptr, (size_t)p.N * SWB_RHDR_DWORDS) || h->d_arena_head.fill(nullptr, 2))
+      return SWB_ERR_HIP;
     p.runs = h->d_runs; p.rhdr = h->d_rhdr;
     p.arena_head = h->d_arena_head;
     p.arena_base = (int64_t)fixed;
@@ -304,8 +312,7 @@ int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
 int drop_run_lists(swb_engine* h) {
   if (!h->d_runs) return 0;
   HIP_TRY(hipDeviceSynchronize());
-  (void)hipFree(h->d_runs); (void)hipFree(h->d_rhdr); (void)hipFree(h->d_arena_head);
-  h->d_runs = nullptr; h->d_rhdr = nullptr; h->d_arena_head = nullptr;
+  h->d_runs.release(); h->d_rhdr.release(); h->d_arena_head.release();
   h->p.runs = nullptr; h->p.rhdr = nullptr; h->p.arena_head = nullptr;
   h->lists_valid = false;
   h->tables_dirty = true;
@@ -336,26 +343,24 @@ int flush_timing(swb_engine* h) {
   return 0;
 }
 
-int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream);
+// ---------------------------------------------------------------------------------------------------
+// What the two step paths share: launch() (tuned kernels) and launch_large() (large frames, many sprites) are each
+// check_ready, bind_step, their own kernels between the three marks of a step_timer, and, where the state phase is a cover build,
+// cover_launch_config.
+// ---------------------------------------------------------------------------------------------------
 
-int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
-  if (h->large_frames) return launch_large(h, actions, out, render_only, stream);
+int check_ready(const swb_engine* h, const void* actions, int render_only) {
   if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
-  const swb_config& c = h->cfg;
-  if (c.anti_aliasing != 1 && !(h->have_h && h->have_v))
+  if (h->p.AA != 1 && !(h->have_h && h->have_v))
     return fail(SWB_ERR_STATE, "swb_upload_resample (both axes) is required when anti_aliasing > 1");
-  const variant* v = pick_variant(h->p.Wc);
-  if (!v) return fail(SWB_ERR_INVALID, "canvas %dx%d not supported", h->p.Wc, h->p.Hc);
-  const bool paints_itself = h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1 && !h->no_paint_in_cover && v->fn_paint;
-  if (int rc = ensure_handoff_tables(h, !paints_itself)) return rc;
-  int vs = 0;
-  const kernel_fn fn2 = pick_resample(h->p.AA, h->vslots, &vs);
+  if (!render_only && actions == nullptr) return fail(SWB_ERR_INVALID, "actions is NULL");
+  return 0;
+}
+
+// The kernel argument of one launch: the handle's parameters with the caller's buffers bound.
+swb_params bind_step(const swb_engine* h, const void* actions, const swb_outputs* out, int render_only) {
   swb_params p = h->p;
-  if (p.v_tab && vs == 8) {                                           // slot tables of this VS
-    p.v_tab += (size_t)p.Hc * SWB_VSLOTS;
-    p.v_pfx += (size_t)(p.Hc + 1) * SWB_VSLOTS;
-  }
   p.actions = actions;
   p.obs = out ? out->obs : nullptr;
   p.reward = out ? out->reward : nullptr;
@@ -364,18 +369,83 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   p.success = out ? out->success : nullptr;
   p.error = out ? out->error : nullptr;
   p.render_only = render_only;
-  if (!render_only && actions == nullptr) return fail(SWB_ERR_INVALID, "actions is NULL");
+  return p;
+}
+
+// Launch configuration of cover build `fn` of variant `v`: the dynamic LDS of a wave, and how the kernel finds its way in it.
+int cover_launch_config(const swb_engine* h, const variant* v, kernel_fn fn, swb_params* p, size_t* lds_out) {
   int cpath_in_masks = 0;
   const size_t lds = lds_per_wave(h, v, &cpath_in_masks);
-  p.cpath_in_masks = cpath_in_masks;
-  p.lds_per_wave = (int32_t)lds;
-  p.outrow_bytes = (int32_t)v->outrow_bytes;
+  p->cpath_in_masks = cpath_in_masks;
+  p->lds_per_wave = (int32_t)lds;
+  p->outrow_bytes = (int32_t)v->outrow_bytes;
   if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "LDS request %zu B exceeds 160 KiB", lds);
-  // engines on which a sprite setter has been called run the build that reads the per-environment overrides
-  const bool paint = h->p.AA == 1 && h->p.ncg == 1 && out && out->obs && !h->no_paint_in_cover && v->fn_paint;
-  const kernel_fn fn = paint ? (h->d_ov_flag ? v->fn_paint_ov : v->fn_paint) : (h->d_ov_flag ? v->fn_ov : v->fn);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  *lds_out = lds;
+  return 0;
+}
+
+// The three events of a timed step (swb_timing_enable; nothing at all otherwise): begin() before the first kernel, mid() behind the
+// state / cover kernel, end() behind the last one.  A counted step's events wait for flush_timing; those of a launch that is not
+// one (swb_evaluate), or that failed half-way, go back to the pool unread.
+struct step_timer {
+  swb_engine* h;
+  hipStream_t stream;
+  swb_engine::step_events ev = {nullptr, nullptr, nullptr};
+  bool held = false;
+  step_timer(swb_engine* h_, hipStream_t stream_) : h(h_), stream(stream_) {}
+  ~step_timer() { if (held) h->event_pool.push_back(ev); }
+  int begin() {
+    if (!h->timing) return 0;
+    if (!h->event_pool.empty()) { ev = h->event_pool.back(); h->event_pool.pop_back(); }
+    else
+      for (hipEvent_t* e : {&ev.e0, &ev.e1, &ev.e2}) HIP_TRY(hipEventCreate(e));
+    held = true;
+    HIP_TRY(hipEventRecord(ev.e0, stream));
+    return 0;
+  }
+  int mid() {
+    if (held) HIP_TRY(hipEventRecord(ev.e1, stream));
+    return 0;
+  }
+  int end(bool counted) {
+    if (!held) return 0;
+    HIP_TRY(hipEventRecord(ev.e2, stream));
+    if (!counted) return 0;
+    held = false;
+    h->events.push_back(ev);
+    return h->events.size() >= 4096 ? flush_timing(h) : 0;
+  }
+};
+
+// This handle's cover kernel paints the frame itself -- anti_aliasing = 1 and one column group, that is a canvas of up to 64 px:
+// the one variant with painting builds -- and no second kernel runs, no run lists exist.  SWB_NO_PAINT_IN_COVER (tests, A/B) keeps
+// such a handle on two kernels; honour_switch = false asks about the geometry alone.
+bool paints_in_cover(const swb_engine* h, const variant* v, bool honour_switch = true) {
+  return h->p.AA == 1 && h->p.ncg == 1 && v && v->fn_paint && !(honour_switch && h->no_paint_in_cover);
+}
+
+int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream);
+
+int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
+  if (h->large_frames) return launch_large(h, actions, out, render_only, stream);
+  if (int rc = check_ready(h, actions, render_only)) return rc;
+  const variant* v = pick_variant(h->p.Wc);
+  if (!v) return fail(SWB_ERR_INVALID, "canvas %dx%d not supported", h->p.Wc, h->p.Hc);
+  if (int rc = ensure_handoff_tables(h, !paints_in_cover(h, v))) return rc;
+  int vs = 0;
+  const kernel_fn fn2 = pick_resample(h->p.AA, h->vslots, &vs);
+  swb_params p = bind_step(h, actions, out, render_only);
+  if (p.v_tab && vs == 8) {                                           // slot tables of this VS
+    p.v_tab += (size_t)p.Hc * SWB_VSLOTS;
+    p.v_pfx += (size_t)(p.Hc + 1) * SWB_VSLOTS;
+  }
+  // engines on which a sprite setter has been called run the build that reads the per-environment overrides
+  const bool paint = p.obs && paints_in_cover(h, v);
+  const kernel_fn fn = paint ? (h->d_ov_flag ? v->fn_paint_ov : v->fn_paint) : (h->d_ov_flag ? v->fn_ov : v->fn);
+  size_t lds = 0;
+  if (int rc = cover_launch_config(h, v, fn, &p, &lds)) return rc;
   // first launch, a new pool that shrank the LDS footprint (more waves resident), or the switch to the override build -- not
   // the switch between the painting and the plain build of a family, which alternating launches with and without an
   // observation buffer make at every launch (the cache is keyed on the family's plain build)
@@ -383,24 +453,15 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   if (!h->d_ovf || (int)lds < h->ovf_lds_bytes || fn_family != h->ovf_fn) {
     if (h->d_ovf) {
       HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(h->d_ovf); (void)hipFree(h->d_ovf_bitmap);
-      h->d_ovf = nullptr; h->d_ovf_bitmap = nullptr;
+      h->d_ovf.release(); h->d_ovf_bitmap.release();
     }
     if (int rc = ensure_overflow_slots(h, fn_family, h->d_ov_flag ? v->fn_paint_ov : v->fn_paint, lds)) return rc;
     h->ovf_lds_bytes = (int)lds;
     h->ovf_fn = fn_family;
     p.ovf = h->p.ovf; p.ovf_bitmap = h->p.ovf_bitmap; p.ovf_slots = h->p.ovf_slots;
   }
-  swb_engine::step_events ev = {nullptr, nullptr, nullptr};
-  if (h->timing) {
-    if (!h->event_pool.empty()) { ev = h->event_pool.back(); h->event_pool.pop_back(); }
-    else {
-      HIP_TRY(hipEventCreate(&ev.e0));
-      HIP_TRY(hipEventCreate(&ev.e1));
-      HIP_TRY(hipEventCreate(&ev.e2));
-    }
-    HIP_TRY(hipEventRecord(ev.e0, stream));
-  }
+  step_timer timer(h, stream);
+  if (int rc = timer.begin()) return rc;
   const size_t lds2 = p.AA == 1 ? 0 : (((size_t)p.h_pfx_len * 4 + 15) & ~(size_t)15);
   p.parity = h->launch_parity;
   p.cphase = h->launch_phase;
@@ -425,34 +486,22 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
     const dim3 grid(blocks_x, (p.cost_cnt && p.band_tasks) ? 1 : p.nbands, p.cost_cnt ? 1 : p.ncg);
     hipLaunchKernelGGL(fn2, grid, dim3(SWB_WAVE * SWB_RS_WAVES_PER_BLOCK), lds2, st, p);
   };
-  launch_cover(0, c.n_envs);
+  launch_cover(0, p.N);
   HIP_TRY(hipGetLastError());
-  if (h->timing && !p.paint_in_cover) HIP_TRY(hipEventRecord(ev.e1, stream));
-  if (p.obs && !p.paint_in_cover) launch_resample(0, c.n_envs, stream);
+  if (int rc = timer.mid()) return rc;            // (a painting cover kernel is the whole step: nothing follows before end())
+  if (p.obs && !p.paint_in_cover) launch_resample(0, p.N, stream);
   HIP_TRY(hipGetLastError());
   if (!p.obs && p.cost_cnt && render_only != 2)   // no second kernel to clear the next launch's bucket counters (kind 0; the cover kernel keeps kind 1)
     HIP_TRY(hipMemsetAsync(h->d_cost_cnt + (size_t)(p.parity ^ 1) * SWB_COST_SET, 0, SWB_COST_SET * sizeof(uint32_t), stream));
-  if (render_only == 2) {
-    // swb_evaluate files nothing and lists nothing: the dispatch state (parity, phase, what the previous launch filed) stays as
-    // the last step left it -- an evaluation between two steps does not cost the next one its cost order (round-5 advice)
-    if (h->timing) {
-      HIP_TRY(hipEventRecord(ev.e1, stream));
-      HIP_TRY(hipEventRecord(ev.e2, stream));
-      h->event_pool.push_back(ev);
-    }
-    return 0;
-  }
+  // swb_evaluate files nothing and lists nothing: the dispatch state (parity, phase, what the previous launch filed) stays as
+  // the last step left it -- an evaluation between two steps does not cost the next one its cost order (round-5 advice) --, and
+  // it is not a timed launch
+  if (render_only == 2) return timer.end(false);
   h->cover_lists_filed = p.obs && p.ccost_list;
   h->lists_valid = p.obs && !p.paint_in_cover;
   h->launch_phase = (h->launch_phase + 1) % 3;
   h->launch_parity ^= 1;
-  if (h->timing) {
-    if (p.paint_in_cover) HIP_TRY(hipEventRecord(ev.e1, stream));      // (no second kernel: the whole step is the cover kernel)
-    HIP_TRY(hipEventRecord(ev.e2, stream));
-    h->events.push_back(ev);
-    if (h->events.size() >= 4096) return flush_timing(h);
-  }
-  return 0;
+  return timer.end(true);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -485,10 +534,9 @@ int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
   const size_t per_env = p.AA == 1 ? 0 : (size_t)p.Hc * p.Wo * 3;
   long long chunk = per_env ? (long long)(h->lf_scratch_budget / per_env) : (long long)p.N;
   chunk = std::max(1ll, std::min(chunk, std::min((long long)p.N, 65535ll)));       // (environments are a grid dimension)
-  if (per_env && h->lf_tmp_bytes < (size_t)chunk * per_env) {
-    if (h->d_lf_tmp) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(h->d_lf_tmp); h->d_lf_tmp = nullptr; h->lf_tmp_bytes = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_lf_tmp), (size_t)chunk * per_env));
-    h->lf_tmp_bytes = (size_t)chunk * per_env;
+  if (per_env && h->d_lf_tmp.count < (size_t)chunk * per_env) {
+    if (h->d_lf_tmp) HIP_TRY(hipDeviceSynchronize());
+    if (h->d_lf_tmp.fill(nullptr, (size_t)chunk * per_env)) return SWB_ERR_HIP;
   }
   swb_lf_args a;
   memset(&a, 0, sizeof(a));
@@ -519,21 +567,8 @@ int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
 }
 
 int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
-  if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
-  if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
-  if (h->p.AA != 1 && !(h->have_h && h->have_v))
-    return fail(SWB_ERR_STATE, "swb_upload_resample (both axes) is required when anti_aliasing > 1");
-  if (!render_only && actions == nullptr) return fail(SWB_ERR_INVALID, "actions is NULL");
-  const variant* v = &kVariants[0];
-  swb_params p = h->p;
-  p.actions = actions;
-  p.obs = out ? out->obs : nullptr;
-  p.reward = out ? out->reward : nullptr;
-  p.discount = out ? out->discount : nullptr;
-  p.step_type = out ? out->step_type : nullptr;
-  p.success = out ? out->success : nullptr;
-  p.error = out ? out->error : nullptr;
-  p.render_only = render_only;
+  if (int rc = check_ready(h, actions, render_only)) return rc;
+  swb_params p = bind_step(h, actions, out, render_only);
   // the state phase: the cover kernel of the narrowest build with obs = NULL, or (many sprites) swb_ms_state_kernel, whose LDS
   // does not depend on the scene
   kernel_fn fn;
@@ -542,42 +577,22 @@ int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int
     fn = h->d_ov_flag ? swb_ms_state_kernel<true> : swb_ms_state_kernel<false>;
     lds = sizeof(swb_ms_lds);
   } else {
-    int cpath_in_masks = 0;
-    lds = lds_per_wave(h, v, &cpath_in_masks);
-    p.cpath_in_masks = cpath_in_masks;
-    p.lds_per_wave = (int32_t)lds;
-    p.outrow_bytes = (int32_t)v->outrow_bytes;
-    if (lds > 160 * 1024) return fail(SWB_ERR_INVALID, "LDS request %zu B exceeds 160 KiB", lds);
+    const variant* v = &kVariants[0];
     fn = h->d_ov_flag ? v->fn_ov : v->fn;
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = cover_launch_config(h, v, fn, &p, &lds)) return rc;
   }
-  swb_engine::step_events ev = {nullptr, nullptr, nullptr};
-  if (h->timing) {
-    if (!h->event_pool.empty()) { ev = h->event_pool.back(); h->event_pool.pop_back(); }
-    else {
-      HIP_TRY(hipEventCreate(&ev.e0));
-      HIP_TRY(hipEventCreate(&ev.e1));
-      HIP_TRY(hipEventCreate(&ev.e2));
-    }
-    HIP_TRY(hipEventRecord(ev.e0, stream));
-  }
+  step_timer timer(h, stream);
+  if (int rc = timer.begin()) return rc;
   if (render_only != 1) {                      // the state phase (swb_render has no state to advance: the frame only)
     swb_params pc = p;
     pc.obs = nullptr;
     hipLaunchKernelGGL(fn, dim3(p.N), dim3(SWB_WAVE), lds, stream, pc);
     HIP_TRY(hipGetLastError());
   }
-  if (h->timing) HIP_TRY(hipEventRecord(ev.e1, stream));
+  if (int rc = timer.mid()) return rc;
   if (p.obs && render_only != 2)
     if (int rc = lf_render(h, p, stream)) return rc;
-  if (h->timing) {
-    HIP_TRY(hipEventRecord(ev.e2, stream));
-    if (render_only == 2) { h->event_pool.push_back(ev); return 0; }     // (swb_evaluate: not a timed launch, as on the tuned path)
-    h->events.push_back(ev);
-    if (h->events.size() >= 4096) return flush_timing(h);
-  }
-  return 0;
+  return timer.end(render_only != 2);          // (swb_evaluate: not a timed launch, as on the tuned path)
 }
 
 // swb_upload_resample of a large-frame handle: the raw Pillow tables, and per output column the prefix sums of its
@@ -597,7 +612,7 @@ int upload_resample_large(swb_engine* h, int axis, int out_size, int ksize, cons
       hp.push_back(0);
       for (int j = 0; j < cnt; ++j) { acc += coeffs[(size_t)o * ksize + j]; hp.push_back(acc); }
     }
-    if (upload(&h->d_lf_hb, hb.data(), hb.size()) || upload(&h->d_lf_hpo, hpo.data(), hpo.size()) || upload(&h->d_lf_hp, hp.data(), hp.size()))
+    if (h->d_lf_hb.fill(hb.data(), hb.size()) || h->d_lf_hpo.fill(hpo.data(), hpo.size()) || h->d_lf_hp.fill(hp.data(), hp.size()))
       return SWB_ERR_HIP;
     h->have_h = true;
   } else if (axis == 1) {
@@ -606,13 +621,33 @@ int upload_resample_large(swb_engine* h, int axis, int out_size, int ksize, cons
       const int ymin = bounds[2 * r], cnt = bounds[2 * r + 1];
       if (cnt < 0 || cnt > ksize || ymin < 0 || ymin + cnt > p.Hc) return fail(SWB_ERR_INVALID, "bad vertical bounds at %d", r);
     }
-    if (upload(&h->d_lf_vb, bounds, 2 * (size_t)out_size) || upload(&h->d_lf_vk, coeffs, (size_t)out_size * ksize)) return SWB_ERR_HIP;
+    if (h->d_lf_vb.fill(bounds, 2 * (size_t)out_size) || h->d_lf_vk.fill(coeffs, (size_t)out_size * ksize)) return SWB_ERR_HIP;
     h->lf_vks = ksize;
     h->have_v = true;
   } else {
     return fail(SWB_ERR_INVALID, "axis must be 0 or 1");
   }
   return SWB_OK;
+}
+
+// The pool's device arrays as the kernels see them (swb_set_pool, swb_sample_pool).  The angle and colour columns are optional in
+// a pool set from the host, the per-cell labels exist on handles with a task that keys on position.
+void bind_pool(swb_engine* h, bool have_angle, bool have_color) {
+  swb_params& p = h->p;
+  p.p_n = h->d_p_n; p.p_x = h->d_p_x; p.p_y = h->d_p_y; p.p_xv = h->d_p_xv; p.p_yv = h->d_p_yv;
+  p.p_scale = h->d_p_scale; p.p_ca = h->d_p_ca; p.p_sa = h->d_p_sa; p.p_shape = h->d_p_shape; p.p_rgb = h->d_p_rgb;
+  p.p_label = h->d_p_label; p.pool_base = h->d_pool_base; p.pool_len = h->d_pool_len;
+  p.p_angle = have_angle ? h->d_p_angle.ptr : nullptr;
+  p.p_color = have_color ? h->d_p_color.ptr : nullptr;
+  p.p_cell_label = h->keyed ? h->d_p_cell_label.ptr : nullptr;
+}
+
+// Argument of swb_sample_pool_kernel.  skip_live (swb_resample_pool): entries an environment is playing are left as they are.
+swb_sampler_args sampler_args(const swb_engine* h, uint64_t seed, uint64_t first_entry, bool skip_live) {
+  return {h->d_sampler, h->pool_entries, h->p.S, h->p.n_tasks, seed, first_entry, skip_live ? h->d_entry.ptr : nullptr,
+          skip_live ? h->d_pool_base.ptr : nullptr, skip_live ? h->d_pool_len.ptr : nullptr, h->p.N, h->d_p_n, h->d_p_x, h->d_p_y,
+          h->d_p_xv, h->d_p_yv, h->d_p_scale, h->d_p_ca, h->d_p_sa, h->d_p_angle, h->d_p_color, h->d_p_shape, h->d_p_rgb,
+          h->d_p_label, h->d_p_attr};
 }
 
 }  // namespace
@@ -639,10 +674,12 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(SWB_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-  swb_engine* h = new swb_engine();
+  // (a refusal below frees whatever the handle holds by then: it is the caller's only once *out is set)
+  std::unique_ptr<swb_engine> owner(new swb_engine());
+  swb_engine* const h = owner.get();
   h->cfg = *cfg;
   h->device = device;
-  (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device);
+  HIP_TRY(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device));
   h->no_paint_in_cover = getenv("SWB_NO_PAINT_IN_COVER") != nullptr;
   h->force_cover_order = getenv("SWB_COVER_ORDER") != nullptr;
   swb_params& p = h->p;
@@ -662,12 +699,10 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   memcpy(p.tasks, cfg->tasks, sizeof(p.tasks));
   for (int t = 0; t < cfg->n_tasks; ++t) {
     const swb_task& tk = cfg->tasks[t];
-    if (tk.n_xcuts < 0 || tk.n_xcuts > SWB_MAX_CUTS || tk.n_ycuts < 0 || tk.n_ycuts > SWB_MAX_CUTS) {
-      delete h;
+    if (tk.n_xcuts < 0 || tk.n_xcuts > SWB_MAX_CUTS || tk.n_ycuts < 0 || tk.n_ycuts > SWB_MAX_CUTS)
       return fail(SWB_ERR_INVALID, "task %d: between 0 and %d position thresholds per axis supported", t, SWB_MAX_CUTS);
-    }
-    for (int k = 1; k < tk.n_xcuts; ++k) if (!(tk.xcuts[k - 1] < tk.xcuts[k])) { delete h; return fail(SWB_ERR_INVALID, "task %d: xcuts must ascend", t); }
-    for (int k = 1; k < tk.n_ycuts; ++k) if (!(tk.ycuts[k - 1] < tk.ycuts[k])) { delete h; return fail(SWB_ERR_INVALID, "task %d: ycuts must ascend", t); }
+    for (int k = 1; k < tk.n_xcuts; ++k) if (!(tk.xcuts[k - 1] < tk.xcuts[k])) return fail(SWB_ERR_INVALID, "task %d: xcuts must ascend", t);
+    for (int k = 1; k < tk.n_ycuts; ++k) if (!(tk.ycuts[k - 1] < tk.ycuts[k])) return fail(SWB_ERR_INVALID, "task %d: ycuts must ascend", t);
     if (tk.n_xcuts + tk.n_ycuts > 0) h->keyed = true;
   }
   // frames the tuned kernels cannot take (a canvas wider than the widest cover build, more than SWB_MAX_CG column groups) go
@@ -682,31 +717,31 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     if (const char* x = getenv("SWB_LF_SCRATCH_BYTES")) h->lf_scratch_budget = (size_t)std::max(1ll, atoll(x));   // tests: force chunks
   }
   if (h->large_frames) {
-    if (p.Wc > SWB_LF_MAX_CANVAS || p.Hc > SWB_LF_MAX_CANVAS) {
-      delete h;
+    if (p.Wc > SWB_LF_MAX_CANVAS || p.Hc > SWB_LF_MAX_CANVAS)
       return fail(SWB_ERR_INVALID, "canvas %dx%d too large: at most %d px in either direction (anti_aliasing * image_size)", p.Wc, p.Hc,
                   SWB_LF_MAX_CANVAS);
-    }
-    if (p.Wo > SWB_LF_MAX_COLUMNS) { delete h; return fail(SWB_ERR_INVALID, "image width %d too large: at most %d columns", p.Wo, SWB_LF_MAX_COLUMNS); }
+    if (p.Wo > SWB_LF_MAX_COLUMNS) return fail(SWB_ERR_INVALID, "image width %d too large: at most %d columns", p.Wo, SWB_LF_MAX_COLUMNS);
   } else if (p.Hc > 65535) {
-    delete h;
     return fail(SWB_ERR_INVALID, "canvas %dx%d too large", p.Wc, p.Hc);
   }
+  // groups of 64 output columns (the kernels of the large-frame path know none: swb_params::ncg stays 0 there)
+  const int ncg = (p.Wo + 63) / 64;
+  if (!h->large_frames) p.ncg = ncg;
+  const int cus = std::max(h->cus, 1);
   // Bands of output rows per (environment, column group) in the second kernel: a band repeats the 25 canvas rows it
   // shares with the band above, so there are only as many as it takes to give every SIMD its eight waves (small
   // batches), in bands of at least 16 rows -- of 8 rows where those fill the SIMDs no more than once (measured, 64-px images:
   // 512 environments 0.0311 ms in 8 bands against 0.0354 in 4; 1024 environments, every band a task of its own (band_tasks
   // below), 0.0342 against 0.0366; 2048 environments 0.0498 against 0.0422: profiles/r06_experiments/bands_small_batches.txt).
   {
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const long long resident = (long long)std::max(cus, 1) * 4 * SWB_RS_WAVES_PER_SIMD;
-    const long long tasks = (long long)p.N * ((p.Wo + 63) / 64);
+    const long long resident = (long long)cus * 4 * SWB_RS_WAVES_PER_SIMD;
+    const long long tasks = (long long)p.N * ncg;
     int nb = 1;
     while (nb < SWB_MAX_BANDS && tasks * nb < resident && (p.Ho / (2 * nb) >= 16 || (p.Ho / (2 * nb) >= 8 && tasks * nb * 2 <= resident))) nb *= 2;
     if (const char* x = getenv("SWB_BANDS")) nb = std::max(1, std::min(atoi(x), (int)SWB_MAX_BANDS));
     h->nbands = std::min(nb, p.Ho);
   }
+  const long long rs_waves = (long long)p.N * ncg * h->nbands;      // waves of the second kernel: one per (environment, column group, band)
   // cost buckets of the second kernel's tasks: 32 of them over the cost of a run list (3 per run + 2 per 8-byte unit: a canvas row
   // costs 1 unit (one span), 2 (two or three) or more, and rows that repeat the row above nothing); the range they span is
   // fitted by every launch (cost_housekeeping), to begin with it is [0, 8 * canvas height)
@@ -716,14 +751,9 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     // the launch has four waves or more per SIMD to deal (measured, resample / fill kernel: 2048 environments in 4 bands -9.5 %,
     // 1024 -2 %, a 128x128 image at anti_aliasing = 1 -22 %; two waves per SIMD, 256 environments in 8 bands, +3 %:
     // profiles/r06_experiments/band_tasks_ab.txt).
-    {
-      int cus3 = 0;
-      (void)hipDeviceGetAttribute(&cus3, hipDeviceAttributeMultiprocessorCount, device);
-      const long long waves3 = (long long)p.N * ((p.Wo + 63) / 64) * h->nbands;
-      p.band_tasks = (h->nbands > 1 && waves3 >= 4ll * std::max(cus3, 1) * 4 && !getenv("SWB_NO_BAND_TASKS")) ? 1 : 0;
-      if (const char* x = getenv("SWB_BAND_TASKS")) p.band_tasks = (h->nbands > 1 && atoi(x) != 0) ? 1 : 0;      // tests
-    }
-    p.cost_cap = ((p.Wo + 63) / 64) * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) * (p.band_tasks ? h->nbands : 1);
+    p.band_tasks = (h->nbands > 1 && rs_waves >= 4ll * cus * 4 && !getenv("SWB_NO_BAND_TASKS")) ? 1 : 0;
+    if (const char* x = getenv("SWB_BAND_TASKS")) p.band_tasks = (h->nbands > 1 && atoi(x) != 0) ? 1 : 0;      // tests
+    p.cost_cap = ncg * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) * (p.band_tasks ? h->nbands : 1);
     std::vector<uint32_t> cnt0(5 * SWB_COST_SET + SWB_COST_WORDS, 0u);
     for (int ph = 0; ph < 3; ++ph) cnt0[SWB_COST_WORD_COVER_SHIFT(ph)] = 12;   // bucket width of the cover kernel's cycle counts: 2^12 to begin with
     for (int par = 0; par < 2; ++par) {                                       // buckets of the second kernel's tasks: [0, cost_range0) to begin with
@@ -734,30 +764,20 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     p.prio_div = 4;              // (measured: levels of a quarter of a mean wave 2 % better than of half a wave, at 8192 environments)
     if (const char* x = getenv("SWB_PRIO_DIV")) p.prio_div = std::max(1, atoi(x));
     // (priorities when the launch is at most two rounds of resample waves: in steady state they cost 0.8 %)
-    {
-      int cus2 = 0;
-      (void)hipDeviceGetAttribute(&cus2, hipDeviceAttributeMultiprocessorCount, device);
-      const long long waves = (long long)p.N * ((p.Wo + 63) / 64) * h->nbands;
-      p.prio_levels = (!getenv("SWB_NO_PRIO") && waves <= 2ll * std::max(cus2, 1) * 4 * SWB_RS_WAVES_PER_SIMD) ? 1 : 0;
-      if (!getenv("SWB_NO_COVER_PRIO")) p.prio_levels |= 2;          // (cover waves: only ever used with cover_order)
-    }
+    p.prio_levels = (!getenv("SWB_NO_PRIO") && rs_waves <= 2ll * cus * 4 * SWB_RS_WAVES_PER_SIMD) ? 1 : 0;
+    if (!getenv("SWB_NO_COVER_PRIO")) p.prio_levels |= 2;          // (cover waves: only ever used with cover_order)
     const size_t ccap = (size_t)(p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS;
-    if (upload(&h->d_cost_cnt, cnt0.data(), cnt0.size()) ||
-        upload(&h->d_ccost_list, (const int32_t*)nullptr, (size_t)3 * SWB_COST_SHARDS * SWB_COST_BUCKETS * ccap) ||
-        upload(&h->d_cost_list, (const int32_t*)nullptr, (size_t)2 * SWB_COST_SHARDS * SWB_COST_BUCKETS * p.cost_cap)) {
-      swb_destroy(h);
+    if (h->d_cost_cnt.fill(cnt0.data(), cnt0.size()) ||
+        h->d_ccost_list.fill(nullptr, (size_t)3 * SWB_COST_SHARDS * SWB_COST_BUCKETS * ccap) ||
+        h->d_cost_list.fill(nullptr, (size_t)2 * SWB_COST_SHARDS * SWB_COST_BUCKETS * p.cost_cap))
       return SWB_ERR_HIP;
-    }
     p.cost_cnt = h->d_cost_cnt; p.cost_list = h->d_cost_list;
     if (!getenv("SWB_NO_COVER_ORDER")) p.ccost_list = h->d_ccost_list;
     // rounds of the dealing = the compute units of an XCD (8 XCDs; a power of two on this part: 32)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const int per_xcd = cus / SWB_COST_SHARDS;
+    const int per_xcd = h->cus / SWB_COST_SHARDS;
     // (only when every wave of the launch is resident at once: with several rounds of waves the heaviest tasks must simply
     // come first -- measured on two rounds: +1...2 % with alternating rounds)
-    const long long waves = (long long)p.N * ((p.Wo + 63) / 64) * h->nbands;
-    if (per_xcd >= 2 && (per_xcd & (per_xcd - 1)) == 0 && waves <= (long long)cus * 4 * SWB_RS_WAVES_PER_SIMD && !getenv("SWB_NO_SNAKE"))
+    if (per_xcd >= 2 && (per_xcd & (per_xcd - 1)) == 0 && rs_waves <= (long long)h->cus * 4 * SWB_RS_WAVES_PER_SIMD && !getenv("SWB_NO_SNAKE"))
       while ((1 << p.deal_shift) < per_xcd) ++p.deal_shift;
     if (const char* x = getenv("SWB_DEAL_SHIFT")) p.deal_shift = std::max(0, atoi(x));      // tests: short rounds on small batches
   }
@@ -773,15 +793,9 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   if (const char* x = getenv("SWB_RUN_CAP")) p.run_cap = std::max(8, atoi(x));      // tests
   if (const char* x = getenv("SWB_ARENA_UNITS")) h->arena_override = std::max(0, atoi(x));   // tests (0: no arena)
   const size_t NS = (size_t)p.N * p.S;
-  int rc = 0;
-  rc |= upload(&h->d_x, (const double*)nullptr, NS);
-  rc |= upload(&h->d_y, (const double*)nullptr, NS);
-  rc |= upload(&h->d_nspr, (const int32_t*)nullptr, p.N);
-  rc |= upload(&h->d_entry, (const int32_t*)nullptr, p.N);
-  rc |= upload(&h->d_step_count, (const int32_t*)nullptr, p.N);
-  rc |= upload(&h->d_episode, (const int32_t*)nullptr, p.N);
-  rc |= upload(&h->d_reset_next, (const uint8_t*)nullptr, p.N);
-  if (rc) { swb_destroy(h); return SWB_ERR_HIP; }
+  if (h->d_x.fill(nullptr, NS) || h->d_y.fill(nullptr, NS) || h->d_nspr.fill(nullptr, p.N) || h->d_entry.fill(nullptr, p.N) ||
+      h->d_step_count.fill(nullptr, p.N) || h->d_episode.fill(nullptr, p.N) || h->d_reset_next.fill(nullptr, p.N))
+    return SWB_ERR_HIP;
   p.max_spans = SWB_MIN_SPANS;
   if (const char* ms = getenv("SWB_MAX_SPANS")) p.max_spans = atoi(ms) < SWB_MIN_SPANS ? SWB_MIN_SPANS : atoi(ms);
   p.span_cap = p.max_spans;
@@ -792,7 +806,7 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   p.ovf = nullptr;
   p.x = h->d_x; p.y = h->d_y; p.nspr = h->d_nspr; p.entry = h->d_entry; p.step_count = h->d_step_count;
   p.episode = h->d_episode; p.reset_next = h->d_reset_next;
-  *out = h;
+  *out = owner.release();
   return SWB_OK;
 }
 
@@ -801,14 +815,6 @@ int swb_destroy(swb_handle h) {
   (void)hipSetDevice(h->device);
   for (auto* list : {&h->events, &h->event_pool})
     for (auto& ev : *list) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); (void)hipEventDestroy(ev.e2); }
-  void* bufs[] = {h->d_shape_verts, h->d_shape_dmin, h->d_shape_off, h->d_h_xmin, h->d_h_cnt, h->d_h_tbl, h->d_h_pfx, h->d_v_tab,
-                  h->d_v_pfx, h->d_v_end, h->d_p_n, h->d_p_x, h->d_p_y, h->d_p_xv, h->d_p_yv, h->d_p_scale, h->d_p_ca, h->d_p_sa,
-                  h->d_p_shape, h->d_p_rgb, h->d_p_label, h->d_p_cell_label, h->d_ov_cell_label, h->d_p_attr, h->d_pool_base, h->d_pool_len, h->d_x, h->d_y, h->d_nspr,
-                  h->d_entry, h->d_step_count, h->d_episode, h->d_reset_next, h->d_ovf, h->d_ovf_bitmap, h->d_p_angle, h->d_p_color, h->d_sampler,
-                  h->d_ov_flag, h->d_ov_shape, h->d_ov_scale, h->d_ov_angle, h->d_ov_cpath, h->d_ov_label,
-                  h->d_cost_cnt, h->d_cost_list, h->d_ccost_list, h->d_runs, h->d_rhdr, h->d_arena_head, h->d_env_state, h->d_band_y0, h->d_band_first, h->d_band_lo, h->d_cg_lo, h->d_cg_hi, h->d_v_break,
-                  h->d_lf_hb, h->d_lf_hpo, h->d_lf_hp, h->d_lf_vb, h->d_lf_vk, h->d_lf_tmp, h->d_rollout, h->d_rollout_steps};
-  for (void* b : bufs) if (b) (void)hipFree(b);
   delete h;
   return SWB_OK;
 }
@@ -838,10 +844,10 @@ int swb_upload_shapes(swb_handle h, const double* verts, const int32_t* offsets,
   dmin.resize(SWB_MAX_SHAPES, 0.0);
   std::vector<int32_t> off_padded(offsets, offsets + n_shapes + 1);
   off_padded.resize(SWB_MAX_SHAPES + 1, offsets[n_shapes]);
-  if (upload(&h->d_shape_dmin, dmin.data(), dmin.size())) return SWB_ERR_HIP;
+  if (h->d_shape_dmin.fill(dmin.data(), dmin.size())) return SWB_ERR_HIP;
   h->p.shape_dmin = h->d_shape_dmin;
-  if (upload(&h->d_shape_verts, verts, (size_t)offsets[n_shapes] * 2)) return SWB_ERR_HIP;
-  if (upload(&h->d_shape_off, off_padded.data(), off_padded.size())) return SWB_ERR_HIP;
+  if (h->d_shape_verts.fill(verts, (size_t)offsets[n_shapes] * 2)) return SWB_ERR_HIP;
+  if (h->d_shape_off.fill(off_padded.data(), off_padded.size())) return SWB_ERR_HIP;
   h->p.shape_verts = h->d_shape_verts;
   h->p.shape_off = h->d_shape_off;
   h->p.max_verts = maxv;
@@ -876,8 +882,8 @@ int swb_upload_resample(swb_handle h, int32_t axis, int32_t out_size, int32_t ks
       tbl[o] = uniq_off[found];
     }
     if (pfx.size() * 4 > 32 * 1024) return fail(SWB_ERR_INVALID, "horizontal prefix table too large (%zu entries)", pfx.size());
-    if (upload(&h->d_h_xmin, xmin.data(), xmin.size()) || upload(&h->d_h_cnt, cnt.data(), cnt.size()) ||
-        upload(&h->d_h_tbl, tbl.data(), tbl.size()) || upload(&h->d_h_pfx, pfx.data(), pfx.size()))
+    if (h->d_h_xmin.fill(xmin.data(), xmin.size()) || h->d_h_cnt.fill(cnt.data(), cnt.size()) ||
+        h->d_h_tbl.fill(tbl.data(), tbl.size()) || h->d_h_pfx.fill(pfx.data(), pfx.size()))
       return SWB_ERR_HIP;
     h->p.h_xmin = h->d_h_xmin; h->p.h_cnt = h->d_h_cnt; h->p.h_tbl = h->d_h_tbl; h->p.h_pfx = h->d_h_pfx;
     h->p.h_pfx_len = (int32_t)pfx.size();
@@ -923,8 +929,8 @@ int swb_upload_resample(swb_handle h, int32_t axis, int32_t out_size, int32_t ks
               vpfx[t * pfx_len + (size_t)y * SWB_VSLOTS + k] + vtab[t * tab_len + (size_t)y * SWB_VSLOTS + k];
     std::vector<int32_t> vend_padded(vend);
     vend_padded.push_back(0x7fffffff); vend_padded.push_back(0x7fffffff);       // the resample kernel loads one row ahead
-    if (upload(&h->d_v_tab, vtab.data(), vtab.size()) || upload(&h->d_v_end, vend_padded.data(), vend_padded.size()) ||
-        upload(&h->d_v_pfx, vpfx.data(), vpfx.size()))
+    if (h->d_v_tab.fill(vtab.data(), vtab.size()) || h->d_v_end.fill(vend_padded.data(), vend_padded.size()) ||
+        h->d_v_pfx.fill(vpfx.data(), vpfx.size()))
       return SWB_ERR_HIP;
     h->p.v_tab = h->d_v_tab; h->p.v_end = h->d_v_end; h->p.v_pfx = h->d_v_pfx;
     h->vslots = used;
@@ -973,30 +979,24 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
   for (size_t i = 0; i < PS; ++i)
     if (pool->shape[i] < 0 || (h->have_shapes && pool->shape[i] >= SWB_MAX_SHAPES)) return fail(SWB_ERR_INVALID, "bad shape index in pool");
   int rc = 0;
-  rc |= upload(&h->d_p_n, pool->n_sprites, P);
-  rc |= upload(&h->d_p_x, pool->x, PS); rc |= upload(&h->d_p_y, pool->y, PS);
-  rc |= upload(&h->d_p_xv, pool->x_vel, PS); rc |= upload(&h->d_p_yv, pool->y_vel, PS);
-  rc |= upload(&h->d_p_scale, pool->scale, PS); rc |= upload(&h->d_p_ca, pool->cos_a, PS); rc |= upload(&h->d_p_sa, pool->sin_a, PS);
-  rc |= upload(&h->d_p_shape, pool->shape, PS);
-  rc |= upload(&h->d_p_rgb, rgb.data(), PS);
-  rc |= upload(&h->d_p_label, pool->label, (size_t)P * T * S);
+  rc |= h->d_p_n.fill(pool->n_sprites, P);
+  rc |= h->d_p_x.fill(pool->x, PS); rc |= h->d_p_y.fill(pool->y, PS);
+  rc |= h->d_p_xv.fill(pool->x_vel, PS); rc |= h->d_p_yv.fill(pool->y_vel, PS);
+  rc |= h->d_p_scale.fill(pool->scale, PS); rc |= h->d_p_ca.fill(pool->cos_a, PS); rc |= h->d_p_sa.fill(pool->sin_a, PS);
+  rc |= h->d_p_shape.fill(pool->shape, PS);
+  rc |= h->d_p_rgb.fill(rgb.data(), PS);
+  rc |= h->d_p_label.fill(pool->label, (size_t)P * T * S);
   if (h->keyed) {
     if (!pool->cell_label) return fail(SWB_ERR_INVALID, "a task of this handle keys on position (swb_task::n_xcuts / n_ycuts): swb_pool::cell_label is required");
-    rc |= upload(&h->d_p_cell_label, pool->cell_label, (size_t)P * T * S * SWB_MAX_CELLS);
+    rc |= h->d_p_cell_label.fill(pool->cell_label, (size_t)P * T * S * SWB_MAX_CELLS);
   }
-  rc |= upload(&h->d_p_attr, pool->attr_f32, PS);                      // (NULL: zeros = Python numbers)
-  rc |= upload(&h->d_pool_base, pool->pool_base, N);
-  rc |= upload(&h->d_pool_len, pool->pool_len, N);
-  if (pool->angle) rc |= upload(&h->d_p_angle, pool->angle, PS);
-  if (pool->color) rc |= upload(&h->d_p_color, pool->color, PS * 3);
+  rc |= h->d_p_attr.fill(pool->attr_f32, PS);                          // (NULL: zeros = Python numbers)
+  rc |= h->d_pool_base.fill(pool->pool_base, N);
+  rc |= h->d_pool_len.fill(pool->pool_len, N);
+  if (pool->angle) rc |= h->d_p_angle.fill(pool->angle, PS);
+  if (pool->color) rc |= h->d_p_color.fill(pool->color, PS * 3);
   if (rc) return SWB_ERR_HIP;
-  h->p.p_angle = pool->angle ? h->d_p_angle : nullptr;
-  h->p.p_color = pool->color ? h->d_p_color : nullptr;
-  swb_params& p = h->p;
-  p.p_n = h->d_p_n; p.p_x = h->d_p_x; p.p_y = h->d_p_y; p.p_xv = h->d_p_xv; p.p_yv = h->d_p_yv;
-  p.p_scale = h->d_p_scale; p.p_ca = h->d_p_ca; p.p_sa = h->d_p_sa; p.p_shape = h->d_p_shape; p.p_rgb = h->d_p_rgb;
-  p.p_label = h->d_p_label; p.pool_base = h->d_pool_base; p.pool_len = h->d_pool_len;
-  p.p_cell_label = h->keyed ? h->d_p_cell_label : nullptr;
+  bind_pool(h, pool->angle != nullptr, pool->color != nullptr);
   h->pool_entries = P;
   h->pool_sampled = false;
   if (most_verts > 0) h->p.max_edges = most_verts;
@@ -1090,28 +1090,23 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
   const size_t PS = (size_t)P * S;
   int rc = 0;
   if (h->pool_entries != P || !h->d_p_angle || !h->d_p_color) {
-    rc |= upload<int32_t>(&h->d_p_n, nullptr, P);
-    rc |= upload<double>(&h->d_p_x, nullptr, PS); rc |= upload<double>(&h->d_p_y, nullptr, PS);
-    rc |= upload<double>(&h->d_p_xv, nullptr, PS); rc |= upload<double>(&h->d_p_yv, nullptr, PS);
-    rc |= upload<double>(&h->d_p_scale, nullptr, PS); rc |= upload<double>(&h->d_p_ca, nullptr, PS);
-    rc |= upload<double>(&h->d_p_sa, nullptr, PS);
-    rc |= upload<int32_t>(&h->d_p_shape, nullptr, PS); rc |= upload<uint32_t>(&h->d_p_rgb, nullptr, PS);
-    rc |= upload<int8_t>(&h->d_p_label, nullptr, (size_t)P * T * S);
-    rc |= upload<uint8_t>(&h->d_p_attr, nullptr, PS);
-    rc |= upload<double>(&h->d_p_angle, nullptr, PS); rc |= upload<double>(&h->d_p_color, nullptr, PS * 3);
+    rc |= h->d_p_n.fill(nullptr, P);
+    rc |= h->d_p_x.fill(nullptr, PS); rc |= h->d_p_y.fill(nullptr, PS);
+    rc |= h->d_p_xv.fill(nullptr, PS); rc |= h->d_p_yv.fill(nullptr, PS);
+    rc |= h->d_p_scale.fill(nullptr, PS); rc |= h->d_p_ca.fill(nullptr, PS);
+    rc |= h->d_p_sa.fill(nullptr, PS);
+    rc |= h->d_p_shape.fill(nullptr, PS); rc |= h->d_p_rgb.fill(nullptr, PS);
+    rc |= h->d_p_label.fill(nullptr, (size_t)P * T * S);
+    rc |= h->d_p_attr.fill(nullptr, PS);
+    rc |= h->d_p_angle.fill(nullptr, PS); rc |= h->d_p_color.fill(nullptr, PS * 3);
   }
-  rc |= upload(&h->d_pool_base, pool_base_host, N);
-  rc |= upload(&h->d_pool_len, pool_len_host, N);
-  rc |= upload(&h->d_sampler, spec, 1);
+  rc |= h->d_pool_base.fill(pool_base_host, N);
+  rc |= h->d_pool_len.fill(pool_len_host, N);
+  rc |= h->d_sampler.fill(spec, 1);
   if (rc) return SWB_ERR_HIP;
   h->pool_entries = P;
-  swb_params& p = h->p;
-  p.p_n = h->d_p_n; p.p_x = h->d_p_x; p.p_y = h->d_p_y; p.p_xv = h->d_p_xv; p.p_yv = h->d_p_yv;
-  p.p_scale = h->d_p_scale; p.p_ca = h->d_p_ca; p.p_sa = h->d_p_sa; p.p_shape = h->d_p_shape; p.p_rgb = h->d_p_rgb;
-  p.p_label = h->d_p_label; p.pool_base = h->d_pool_base; p.pool_len = h->d_pool_len;
-  p.p_angle = h->d_p_angle; p.p_color = h->d_p_color;
-  swb_sampler_args a{h->d_sampler, P, S, T, seed, first_entry, nullptr, nullptr, nullptr, N, h->d_p_n, h->d_p_x, h->d_p_y, h->d_p_xv, h->d_p_yv, h->d_p_scale,
-                     h->d_p_ca, h->d_p_sa, h->d_p_angle, h->d_p_color, h->d_p_shape, h->d_p_rgb, h->d_p_label, h->d_p_attr};
+  bind_pool(h, true, true);
+  const swb_sampler_args a = sampler_args(h, seed, first_entry, false);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((P + 255) / 256), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
@@ -1133,11 +1128,8 @@ int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* s
   if (!h->pool_uniform)
     return fail(SWB_ERR_STATE, "swb_resample_pool needs the env-major layout pool_base[n] = n * pool_len, equal pool_len");
   HIP_TRY(hipSetDevice(h->device));
-  const int P = h->pool_entries, S = h->p.S, T = h->p.n_tasks, N = h->p.N;
-  swb_sampler_args a{h->d_sampler, P, S, T, seed, first_entry, h->d_entry, h->d_pool_base, h->d_pool_len, N, h->d_p_n,
-                     h->d_p_x, h->d_p_y, h->d_p_xv, h->d_p_yv, h->d_p_scale, h->d_p_ca, h->d_p_sa, h->d_p_angle,
-                     h->d_p_color, h->d_p_shape, h->d_p_rgb, h->d_p_label, h->d_p_attr};
-  hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  const swb_sampler_args a = sampler_args(h, seed, first_entry, true);
+  hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((h->pool_entries + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SWB_OK;
 }
@@ -1226,23 +1218,15 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
   const hipStream_t st = (hipStream_t)stream;
   const size_t NV = (size_t)p.N * M, S = (size_t)p.S;
   const size_t bytes = NV * (16 * S + 32);
-  if (bytes > h->rollout_bytes || K > h->rollout_steps) {   // (the one blocking case: an earlier rollout may still use the old scratch)
+  if (bytes > h->d_rollout.count || (size_t)K > h->d_rollout_steps.count) {   // (the one blocking case: an earlier rollout may still use the old scratch)
     HIP_TRY(hipStreamSynchronize(st));
-    if (bytes > h->rollout_bytes) {
-      if (h->d_rollout) { (void)hipFree(h->d_rollout); h->d_rollout = nullptr; h->rollout_bytes = 0; }
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rollout), bytes));
-      h->rollout_bytes = bytes;
-    }
-    if (K > h->rollout_steps) {
-      if (h->d_rollout_steps) { (void)hipFree(h->d_rollout_steps); h->d_rollout_steps = nullptr; h->rollout_steps = 0; }
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rollout_steps), (size_t)K * sizeof(swb_params)));
-      h->rollout_steps = K;
-    }
+    if (bytes > h->d_rollout.count && h->d_rollout.fill(nullptr, bytes)) return SWB_ERR_HIP;
+    if ((size_t)K > h->d_rollout_steps.count && h->d_rollout_steps.fill(nullptr, K)) return SWB_ERR_HIP;
   }
   swb_rollout_args a;
   memset(&a, 0, sizeof(a));
   a.M = M; a.K = K;
-  a.x = reinterpret_cast<double*>(h->d_rollout);
+  a.x = reinterpret_cast<double*>(h->d_rollout.ptr);
   a.y = a.x + NV * S;
   a.nspr = reinterpret_cast<int32_t*>(a.y + NV * S);
   a.entry = a.nspr + NV; a.step_count = a.entry + NV; a.episode = a.step_count + NV;
@@ -1271,7 +1255,8 @@ int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream) {
   }
   if (run_cap_out) *run_cap_out = h->p.run_cap;
   if (h->lists_trimmed || getenv("SWB_RUN_CAP") || getenv("SWB_NO_TRIM")) return SWB_OK;   // (done already / a test pinned the capacity)
-  if (!h->d_runs && h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1) return SWB_OK;      // (the cover kernel paints the frame: no lists at all)
+  // (the cover kernel paints the frame: no lists at all -- nor, before its first launch, on a handle SWB_NO_PAINT_IN_COVER keeps from it)
+  if (!h->d_runs && paints_in_cover(h, pick_variant(h->p.Wc), false)) return SWB_OK;
   if (!h->d_runs || !h->lists_valid) return fail(SWB_ERR_STATE, "swb_trim_run_lists: the last launch listed no runs (step or render first)");
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   // the longest list of the last launch: its end is in the header (no list has left its fixed part: it holds any scene)
@@ -1323,7 +1308,7 @@ int swb_get_env_state(swb_handle h, int32_t env, int32_t* out5, void* stream) {
   HIP_TRY(hipSetDevice(h->device));
   // (the N = 1 drop-in asks for this several times per step: one gather kernel and ONE 20-byte copy, stream-ordered behind
   // the steps, instead of a stream synchronisation and five 4-byte copies)
-  if (!h->d_env_state && upload(&h->d_env_state, (const int32_t*)nullptr, 8)) return SWB_ERR_HIP;
+  if (!h->d_env_state && h->d_env_state.fill(nullptr, 8)) return SWB_ERR_HIP;
   hipLaunchKernelGGL(swb_env_state_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, h->p, env, h->d_env_state);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out5, h->d_env_state, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -1406,13 +1391,13 @@ int ov_allocate(swb_engine* h) {
   if (h->d_ov_flag) return 0;
   const size_t N = h->p.N, NS = N * h->p.S, T = h->p.n_tasks;
   int rc = 0;
-  rc |= upload<int32_t>(&h->d_ov_shape, nullptr, NS);
-  rc |= upload<double>(&h->d_ov_scale, nullptr, NS);
-  rc |= upload<double>(&h->d_ov_angle, nullptr, NS);
-  rc |= upload<int8_t>(&h->d_ov_label, nullptr, NS * T);
-  rc |= upload<double>(&h->d_ov_cpath, nullptr, NS * SWB_MAX_SHAPE_VERTS * 2);
-  if (h->keyed) rc |= upload<int8_t>(&h->d_ov_cell_label, nullptr, NS * T * SWB_MAX_CELLS);
-  rc |= upload<uint8_t>(&h->d_ov_flag, nullptr, N);       // last: its presence switches the engine to the OV kernels
+  rc |= h->d_ov_shape.fill(nullptr, NS);
+  rc |= h->d_ov_scale.fill(nullptr, NS);
+  rc |= h->d_ov_angle.fill(nullptr, NS);
+  rc |= h->d_ov_label.fill(nullptr, NS * T);
+  rc |= h->d_ov_cpath.fill(nullptr, NS * SWB_MAX_SHAPE_VERTS * 2);
+  if (h->keyed) rc |= h->d_ov_cell_label.fill(nullptr, NS * T * SWB_MAX_CELLS);
+  rc |= h->d_ov_flag.fill(nullptr, N);       // last: its presence switches the engine to the OV kernels
   if (rc) return SWB_ERR_HIP;
   swb_params& p = h->p;
   p.ov_flag = h->d_ov_flag; p.ov_shape = h->d_ov_shape; p.ov_scale = h->d_ov_scale; p.ov_angle = h->d_ov_angle;
@@ -1614,9 +1599,9 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
   out->waves_per_simd = SWB_COVER_WAVES(v->nw);
   out->resample_waves_per_simd = SWB_RS_WAVES_PER_SIMD;
   out->n_bands = h->p.nbands ? h->p.nbands : h->nbands;
-  out->n_column_groups = (h->p.Wo + 63) / 64;
+  out->n_column_groups = h->p.ncg;
   out->run_cap = h->p.run_cap;
-  out->paint_in_cover = (h->p.AA == 1 && (h->p.Wo + 63) / 64 == 1 && !h->no_paint_in_cover) ? 1 : 0;
+  out->paint_in_cover = paints_in_cover(h, v) ? 1 : 0;
   out->arena_units = h->d_runs ? h->p.arena_units : 0;
   out->large_frames = 0;
   out->many_sprites = 0;

@@ -23,6 +23,10 @@ if os.environ.get('SWB_EMU_STATS'):
 LIB = os.path.join(OUT_DIR, 'libswb_emu.so')
 CLANG = '/opt/rocm/lib/llvm/bin/clang++'
 SOURCES = ('swb.hip', 'swb_wide.hip', 'swb_kernels.hip.inc', 'swb_pow.hip.inc', 'swb_pow_tables.inc', 'swb_sampler.hip.inc')
+# compile flags of every unit (tests/test_host_lifecycle.py builds the same units once more, with a sanitizer)
+FLAGS = ['-x', 'c++', '-std=c++17', '-O1', '-g', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-fno-strict-aliasing',
+         '-I', os.path.join(HERE, 'shim'), '-DSWB_BUILD_ID="emulated"', '-Wno-unused-value', '-Wno-ignored-attributes',
+         '-Wno-unknown-attributes']
 
 
 def _rewrite(text, name):
@@ -136,9 +140,7 @@ def _build_locked(force):
     with open(os.path.join(src_dir, name), 'w') as f:
       f.write(text)
   # the kernels include "../../include/swb.h" relative to csrc/: OUT_DIR/src/csrc -> OUT_DIR/include
-  flags = ['-x', 'c++', '-std=c++17', '-O1', '-g', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-fno-strict-aliasing',
-           '-I', os.path.join(HERE, 'shim'), '-DSWB_BUILD_ID="emulated"', '-Wno-unused-value', '-Wno-ignored-attributes',
-           '-Wno-unknown-attributes']
+  flags = FLAGS
   objs, procs = [], []
   for unit in ('swb.hip', 'swb_wide.hip'):
     obj = os.path.join(OUT_DIR, unit + '.o')
