@@ -203,3 +203,57 @@ class SwbSampler(C.Structure):
       ('deg_sin', C.c_double * 360),
       ('groups', SwbSpriteGroup * SWB_MAX_GROUPS),
   ]
+
+
+_P, _h, _p, _i32, _u64, _f64 = C.POINTER, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_double
+
+# Every function include/swb.h declares: name -> (restype, or None for the int status; argtypes).  `_h` is the handle or
+# a stream, `_p` a caller's host or device array.  The one table every loader of the C ABI applies (`declare`).
+PROTOTYPES = {
+    'swb_last_error': (C.c_char_p, []),
+    'swb_version': (None, []),
+    'swb_create': (None, [_P(SwbConfig), C.c_int, _P(C.c_void_p)]),
+    'swb_destroy': (None, [_h]),
+    'swb_upload_shapes': (None, [_h, _p, _p, _i32]),
+    'swb_upload_resample': (None, [_h, _i32, _i32, _i32, _p, _p]),
+    'swb_set_pool': (None, [_h, _P(SwbPool)]),
+    'swb_sample_pool': (None, [_h, _P(SwbSampler), _i32, _p, _p, _u64, _u64, _h]),
+    'swb_resample_pool': (None, [_h, _u64, _u64, _h]),
+    'swb_get_pool': (None, [_h, _P(SwbPool)]),
+    'swb_reset_all': (None, [_h, _h]),
+    'swb_step': (None, [_h, _p, _P(SwbOutputs), _h]),
+    'swb_render': (None, [_h, _p, _h]),
+    'swb_evaluate': (None, [_h, _p, _h]),
+    'swb_rollout': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _h]),
+    'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
+    'swb_factors': (None, [_h, _p, _h]),
+    'swb_get_env_state': (None, [_h, _i32, _p, _h]),
+    'swb_get_sprite_types': (None, [_h, _i32, _i32, _P(_i32), _h]),
+    'swb_get_state': (None, [_h, _P(SwbState), _h]),
+    'swb_set_positions': (None, [_h, _p, _p, _h]),
+    'swb_set_sprite_attr': (None, [_h, _i32, _i32, _i32, _f64, _p, _p, _h]),
+    'swb_set_sprite_cell_labels': (None, [_h, _i32, _i32, _p, _h]),
+    'swb_get_sprite': (None, [_h, _i32, _i32, _p, _p, _p, _p, _p, _h]),
+    'swb_sprite_path_op': (None, [_i32, _f64, _f64, _i32, _p, _p]),
+    'swb_variant': (None, [_h, _P(SwbVariantInfo)]),
+    'swb_build_id': (C.c_char_p, []),
+    'swb_timing_enable': (None, [_h, _i32]),
+    'swb_step_time_ms': (None, [_h, _P(_f64), _P(C.c_int64)]),
+    'swb_kernel_times_ms': (None, [_h, _P(_f64), _P(_f64), _P(C.c_int64)]),
+}
+
+
+def declare(lib, tolerate_missing=False):
+  """Applies PROTOTYPES to a loaded library and returns it.  A symbol the library lacks is an AttributeError, unless
+  `tolerate_missing`: an alternative build or source copy of an older revision, whose callers ask `hasattr` first."""
+  for name, (restype, argtypes) in PROTOTYPES.items():
+    if tolerate_missing and not hasattr(lib, name):
+      continue
+    fn = getattr(lib, name)
+    fn.argtypes = argtypes
+    if restype is not None:
+      fn.restype = restype
+  return lib
+
+
+del _P, _h, _p, _i32, _u64, _f64

@@ -17,7 +17,7 @@ from spriteworld_amd import lowering
 from spriteworld_amd import renderers
 from spriteworld_amd import synthetic
 from spriteworld_amd import tasks
-from tests import _util
+from tests import _parity
 
 CASES = ('square', 'square_bg', 'square_wide', 'stack5')
 
@@ -50,8 +50,8 @@ def build(case, n_envs, aa, episodes_per_env=2, seed=0):
 
 
 def run(make_engine, case, n_envs, steps, aa, seed=0):
-  """Steps `make_engine(cfg, pool)` and the oracle side by side: positions, rewards, step types, discounts and flags bit for bit,
-  frames +-0."""
+  """Steps `make_engine(cfg, pool)` and the oracle side by side: the bar of tests/_parity.py (state, rewards, step types,
+  discounts and flags bit for bit, frames +-0)."""
   from oracle import oracle
   cfg, pool, sample = build(case, n_envs, aa, seed=seed)
   ora, eng = oracle.Engine(cfg, pool), make_engine(cfg, pool)
@@ -60,19 +60,5 @@ def run(make_engine, case, n_envs, steps, aa, seed=0):
     a = sample(rng)
     want = ora.step(a)
     eng.step(a)
-    got = eng.outputs_host()
-    st_o, st_g = ora.state(), eng.state()
-    what = '%s, %d environments, anti_aliasing %d, step %d' % (case, n_envs, aa, t)
-    assert not got['error'].any(), (what, np.flatnonzero(got['error'])[:8])
-    np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg=what)
-    np.testing.assert_array_equal(_util.bits64(st_g['x']), _util.bits64(st_o['x']), err_msg=what)
-    np.testing.assert_array_equal(_util.bits64(st_g['y']), _util.bits64(st_o['y']), err_msg=what)
-    np.testing.assert_array_equal(got['success'], want['success'], err_msg=what)
-    np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32), err_msg=what)
-    gr, wr = got['reward'], want['reward']
-    assert np.array_equal(np.isnan(gr), np.isnan(wr)), what
-    ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(_util.bits64(gr[ok]), _util.bits64(wr[ok]), err_msg=what)
-    diff = got['obs'].astype(np.int16) - want['obs'].astype(np.int16)
-    assert not diff.any(), (what, int(np.abs(diff).max()), int((diff != 0).sum()), np.argwhere(diff != 0)[:5].tolist())
+    _parity.compare(t, ora, eng, want, eng.outputs_host(), what='%s, %d environments, anti_aliasing %d' % (case, n_envs, aa))
   eng.close()

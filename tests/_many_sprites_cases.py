@@ -5,54 +5,17 @@ import numpy as np
 
 from spriteworld_amd import _abi
 from spriteworld_amd import workloads
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+from tests import _parity
 
 
 def _np(a):
   return a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)
 
 
-def compare(t, ora, eng, want, got, frames=True):
-  """One step's outputs and the state after it; returns the engine's state."""
-  st_o, st_g = ora.state(), eng.state()
-  assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-  np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-  for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-    np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-  np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-  np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32), err_msg='discount t=%d' % t)
-  gr, wr = got['reward'], want['reward']
-  assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-  ok = ~np.isnan(wr)
-  np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-  if frames:
-    diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-    assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t, np.argwhere(diff > 0)[:5].tolist())
-  return st_g
-
-
 def run_parity(make_engine, name, n_envs, steps, aa, seed=0, episodes_per_env=2, frame_every=1):
   """Steps `name` on the engine and the oracle; returns (FIRST steps seen, the most sprites an episode had)."""
-  from oracle import oracle
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=episodes_per_env, seed=seed, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), make_engine(cfg, pool)
-  assert eng.variant()['many_sprites'] == 1 and eng.variant()['large_frames'] == 1
-  rng = np.random.default_rng(seed + 100)
-  firsts, most = 0, 0
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    st = compare(t, ora, eng, want, eng.outputs_host(), frames=(t % frame_every == 0))
-    firsts += int((want['step_type'] == 0).sum())
-    most = max(most, int(st['n_sprites'].max()))
-  eng.close()
-  return firsts, most
+  return _parity.run(make_engine, name, n_envs, steps, aa, seed=seed, episodes_per_env=episodes_per_env, frame_every=frame_every,
+                     expect={'many_sprites': 1, 'large_frames': 1})
 
 
 def setters_case(make_engine, name='ragged_s64', n_envs=4, steps=5, aa=3, seed=1, built=None):
@@ -70,7 +33,7 @@ def setters_case(make_engine, name='ragged_s64', n_envs=4, steps=5, aa=3, seed=1
     a = sample(rng)
     want = ora.step(a)
     eng.step(a)
-    st = compare(t, ora, eng, want, eng.outputs_host())
+    st = _parity.compare(t, ora, eng, want, eng.outputs_host())
     live = np.flatnonzero(st['reset_next'] == 0)
     for env in live[:3]:
       k = int(srng.randint(16, st['n_sprites'][env]))
@@ -82,7 +45,7 @@ def setters_case(make_engine, name='ragged_s64', n_envs=4, steps=5, aa=3, seed=1
       applied += 1
       so, sg = ora.get_sprite(int(env), k), eng.get_sprite(int(env), k)
       assert (so['shape'], so['angle'], so['scale']) == (sg['shape'], sg['angle'], sg['scale'])
-      assert np.array_equal(_bits(so['path']), _bits(sg['path'])), (t, env, k, attr, value)
+      assert np.array_equal(_parity.bits(so['path']), _parity.bits(sg['path'])), (t, env, k, attr, value)
     np.testing.assert_array_equal(_np(eng.render()), ora.render(), err_msg='render t=%d' % t)
   assert applied > 0
   eng.close()
@@ -100,7 +63,7 @@ def render_and_evaluate_case(make_engine, name='cluster_s40', n_envs=3, aa=5, se
     a = sample(rng)
     want = ora.step(a)
     eng.step(a)
-    compare(t, ora, eng, want, eng.outputs_host())
+    _parity.compare(t, ora, eng, want, eng.outputs_host())
   frame = eng.outputs_host()['obs'].copy()
   before = eng.state()
   np.testing.assert_array_equal(_np(eng.render()), frame)
@@ -234,7 +197,7 @@ def scene_claims(cfg, pool):
 
 
 def run_scene(make_engine, built, steps, many=True, check_claims=True, want_most=17, want_reset=True):
-  """Steps a (cfg, pool, sample) triple on the engine and the oracle, every step to the bar of compare(); asserts what the
+  """Steps a (cfg, pool, sample) triple on the engine and the oracle, every step to the bar of _parity.compare(); asserts what the
   case claims to exercise: the kernel path, more than 16 sprites seen, a reset seen, sprites moved by a hit (SelectMove /
   DragAndDrop), sprites across row blocks, of a few pixels and over each canvas edge."""
   from oracle import oracle
@@ -255,7 +218,7 @@ def run_scene(make_engine, built, steps, many=True, check_claims=True, want_most
     a = sample(rng, st)
     want = ora.step(a)
     eng.step(a)
-    new = compare(t, ora, eng, want, eng.outputs_host())
+    new = _parity.compare(t, ora, eng, want, eng.outputs_host())
     if st is not None:
       mid = want['step_type'] != 0                  # (a FIRST step installs a new episode: not a move)
       moved += int(((new['x'][mid] != st['x'][mid]) | (new['y'][mid] != st['y'][mid])).any(axis=1).sum())
@@ -344,21 +307,21 @@ def vertex_budget_case(make_engine, error, image_size, aa, n_envs=2):
     assert eng.variant()['many_sprites'] == 1 and eng.variant()['large_frames'] == 1
     rng = np.random.default_rng(3)
     a = sample(rng)
-    compare(0, ora, eng, ora.step(a), (eng.step(a), eng.outputs_host())[1])
+    _parity.compare(0, ora, eng, ora.step(a), (eng.step(a), eng.outputs_host())[1])
     # sprite 0 of environment 0 (an episode of B vertices) has one of the small shapes: as a 64-gon the scene exceeds B
     assert idx[0] != circle and eng.state()['n_sprites'][0] == len(idx)
     before = eng.get_sprite(0, 0)
     with pytest.raises(error, match='swb_set_sprite_attr: a scene of [0-9]+ polygon vertices exceeds the vertex budget'):
       eng.set_sprite_attr(0, 0, _abi.ATTR_SHAPE, float(circle))
     after = eng.get_sprite(0, 0)
-    assert after['shape'] == before['shape'] and np.array_equal(_bits(after['path']), _bits(before['path']))
+    assert after['shape'] == before['shape'] and np.array_equal(_parity.bits(after['path']), _parity.bits(before['path']))
     np.testing.assert_array_equal(_np(eng.render()), ora.render())
     # ... and one that keeps the scene at B vertices (an angle) is accepted: the scene renders at its budget through the setters' tables
     ora.set_sprite_attr(0, 0, _abi.ATTR_ANGLE, 33.0)
     eng.set_sprite_attr(0, 0, _abi.ATTR_ANGLE, 33.0)
     np.testing.assert_array_equal(_np(eng.render()), ora.render())
     a = sample(rng)
-    compare(1, ora, eng, ora.step(a), (eng.step(a), eng.outputs_host())[1])
+    _parity.compare(1, ora, eng, ora.step(a), (eng.step(a), eng.outputs_host())[1])
     eng.close()
   return B
 
@@ -390,7 +353,7 @@ def factors_case(make_engine, n_envs=3):
   assert f.shape == (n_envs, 40, 10)
   want = _want_factors(st, pool, shape, angle, scale)
   for c, name in enumerate(FACTOR_COLUMNS):
-    np.testing.assert_array_equal(_bits(f[:, :, c]), _bits(want[:, :, c]), err_msg=name)
+    np.testing.assert_array_equal(_parity.bits(f[:, :, c]), _parity.bits(want[:, :, c]), err_msg=name)
   for env, k in ((0, 16), (1, 39), (n_envs - 1, 27)):
     assert eng.sprite_types(env, k) == (bool(pool.attr_f32[e[env], k] & 1), bool(pool.attr_f32[e[env], k] & 2)), (env, k)
   # setters on sprites beyond 16 of environment 1: its factors come from the setters' tables, the others' from the pool
@@ -401,7 +364,7 @@ def factors_case(make_engine, n_envs=3):
   f = _np(eng.factors())
   want = _want_factors(eng.state(), pool, shape, angle, scale)
   for c, name in enumerate(FACTOR_COLUMNS):
-    np.testing.assert_array_equal(_bits(f[:, :, c]), _bits(want[:, :, c]), err_msg=name + ' after setters')
+    np.testing.assert_array_equal(_parity.bits(f[:, :, c]), _parity.bits(want[:, :, c]), err_msg=name + ' after setters')
   assert eng.sprite_types(1, 39) == (bool(pool.attr_f32[e[1], 39] & 1), bool(pool.attr_f32[e[1], 39] & 2))
   eng.close()
 
@@ -446,7 +409,7 @@ def device_sampler_case(total, num_envs=4, episodes_per_env=3):
     a = rng.uniform(0, 1, size=(num_envs, 4))
     want_o = ora.step(a)
     env.engine.step(a)
-    compare(t, ora, env.engine, want_o, env.engine.outputs_host())
+    _parity.compare(t, ora, env.engine, want_o, env.engine.outputs_host())
   env.close()
 
 

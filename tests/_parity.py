@@ -1,0 +1,64 @@
+"""The bar every engine-against-oracle test holds a step to (TEST INFRASTRUCTURE ONLY): sprite positions, the state arrays,
+step types, success flags, discounts and rewards bit-exact (rewards with the same NaN pattern), frames +-0, no error flag.
+The emulated suites and the `-m gpu` suites call the same three functions with an engine factory of their own."""
+import numpy as np
+
+from spriteworld_amd import workloads
+
+
+def bits(a):
+  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what=''):
+  """One step's outputs (`want`: the oracle's, `got`: the engine's, on the host) and the state after it; returns the
+  engine's state.  reward_ulp: a bound in units of the last place in place of bit-equal rewards; `what`: the caller's case, put
+  in front of the step in every message."""
+  at = '%st=%d' % (what and what + ', ', t)
+  st_o, st_g = ora.state(), eng.state()
+  assert not got['error'].any(), ('error flags ' + at, np.flatnonzero(got['error'])[:8])
+  np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type ' + at)
+  np.testing.assert_array_equal(bits(st_g['x']), bits(st_o['x']), err_msg='x ' + at)
+  np.testing.assert_array_equal(bits(st_g['y']), bits(st_o['y']), err_msg='y ' + at)
+  for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
+    np.testing.assert_array_equal(st_g[k], st_o[k], err_msg=k + ' ' + at)
+  np.testing.assert_array_equal(got['success'], want['success'], err_msg='success ' + at)
+  np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32), err_msg='discount ' + at)
+  assert_rewards_equal(got['reward'], want['reward'], at, reward_ulp)
+  if frames:
+    diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
+    assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), at, np.argwhere(diff > 0)[:5].tolist())
+  return st_g
+
+
+def assert_rewards_equal(gr, wr, what, reward_ulp=0):
+  """NaN where the oracle has NaN (a FIRST step has no reward), bit-equal -- or within `reward_ulp` -- elsewhere."""
+  assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern ' + what
+  ok = ~np.isnan(wr)
+  if reward_ulp == 0:
+    np.testing.assert_array_equal(bits(gr[ok]), bits(wr[ok]), err_msg='reward ' + what)
+  elif ok.any():
+    d = np.abs(bits(gr[ok]).astype(np.int64) - bits(wr[ok]).astype(np.int64))
+    assert d.max() <= reward_ulp, ('reward ulp', d.max(), what)
+
+
+def run(make_engine, name, n_envs, steps, aa, seed=0, episodes_per_env=3, frame_every=1, expect=None):
+  """Steps workload `name` on `make_engine(cfg, pool)` and the oracle, every step through compare(); `expect`: entries of
+  variant() that must hold (large_frames, many_sprites).  Returns (FIRST steps seen, the most sprites an episode had)."""
+  from oracle import oracle
+  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=episodes_per_env, seed=seed, anti_aliasing=aa)
+  ora, eng = oracle.Engine(cfg, pool), make_engine(cfg, pool)
+  v = eng.variant()
+  for k, value in (expect or {}).items():
+    assert v[k] == value, (k, v)
+  rng = np.random.default_rng(seed + 100)
+  firsts, most = 0, 0
+  for t in range(steps):
+    a = sample(rng)
+    want = ora.step(a)
+    eng.step(a)
+    st = compare(t, ora, eng, want, eng.outputs_host(), frames=(t % frame_every == 0))
+    firsts += int((want['step_type'] == 0).sum())
+    most = max(most, int(st['n_sprites'].max()))
+  eng.close()
+  return firsts, most

@@ -10,11 +10,11 @@ import numpy as np
 
 from spriteworld_amd import _abi
 from spriteworld_amd import workloads
-from tests import _many_sprites_cases as ms
+from tests import _parity
 
 N_ENVS, M, T0, K, MAX_LEN = 16, 3, 3, 6, 4
 PARITY = ('goal_s5', 'cluster_s5', 'sorting_s4', 'embodied_s12', 'f64_drag', 'cluster_s5_f32a', 'pos:goal_x_lt_half', 'ragged_s64')
-_bits = ms._bits
+_bits = _parity.bits
 
 
 def built(name, n_envs=N_ENVS, seed=0, max_len=MAX_LEN, episodes_per_env=2):
@@ -44,9 +44,9 @@ def candidates(cfg, sample, rng, st, n_cand, n_steps):
 
 
 def rollout(eng, actions, positions=True):
-  """swb_rollout through the engine under test -> dict of numpy arrays in the C layout.  engine.Engine has the method; the
-  emulated engine (numpy "device" buffers) is called through its library handle."""
-  if hasattr(eng, 'rollout'):
+  """swb_rollout through the engine under test -> dict of numpy arrays in the C layout: Engine.rollout on the device; on the
+  emulated library (its buffers are host memory) through the handle, into outputs filled with garbage first."""
+  if eng.device.type != 'cpu':
     return {k: v.cpu().numpy() for k, v in eng.rollout(actions, positions=positions).items()}
   return rollout_through_library(eng, actions, positions)
 
@@ -73,14 +73,11 @@ def raw_call(eng, actions, n_cand, n_steps, res=None):
   """(status, message) of swb_rollout called on the engine's handle as given: `actions` a numpy array, a device tensor or
   None (NULL), `res` a dict of numpy arrays / tensors for the output struct."""
   lib = eng.lib
-  lib.swb_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_abi.SwbRolloutOutputs), C.c_void_p]
-  lib.swb_last_error.restype = C.c_char_p
   addr = lambda t: None if t is None else (t.data_ptr() if hasattr(t, 'data_ptr') else t.ctypes.data)
   o = _abi.SwbRolloutOutputs()
   for k, t in (res or {}).items():
     setattr(o, k, addr(t))
-  stream = eng._stream() if hasattr(eng, '_stream') else None
-  rc = lib.swb_rollout(eng._h, addr(actions), int(n_cand), int(n_steps), C.byref(o), stream)
+  rc = lib.swb_rollout(eng._h, addr(actions), int(n_cand), int(n_steps), C.byref(o), eng._stream())
   return rc, lib.swb_last_error().decode() if rc else ''
 
 
@@ -112,10 +109,7 @@ def assert_equal(got, want, what=''):
   np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type ' + what)
   np.testing.assert_array_equal(got['success'], want['success'], err_msg='success ' + what)
   np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32), err_msg='discount ' + what)
-  gr, wr = got['reward'], want['reward']
-  assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern ' + what
-  ok = ~np.isnan(wr)
-  np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward ' + what)
+  _parity.assert_rewards_equal(got['reward'], want['reward'], what)
   np.testing.assert_array_equal(got['error'], want['error'], err_msg='error ' + what)
   if 'x' in got:
     np.testing.assert_array_equal(_bits(got['x']), _bits(want['x']), err_msg='x ' + what)
@@ -180,7 +174,7 @@ def live_state_case(make_engine, name='goal_s5'):
     want = ora.step(a)
     eng.step(a)
     out = eng.outputs_host()
-    ms.compare(k, ora, eng, want, out)
+    _parity.compare(k, ora, eng, want, out)
     np.testing.assert_array_equal(out['step_type'], got['step_type'][k, :, 0])
     np.testing.assert_array_equal(out['success'], got['success'][k, :, 0])
     np.testing.assert_array_equal(out['discount'].view(np.uint32), got['discount'][k, :, 0].view(np.uint32))
@@ -193,11 +187,8 @@ def live_state_case(make_engine, name='goal_s5'):
 
 
 def _set_error(eng, values):
-  if hasattr(eng.error, 'copy_'):
-    import torch
-    eng.error.copy_(torch.as_tensor(values))
-  else:
-    eng.error[:] = values
+  import torch
+  eng.error.copy_(torch.as_tensor(values))
 
 
 EDGES = ('one_step', 'sixty_four_candidates', 'forty_steps', 'after_reset_all', 'scratch_grows')
@@ -241,10 +232,8 @@ def refusals_case(make_engine, name='goal_s5'):
   """4. K = 0, M = 0 and NULL actions: SWB_ERR_INVALID; after a sprite setter: SWB_ERR_STATE; each with a message."""
   cfg, pool, sample, eng, live, rng = started(make_engine, name)
   acts = candidates(cfg, sample, rng, None, M, K)
-  dev = acts
-  if hasattr(eng, 'rollout'):                   # (a device buffer for the real engine)
-    import torch
-    dev = torch.as_tensor(acts, device=eng.device)
+  import torch
+  dev = torch.as_tensor(acts, device=eng.device)      # (a device buffer for the real engine)
   for n_cand, n_steps, a, what in ((M, 0, dev, 'M and K must be positive'), (0, K, dev, 'M and K must be positive'),
                                    (M, -1, dev, 'M and K must be positive'), (M, K, None, 'actions is NULL')):
     rc, msg = raw_call(eng, a, n_cand, n_steps)

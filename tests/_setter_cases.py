@@ -6,35 +6,19 @@ import numpy as np
 import pytest
 
 from spriteworld_amd import _abi, shapes, workloads
+from tests import _parity
 
 
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _compare(t, ora, eng, want, got):
-  st_o, st_g = ora.state(), eng.state()
-  assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-  np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-  for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-    np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-  np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-  gr, wr = got['reward'], want['reward']
-  assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-  ok = ~np.isnan(wr)
-  np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-  diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-  assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t, np.argwhere(diff > 0)[:5].tolist())
-  return st_o
-
-
-def run_parity(make_engine, name, n_envs, steps, aa, seed=0, calls_per_step=6):
+def run_parity(make_engine, name, n_envs, steps, aa, seed=0, calls_per_step=6, expect=None, render_every=3):
+  """`expect`: entries of variant() that must hold (as tests/_parity.run); observation() is compared with the oracle's after
+  the setters of every `render_every`-th step."""
   from oracle import oracle
   cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=seed, anti_aliasing=aa)
   ora = oracle.Engine(cfg, pool)
   eng = make_engine(cfg, pool)
+  v = eng.variant()
+  for k, value in (expect or {}).items():
+    assert v[k] == value, (k, v)
   rng = np.random.default_rng(seed + 100)
   srng = np.random.RandomState(seed + 5)
   n_shapes = len(shapes.SHAPES)
@@ -43,7 +27,7 @@ def run_parity(make_engine, name, n_envs, steps, aa, seed=0, calls_per_step=6):
     a = sample(rng)
     want = ora.step(a)
     eng.step(a)
-    st = _compare(t, ora, eng, want, eng.outputs_host())
+    st = _parity.compare(t, ora, eng, want, eng.outputs_host())
     # setters on live sprites of random environments (never one whose episode just ended)
     live = np.flatnonzero((st['reset_next'] == 0) & (st['n_sprites'] > 0))
     for _ in range(calls_per_step if len(live) else 0):
@@ -58,12 +42,16 @@ def run_parity(make_engine, name, n_envs, steps, aa, seed=0, calls_per_step=6):
       applied += 1
       so, sg = ora.get_sprite(env, k), eng.get_sprite(env, k)
       assert (so['shape'], so['angle'], so['scale']) == (sg['shape'], sg['angle'], sg['scale'])
-      assert np.array_equal(_bits(so['path']), _bits(sg['path'])), (t, env, k, attr, value)
+      assert np.array_equal(_parity.bits(so['path']), _parity.bits(sg['path'])), (t, env, k, attr, value)
     # observation() between steps shows the modified sprites at once
-    if t % 3 == 0:
+    if t % render_every == 0:
       np.testing.assert_array_equal(eng.render().cpu().numpy(), ora.render(), err_msg='render t=%d' % t)
   assert applied > 0
-  assert eng.variant()['kernel'].startswith(('swb_resample_kernel', 'swb_fill_kernel', 'none'))
+  v = eng.variant()      # the kernel's name agrees with the render path the handle reports
+  if v.get('large_frames') == 1:
+    assert v['kernel'].startswith('swb_lf_raster_kernel'), v
+  else:
+    assert v['kernel'].startswith(('swb_resample_kernel', 'swb_fill_kernel', 'none')), v
   eng.close()
 
 

@@ -15,11 +15,8 @@ import numpy as np
 import pytest
 
 from spriteworld_amd import workloads
+from tests import _parity
 from tests import _util
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _emu(cfg, pool):
@@ -27,37 +24,8 @@ def _emu(cfg, pool):
   return _emu_engine.EmuEngine(cfg, pool)
 
 
-def _emu_torch(cfg, pool):
-  from tests import _emu_engine
-  return _emu_engine.EmuTorchEngine(cfg, pool)
-
-
 def _run(name, n_envs, steps, aa, seed=0):
-  from oracle import oracle
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=seed, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), _emu(cfg, pool)
-  rng = np.random.default_rng(seed + 100)
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    got = eng.outputs_host()
-    st_o, st_g = ora.state(), eng.state()
-    assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-    np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-    for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-      np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-    np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-    np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32))
-    gr, wr = got['reward'], want['reward']
-    assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-    ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-    diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-    assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t, np.argwhere(diff > 0)[:5].tolist())
-  eng.close()
+  _parity.run(_emu, name, n_envs, steps, aa, seed=seed)
 
 
 # the workloads of tests/test_gpu_parity.py (every kernel variant, every task / action space / dtype), a few environments each
@@ -150,7 +118,7 @@ def test_emulated_cover_launches_in_cost_order(monkeypatch, name, n_envs, aa):
       continue
     got = eng.outputs_host()
     np.testing.assert_array_equal(got['step_type'], want['step_type'])
-    np.testing.assert_array_equal(_bits(eng.state()['x']), _bits(ora.state()['x']))
+    np.testing.assert_array_equal(_parity.bits(eng.state()['x']), _parity.bits(ora.state()['x']))
     assert np.array_equal(got['obs'], want['obs']), t
   eng.close()
 
@@ -328,12 +296,12 @@ def test_emulated_ov_kernels_sprite_setters(name, n_envs, steps, aa):
   """The scenarios of tests/test_gpu_setters.py on the emulated library: swb_set_sprite_attr's host arithmetic, the
   override arrays and the OV builds of the step kernel against the oracle's setters."""
   from tests import _setter_cases
-  _setter_cases.run_parity(_emu_torch, name, n_envs, steps, aa)
+  _setter_cases.run_parity(_emu, name, n_envs, steps, aa)
 
 
 def test_emulated_setters_factors_and_reset():
   from tests import _emu_engine, _setter_cases
-  _setter_cases.factors_and_reset_case(_emu_torch, _emu_engine.EmuError)
+  _setter_cases.factors_and_reset_case(_emu, _emu_engine.EmuError)
 
 
 def test_emulated_live_sprite_handles(monkeypatch):
@@ -474,7 +442,7 @@ def test_emulated_kernel_equals_the_unmodified_reference(module, mode):
     assert not out['error'][0], t
     assert int(ts.step_type) == int(out['step_type'][0]), t
     r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r)
+    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r)
     assert bool(ts.observation['success']) == bool(out['success'][0]), t
     assert np.array_equal(ts.observation['image'], out['obs'][0]), t
     st = eng.state()
@@ -554,7 +522,7 @@ def test_emulated_kernel_tasks_that_filter_on_position(name, f32):
     np.testing.assert_array_equal(got['success'], want['success'])
     assert np.array_equal(np.isnan(got['reward']), np.isnan(want['reward']))
     ok = ~np.isnan(want['reward'])
-    np.testing.assert_array_equal(_bits(got['reward'][ok]), _bits(want['reward'][ok]))
+    np.testing.assert_array_equal(_parity.bits(got['reward'][ok]), _parity.bits(want['reward'][ok]))
     sticky |= want['error']                            # (the engine's error flags are sticky; the oracle's are per step)
     np.testing.assert_array_equal(got['error'], sticky)
     np.testing.assert_array_equal(got['obs'], want['obs'])

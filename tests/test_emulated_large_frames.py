@@ -10,11 +10,8 @@ import numpy as np
 import pytest
 
 from spriteworld_amd import workloads
+from tests import _parity
 from tests import _util
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _emu(cfg, pool):
@@ -22,41 +19,9 @@ def _emu(cfg, pool):
   return _emu_engine.EmuEngine(cfg, pool)
 
 
-def _emu_torch(cfg, pool):
-  from tests import _emu_engine
-  return _emu_engine.EmuTorchEngine(cfg, pool)
-
-
-def _run(name, n_envs, steps, aa, seed=0, episodes_per_env=2):
-  from oracle import oracle
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=episodes_per_env, seed=seed, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), _emu(cfg, pool)
-  assert eng.variant()['large_frames'] == 1
-  rng = np.random.default_rng(seed + 100)
-  firsts = 0
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    got = eng.outputs_host()
-    st_o, st_g = ora.state(), eng.state()
-    assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-    np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-    for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-      np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-    np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-    np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32))
-    gr, wr = got['reward'], want['reward']
-    assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-    ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-    diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-    assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t, np.argwhere(diff > 0)[:5].tolist())
-    firsts += int((got['step_type'] == 0).sum())
-  eng.close()
-  return firsts
+def _run(name, n_envs, steps, aa, seed=0):
+  """-> the FIRST steps seen."""
+  return _parity.run(_emu, name, n_envs, steps, aa, seed=seed, episodes_per_env=2, expect={'large_frames': 1})[0]
 
 
 @pytest.mark.parametrize('geom,aa', [('96x96', 8), ('200x40', 4), ('320x32', 1)])
@@ -99,7 +64,7 @@ def test_emulated_large_frames_chunked(monkeypatch):
 def test_emulated_large_frames_sprite_setters(monkeypatch):
   from tests import _setter_cases
   monkeypatch.setenv('SWB_LARGE_FRAMES', '1')
-  _setter_cases.run_parity(_emu_torch, 'goal_s5', 3, 3, 3)
+  _setter_cases.run_parity(_emu, 'goal_s5', 3, 3, 3, expect={'large_frames': 1})
 
 
 def test_emulated_large_frames_render_and_trim():
@@ -110,11 +75,10 @@ def test_emulated_large_frames_render_and_trim():
   for _ in range(2):
     eng.step(sample(rng))
   frame = eng.outputs_host()['obs'].copy()
-  eng.obs[:] = 0x33
-  eng.render()
-  np.testing.assert_array_equal(eng.obs, frame)
+  eng.obs.fill_(0x33)
+  np.testing.assert_array_equal(eng.render().numpy(), frame)
   info = eng.variant()
-  assert info['large_frames'] == 1 and info['run_list_bytes'] == 0
+  assert info['large_frames'] == 1 and info['run_list_bytes'] == 0 and 'swb_lf_raster_kernel' in info['kernel']
   assert eng.trim() == 0
   eng.close()
 

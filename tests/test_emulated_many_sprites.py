@@ -18,11 +18,6 @@ def _emu(cfg, pool):
   return _emu_engine.EmuEngine(cfg, pool)
 
 
-def _emu_torch(cfg, pool):
-  from tests import _emu_engine
-  return _emu_engine.EmuTorchEngine(cfg, pool)
-
-
 @pytest.mark.parametrize('name,n_envs,steps,aa', [('ragged_s64', 4, 10, 5), ('ragged_s64', 3, 6, 1), ('ragged_s64_embodied', 3, 12, 5),
                                                    ('cluster_s40', 3, 6, 5), ('cluster_s40_f32a', 2, 4, 2), ('meta_s24_f64', 4, 10, 3)])
 def test_emulated_many_sprite_workloads(name, n_envs, steps, aa):
@@ -48,11 +43,11 @@ def test_emulated_many_sprite_path_forced(monkeypatch, name, n_envs, steps, aa):
 
 
 def test_emulated_setters_on_sprites_beyond_sixteen():
-  cases.setters_case(_emu_torch)
+  cases.setters_case(_emu)
 
 
 def test_emulated_render_and_evaluate():
-  cases.render_and_evaluate_case(_emu_torch)
+  cases.render_and_evaluate_case(_emu)
 
 
 def test_emulated_factors_and_sprite_types_beyond_sixteen():

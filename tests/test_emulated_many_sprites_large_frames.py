@@ -14,11 +14,6 @@ def _emu(cfg, pool):
   return _emu_engine.EmuEngine(cfg, pool)
 
 
-def _emu_torch(cfg, pool):
-  from tests import _emu_engine
-  return _emu_engine.EmuTorchEngine(cfg, pool)
-
-
 def _error():
   from tests import _emu_engine
   return _emu_engine.EmuError
@@ -48,11 +43,11 @@ def test_emulated_many_sprites_on_large_frames_chunked(monkeypatch):
 
 
 def test_emulated_setters_beyond_sixteen_on_a_large_canvas():
-  cases.setters_case(_emu_torch, steps=3, built=cases.scene(40, (176, 16), 4, 3, episodes_per_env=3, seed=1))      # (a 704 x 64 canvas)
+  cases.setters_case(_emu, steps=3, built=cases.scene(40, (176, 16), 4, 3, episodes_per_env=3, seed=1))      # (a 704 x 64 canvas)
 
 
 def test_emulated_render_and_evaluate_on_a_large_canvas():
-  cases.render_and_evaluate_case(_emu_torch, built=cases.scene(40, (176, 16), 4, 3, task='cluster', max_len=30, seed=2))
+  cases.render_and_evaluate_case(_emu, built=cases.scene(40, (176, 16), 4, 3, task='cluster', max_len=30, seed=2))
 
 
 # the accepted side of each limit, as strips: 4096 px wide, 1024 columns at AA 1, 4096 px tall, 4096 px tall at AA 16 (a

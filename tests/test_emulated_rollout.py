@@ -37,23 +37,20 @@ def test_emulated_rollout_refusals():
 
 
 def test_emulated_rollout_python_surface(monkeypatch):
-  """BatchedEnvironment.rollout, the Rollout tuple and episode_return() over the emulated library.  The engine patched in has
-  a rollout() of its own (numpy buffers), so the argument checks, dtype conversion and allocation of engine.Engine.rollout
-  are NOT run here: they run in tests/test_gpu_rollout.py (its surface case goes through the real method, with the permuted,
-  non-contiguous view BatchedEnvironment hands it)."""
-  import torch
+  """BatchedEnvironment.rollout, the Rollout tuple and episode_return() over the emulated library.  The engine patched in is
+  engine.Engine over that library, so the argument checks, dtype conversion and allocation of Engine.rollout run here too
+  (with the permuted, non-contiguous view BatchedEnvironment hands it), as in tests/test_gpu_rollout.py on the device."""
+  import numpy as np
   from spriteworld_amd import environment
   from tests import _emu_engine
-
-  class Engine(_emu_engine.EmuTorchEngine):
-    """... with engine.Engine's rollout(): CPU tensors in the C layout."""
-
-    def rollout(self, actions, positions=False):
-      a = actions.cpu().numpy() if isinstance(actions, torch.Tensor) else actions
-      return {k: torch.from_numpy(v) for k, v in cases.rollout_through_library(self, a, positions).items()}
-
-  monkeypatch.setattr(environment._engine, 'Engine', Engine)
+  monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuEngine)
   cases.surface_case()
+  cfg, pool, _ = cases.built('goal_s5')
+  eng = _emu(cfg, pool)
+  for shape in ((cases.K, cases.N_ENVS, cases.M), (cases.K, cases.N_ENVS + 1, cases.M, 4), (cases.K, cases.N_ENVS, cases.M, 2)):
+    with pytest.raises(ValueError, match='rollout actions must be'):
+      eng.rollout(np.zeros(shape))
+  eng.close()
 
 
 def test_rollout_outputs_struct_matches_the_header(tmp_path):

@@ -8,45 +8,19 @@ import numpy as np
 import pytest
 
 from spriteworld_amd import workloads
+from tests import _parity
+from tests import _setter_cases
 
 pytestmark = pytest.mark.gpu
 
 
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _compare(t, ora, eng, want, got):
-  st_o, st_g = ora.state(), eng.state()
-  assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-  np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-  np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-  for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-    np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-  np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-  np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32))
-  gr, wr = got['reward'], want['reward']
-  assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-  ok = ~np.isnan(wr)
-  np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-  diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-  assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t, np.argwhere(diff > 0)[:5].tolist())
-
-
-def _run(name, n_envs, steps, aa, seed=0, episodes_per_env=3):
-  from oracle import oracle
+def _engine(cfg, pool):
   from spriteworld_amd import engine
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=episodes_per_env, seed=seed, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), engine.Engine(cfg, pool)
-  assert eng.variant()['large_frames'] == 1
-  rng = np.random.default_rng(seed + 100)
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    _compare(t, ora, eng, want, eng.outputs_host())
-  eng.close()
+  return engine.Engine(cfg, pool)
+
+
+def _run(name, n_envs, steps, aa, seed=0):
+  _parity.run(_engine, name, n_envs, steps, aa, seed=seed, expect={'large_frames': 1})
 
 
 @pytest.mark.parametrize('geom,aa,n_envs,steps', [('256x256', 10, 6, 4), ('256x256', 5, 16, 6), ('160x160', 5, 32, 6),
@@ -103,49 +77,17 @@ def test_large_frames_forced_tasks_that_filter_on_position(monkeypatch):
     a = rng.uniform(0.0, 1.0, size=(n_envs, 4))
     want = ora.step(a)
     eng.step(a)
-    _compare(t, ora, eng, want, eng.outputs_host())
-  eng.close()
-
-
-def _setter_parity(name, n_envs, steps, aa, calls_per_step=6):
-  """The scenario of tests/_setter_cases.run_parity (setters on live sprites between steps, observation() at once) on a
-  large-frame handle."""
-  from oracle import oracle
-  from spriteworld_amd import _abi, engine, shapes
-  from tests import _setter_cases
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=0, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), engine.Engine(cfg, pool)
-  assert eng.variant()['large_frames'] == 1
-  rng, srng = np.random.default_rng(100), np.random.RandomState(5)
-  applied = 0
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    st = _setter_cases._compare(t, ora, eng, want, eng.outputs_host())
-    live = np.flatnonzero((st['reset_next'] == 0) & (st['n_sprites'] > 0))
-    for _ in range(calls_per_step if len(live) else 0):
-      env = int(srng.choice(live))
-      k = int(srng.randint(0, st['n_sprites'][env]))
-      attr = int(srng.randint(0, 3))
-      value = (float(srng.randint(0, len(shapes.SHAPES))) if attr == _abi.ATTR_SHAPE else
-               float(srng.choice([0., 17., 45., 90., 133.5, 270., 359.])) if attr == _abi.ATTR_ANGLE else
-               float(srng.choice([0.08, 0.12, 0.2, 0.3])))
-      ora.set_sprite_attr(env, k, attr, value)
-      eng.set_sprite_attr(env, k, attr, value)
-      applied += 1
-    np.testing.assert_array_equal(eng.render().cpu().numpy(), ora.render(), err_msg='render t=%d' % t)
-  assert applied > 0
+    _parity.compare(t, ora, eng, want, eng.outputs_host())
   eng.close()
 
 
 def test_large_frames_sprite_setters(monkeypatch):
   monkeypatch.setenv('SWB_LARGE_FRAMES', '1')
-  _setter_parity('goal_s5', 32, 5, 5)
+  _setter_cases.run_parity(_engine, 'goal_s5', 32, 5, 5, expect={'large_frames': 1}, render_every=1)
 
 
 def test_large_frame_setters_on_a_large_canvas():
-  _setter_parity('geom_160x160', 8, 4, 5)
+  _setter_cases.run_parity(_engine, 'geom_160x160', 8, 4, 5, expect={'large_frames': 1}, render_every=1)
 
 
 def test_large_frames_render_equals_the_step_frame_and_trim_is_a_no_op():

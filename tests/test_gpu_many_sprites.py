@@ -8,6 +8,7 @@ from spriteworld_amd import _abi
 from spriteworld_amd import lowering
 from spriteworld_amd import workloads
 from tests import _many_sprites_cases as cases
+from tests import _parity
 
 pytestmark = pytest.mark.gpu
 
@@ -71,9 +72,9 @@ def test_gpu_ragged_s64_8192_environments():
     gr, wr = got['reward'][envs], want['reward']
     assert np.array_equal(np.isnan(gr), np.isnan(wr))
     ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(cases._bits(gr[ok]), cases._bits(wr[ok]))
-    np.testing.assert_array_equal(cases._bits(st_g['x'][envs]), cases._bits(st_o['x']))
-    np.testing.assert_array_equal(cases._bits(st_g['y'][envs]), cases._bits(st_o['y']))
+    np.testing.assert_array_equal(_parity.bits(gr[ok]), _parity.bits(wr[ok]))
+    np.testing.assert_array_equal(_parity.bits(st_g['x'][envs]), _parity.bits(st_o['x']))
+    np.testing.assert_array_equal(_parity.bits(st_g['y'][envs]), _parity.bits(st_o['y']))
     np.testing.assert_array_equal(st_g['n_sprites'][envs], st_o['n_sprites'])
   assert st_g['n_sprites'].max() == 64
   eng.close()
@@ -120,7 +121,7 @@ def test_gpu_batched_environment_of_32_sprites():
     r, wr = ts.reward.cpu().numpy(), want['reward']
     assert np.array_equal(np.isnan(r), np.isnan(wr))
     ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(cases._bits(r[ok]), cases._bits(wr[ok]))
+    np.testing.assert_array_equal(_parity.bits(r[ok]), _parity.bits(wr[ok]))
     a = rng.uniform(0, 1, size=(64, 4))
     ts = env.step(torch.as_tensor(a))
     want = ora.step(a)

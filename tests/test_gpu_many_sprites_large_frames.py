@@ -1,7 +1,7 @@
 """GPU: the many-sprite state kernel (17 to 64 sprites) on large, wide and non-square frames; both paths at the limits the code
 states (4096 canvas pixels in either direction, 1024 image columns, 64 sprites, the vertex budget of the raster kernel's LDS)
 and one step past them; more than 65 535 environments on the large-frame path.  Against the CPU oracle, every step: state,
-rewards, step types, discounts and success bit-exact, frames +-0 (tests/_many_sprites_cases.compare).
+rewards, step types, discounts and success bit-exact, frames +-0 (tests/_parity.compare).
 
 The oracle's time per frame, one thread of the build container's CPU, sizes environments x steps of every case (a case's oracle
 work stays under 20 s there):
@@ -25,6 +25,7 @@ import pytest
 from spriteworld_amd import lowering
 from spriteworld_amd import workloads
 from tests import _many_sprites_cases as cases
+from tests import _parity
 
 pytestmark = pytest.mark.gpu
 
@@ -152,10 +153,10 @@ def _big_batch(built, steps, many):
     gr, wr = eng.reward[idx].cpu().numpy(), want['reward']
     assert np.array_equal(np.isnan(gr), np.isnan(wr))
     ok = ~np.isnan(wr)
-    np.testing.assert_array_equal(cases._bits(gr[ok]), cases._bits(wr[ok]))
+    np.testing.assert_array_equal(_parity.bits(gr[ok]), _parity.bits(wr[ok]))
     st_g, st_o = eng.state(), ora.state()
-    np.testing.assert_array_equal(cases._bits(st_g['x'][pick]), cases._bits(st_o['x']))
-    np.testing.assert_array_equal(cases._bits(st_g['y'][pick]), cases._bits(st_o['y']))
+    np.testing.assert_array_equal(_parity.bits(st_g['x'][pick]), _parity.bits(st_o['x']))
+    np.testing.assert_array_equal(_parity.bits(st_g['y'][pick]), _parity.bits(st_o['y']))
     for k in ('step_count', 'reset_next', 'episode', 'n_sprites'):
       np.testing.assert_array_equal(st_g[k][pick], st_o[k], err_msg=k)
   eng.close()

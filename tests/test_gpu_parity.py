@@ -9,47 +9,18 @@ import numpy as np
 import pytest
 
 from spriteworld_amd import workloads
+from tests import _parity
 
 pytestmark = pytest.mark.gpu
 
 
-def _bits(a):
-  return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _run(name, n_envs, steps, aa, seed=0, reward_ulp=0):
-  from oracle import oracle
+def _engine(cfg, pool):
   from spriteworld_amd import engine
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=seed, anti_aliasing=aa)
-  ora = oracle.Engine(cfg, pool)
-  eng = engine.Engine(cfg, pool)
-  rng = np.random.default_rng(seed + 100)
-  for t in range(steps):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a)
-    got = eng.outputs_host()
-    st_o, st_g = ora.state(), eng.state()
-    assert not got['error'].any(), (t, np.flatnonzero(got['error'])[:8])
-    np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['x']), _bits(st_o['x']), err_msg='x t=%d' % t)
-    np.testing.assert_array_equal(_bits(st_g['y']), _bits(st_o['y']), err_msg='y t=%d' % t)
-    for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
-      np.testing.assert_array_equal(st_g[k], st_o[k], err_msg='%s t=%d' % (k, t))
-    np.testing.assert_array_equal(got['success'], want['success'], err_msg='success t=%d' % t)
-    np.testing.assert_array_equal(got['discount'].view(np.uint32), want['discount'].view(np.uint32))
-    gr, wr = got['reward'], want['reward']
-    assert np.array_equal(np.isnan(gr), np.isnan(wr)), 'reward NaN pattern t=%d' % t
-    ok = ~np.isnan(wr)
-    if reward_ulp == 0:
-      np.testing.assert_array_equal(_bits(gr[ok]), _bits(wr[ok]), err_msg='reward t=%d' % t)
-    elif ok.any():
-      d = np.abs(_bits(gr[ok]).astype(np.int64) - _bits(wr[ok]).astype(np.int64))
-      assert d.max() <= reward_ulp, ('reward ulp', d.max(), t)
-    diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
-    assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), t,
-                             np.argwhere(diff > 0)[:5].tolist())
-  eng.close()
+  return engine.Engine(cfg, pool)
+
+
+def _run(name, n_envs, steps, aa, seed=0):
+  _parity.run(_engine, name, n_envs, steps, aa, seed=seed)
 
 
 def test_goal_s5_aa5():
@@ -214,7 +185,7 @@ def test_cover_launches_in_cost_order(monkeypatch, name, n_envs, aa):
     got = eng.outputs_host()
     assert not got['error'].any()
     np.testing.assert_array_equal(got['step_type'], want['step_type'])
-    np.testing.assert_array_equal(_bits(eng.state()['x']), _bits(ora.state()['x']))
+    np.testing.assert_array_equal(_parity.bits(eng.state()['x']), _parity.bits(ora.state()['x']))
     assert np.array_equal(got['obs'], want['obs']), t
   eng.close()
 

@@ -6,7 +6,6 @@ environment: frames, hit-tests, rewards bit for bit) and the library's host arit
 GPU (tests/test_gpu_setters.py): the HIP engine against the oracle.
 """
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -110,8 +109,7 @@ def test_oracle_setters_equal_reference(seed):
 
 def _path_op(attr, a, b, verts):
   build.build()
-  lib = C.CDLL(_lib.LIB_PATH)
-  lib.swb_sprite_path_op.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
+  lib = _lib.load()
   v = np.ascontiguousarray(verts, dtype=np.float64)
   out = np.zeros_like(v)
   assert lib.swb_sprite_path_op(attr, float(a), float(b), len(v), v.ctypes.data, out.ctypes.data) == 0
