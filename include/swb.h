@@ -341,6 +341,39 @@ typedef struct swb_rollout_outputs {   /* device memory, caller-owned; any point
 } swb_rollout_outputs;
 int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream);
 
+/* Random-agent actions drawn on the device: one action per environment, ready for swb_step, without a host round trip.
+ * SWB_SAMPLE_UNIFORM is action_space.sample() (uniform in [0, 1)^4; Embodied: carry in {0, 1}, direction in {0 .. 3}).
+ * SWB_SAMPLE_ON_SPRITE is the batched Environment.sample_contained_position() (environment.py:110-126, sprite.py:117-126): a
+ * sprite of the environment drawn uniformly by index, then a point of its bounding box redrawn until the sprite contains it
+ * (sprite.py:113-115 on the centred path, setter overrides included); SelectMove / DragAndDrop actions click there.
+ * One kernel, one wave per environment, asynchronous on `stream`.  The handle is only READ -- the sprites as they are now, what
+ * swb_render would draw; an environment about to reset keeps its terminal sprites (its next action is ignored anyway) -- and
+ * nothing of it is written: live state, the outputs of the last step, error flags, pool, run lists, dispatch bookkeeping.
+ * Random numbers: Philox4x32-10, key = seed, counter = (entry lo, block, entry hi, 0) with entry = first_env + environment --
+ * the streams of swb_sample_pool.  Draw order per environment (tests/_random_agent_model.py restates it, bit for bit):
+ *   UNIFORM    SelectMove / DragAndDrop: a[0..3] = uniform (two u32 each).  Embodied: a[0] = u32 % 2, a[1] = u32 % 4.
+ *   ON_SPRITE  n sprites.  n == 0: sprite = -1, tries = 0, position = (uniform, uniform).  Else s = u32 % n; low / high = the
+ *              exact min / max over the vertices of its centred path; per try ux, uy = uniform, d = low + (high - low) * u,
+ *              sample = position of s + d, accepted when the path contains sample - position of s (float64 throughout; a
+ *              float32 position enters as its float64 value).  Then SelectMove / DragAndDrop: a[0], a[1] = sample, a[2], a[3] =
+ *              uniform; Embodied: the two integer draws of UNIFORM (the contained position goes to `position` only).
+ * Float32-action handles store (float) of the float64 values: containment is guaranteed for FLOAT64 actions (and `position`)
+ * only -- a click rounded to float32 may leave the sprite at its edge.
+ * DEVIATION from the reference: it gives up after 10^6 tries and raises; the kernel gives up after SWB_CONTAINED_MAX_TRIES
+ * tries, then writes tries = -1 and the sprite's own position.  The worst acceptance rate of a shipped shape over all rotations
+ * is 0.3536 (star_4: area over bounding box), so 1024 consecutive misses have probability below 1e-190; the cap bounds the time
+ * a degenerate sprite (a zero scale through a setter) can take.
+ * SWB_ERR_INVALID: unknown mode; every output NULL; position / sprite / tries given with SWB_SAMPLE_UNIFORM. */
+#define SWB_CONTAINED_MAX_TRIES 1024
+enum swb_action_sampling { SWB_SAMPLE_UNIFORM = 0, SWB_SAMPLE_ON_SPRITE = 1 };
+typedef struct swb_sampled_actions {   /* device memory, caller-owned */
+  void* actions;      /* [N][4] f64 or f32 (the handle's action dtype), or [N][2] i32 (Embodied); may be NULL            */
+  double* position;   /* [N][2] the contained position, always f64; ON_SPRITE only, may be NULL                           */
+  int32_t* sprite;    /* [N] index of the chosen sprite, -1 if the environment has none; ON_SPRITE only, may be NULL      */
+  int32_t* tries;     /* [N] draws used (>= 1); 0: no sprite; -1: cap reached; ON_SPRITE only, may be NULL                */
+} swb_sampled_actions;
+int swb_sample_actions(swb_handle h, int32_t mode, uint64_t seed, uint64_t first_env, const swb_sampled_actions* out, void* stream);
+
 /* Memory of the hand-off lists (what the cover kernel hands the resample / fill kernel: swb_variant_info::run_list_bytes).
  * A handle starts with a list of max(4, max_sprites + 1) units of 8 bytes per canvas row for every environment and group of 64
  * output columns -- enough for ANY scene of convex sprites, about ten times what the usual scene needs (133 KB per environment

@@ -24,6 +24,9 @@ STEP_FIRST, STEP_MID, STEP_LAST = 0, 1, 2
 ENV_ERR_DB_ZERO, ENV_ERR_DB_LABELS, ENV_ERR_SPAN_OVERFLOW = 1, 2, 4
 # enum swb_sprite_attr
 ATTR_SHAPE, ATTR_ANGLE, ATTR_SCALE = 0, 1, 2
+# enum swb_action_sampling
+SAMPLE_UNIFORM, SAMPLE_ON_SPRITE = 0, 1
+SWB_CONTAINED_MAX_TRIES = 1024
 
 
 class SwbTask(C.Structure):
@@ -112,6 +115,15 @@ class SwbRolloutOutputs(C.Structure):
       ('x', C.c_void_p),
       ('y', C.c_void_p),
       ('n_sprites', C.c_void_p),
+  ]
+
+
+class SwbSampledActions(C.Structure):
+  _fields_ = [
+      ('actions', C.c_void_p),
+      ('position', C.c_void_p),
+      ('sprite', C.c_void_p),
+      ('tries', C.c_void_p),
   ]
 
 
@@ -225,6 +237,7 @@ PROTOTYPES = {
     'swb_render': (None, [_h, _p, _h]),
     'swb_evaluate': (None, [_h, _p, _h]),
     'swb_rollout': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _h]),
+    'swb_sample_actions': (None, [_h, _i32, _u64, _u64, _P(SwbSampledActions), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_factors': (None, [_h, _p, _h]),
     'swb_get_env_state': (None, [_h, _i32, _p, _h]),

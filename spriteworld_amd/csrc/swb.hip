@@ -1246,6 +1246,29 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
   return SWB_OK;
 }
 
+// Random-agent actions (include/swb.h): one kernel that only reads the handle -- not a launch(): no parity, phase or cost list moves.
+int swb_sample_actions(swb_handle h, int32_t mode, uint64_t seed, uint64_t first_env, const swb_sampled_actions* out, void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (mode != SWB_SAMPLE_UNIFORM && mode != SWB_SAMPLE_ON_SPRITE) return fail(SWB_ERR_INVALID, "swb_sample_actions: unknown mode %d", mode);
+  if (!out || (!out->actions && !out->position && !out->sprite && !out->tries))
+    return fail(SWB_ERR_INVALID, "swb_sample_actions: every output is NULL");
+  if (mode == SWB_SAMPLE_UNIFORM && (out->position || out->sprite || out->tries))
+    return fail(SWB_ERR_INVALID, "swb_sample_actions: position, sprite and tries are outputs of SWB_SAMPLE_ON_SPRITE only");
+  if (mode == SWB_SAMPLE_ON_SPRITE) {
+    if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
+    if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  swb_sample_actions_args a;
+  memset(&a, 0, sizeof(a));
+  a.mode = mode; a.seed = seed; a.first_env = first_env;
+  a.actions = out->actions; a.position = out->position; a.sprite = out->sprite; a.tries = out->tries;
+  hipLaunchKernelGGL(swb_sample_actions_kernel, dim3((unsigned)h->p.N), dim3(SWB_WAVE), SWB_MAX_SHAPE_VERTS * sizeof(double2),
+                     (hipStream_t)stream, h->p, a);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
+}
+
 int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   HIP_TRY(hipSetDevice(h->device));

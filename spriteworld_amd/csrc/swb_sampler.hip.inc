@@ -225,3 +225,122 @@ __global__ void __launch_bounds__(256) swb_sample_pool_kernel(const swb_sampler_
     for (int t = 0; t < T; ++t) a.p_label[((size_t)e * T + t) * S + q] = 0;
   }
 }
+
+// --------------------------------------------------------------------------------------------
+// Random-agent actions (swb_sample_actions, include/swb.h): one wave per environment draws the environment's next action
+// -- uniform, or a click inside a randomly chosen sprite (environment.py:110-126, sprite.py:117-126) -- from the sprites as
+// they are now.  The handle is only read, and everything read was written by earlier launches (as_const: scalar loads).
+// Every lane runs the same Philox stream (key = seed, entry = first_env + environment), so every drawn value is wave-uniform,
+// as the ballot of contains_point_wave requires.  Draw order (tests/_random_agent_model.py restates it, bit for bit):
+//   UNIFORM    SelectMove / DragAndDrop: a[0..3] = uniform().  Embodied: a[0] = u32 % 2, a[1] = u32 % 4.
+//   ON_SPRITE  1. n = nspr[env]; n == 0: sprite = -1, tries = 0, position = (uniform(), uniform()), on with 4.
+//              2. s = u32 % n
+//              3. the centred path of sprite s into LDS, lanes = vertices (ov_cpath when the environment carries setter
+//                 overrides, else centered_vertex); low / high = exact min / max over the vertices (wave reduction).
+//                 Per try: ux, uy = uniform(); d = low + (high - low) * u (numpy's uniform(low, high)); sample = pos + d
+//                 (sprite.py:122); accepted if the path contains sample - pos (sprite.py:115) -- all float64, no FMA.
+//                 After SWB_CONTAINED_MAX_TRIES misses: tries = -1, sample = pos (the reference raises after 10^6).
+//              4. SelectMove / DragAndDrop: a[0], a[1] = sample, a[2], a[3] = uniform().  Embodied: the integer draws of UNIFORM.
+// --------------------------------------------------------------------------------------------
+#ifndef SWB_WIDE_TU
+struct swb_sample_actions_args {
+  int32_t mode;
+  uint64_t seed, first_env;
+  void* actions;               // [N][4] f64 / f32 or [N][2] i32; any output may be NULL
+  double* position;            // [N][2]
+  int32_t *sprite, *tries;     // [N]
+};
+
+static_assert(sizeof(swb_params) + sizeof(swb_sample_actions_args) <= 4096, "kernel arguments of swb_sample_actions_kernel");
+
+__device__ __forceinline__ double wave_min_d(double v) {
+  for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = (w < v) ? w : v; }
+  return v;
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+  for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = (w > v) ? w : v; }
+  return v;
+}
+
+__global__ void __launch_bounds__(SWB_WAVE)
+swb_sample_actions_kernel(const swb_params p, const swb_sample_actions_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double2* cpath = reinterpret_cast<double2*>(smem);    // SWB_MAX_SHAPE_VERTS vertices: 1 KiB
+  const int l = lane_id();
+  const int env = blockIdx.x;
+  const int S = p.S;
+  philox_stream rng;
+  rng.key0 = (uint32_t)a.seed; rng.key1 = (uint32_t)(a.seed >> 32); rng.block = 0u; rng.have = 0;
+  const uint64_t ge = a.first_env + (uint64_t)env;
+  rng.entry = (uint32_t)ge; rng.entry_hi = (uint32_t)(ge >> 32);
+  const bool embodied = p.action_space == SWB_ACTION_EMBODIED;
+  double a0 = 0.0, a1 = 0.0;
+  if (a.mode == SWB_SAMPLE_ON_SPRITE) {
+    const int n = min(max(as_const(p.nspr)[env], 0), S);
+    int sprite = -1, tries = 0;
+    if (n == 0) {
+      a0 = rng.uniform(); a1 = rng.uniform();
+    } else {
+      sprite = (int)(rng.u32() % (uint32_t)n);
+      const size_t o = (size_t)env * S + sprite, pe = (size_t)as_const(p.entry)[env] * S + sprite;
+      const bool ov = p.ov_flag != nullptr && as_const(p.ov_flag)[env] != 0;   // sprite.py:152-175 setters were applied to this episode
+      const int shape = ov ? as_const(p.ov_shape)[o] : as_const(p.p_shape)[pe];
+      const int sh_idx = (int)min((uint32_t)shape, (uint32_t)(SWB_MAX_SHAPES - 1));
+      const int so = as_const(p.shape_off)[sh_idx];
+      const int nv = min(as_const(p.shape_off)[sh_idx + 1] - so, SWB_MAX_SHAPE_VERTS);
+      const double px = as_const(p.x)[o], py = as_const(p.y)[o];
+      double cx = 0.0, cy = 0.0;
+      if (l < nv) {
+        if (ov) {                                       // the path the setters left (host arithmetic, swb.hip)
+          const double* q = p.ov_cpath + (o * SWB_MAX_SHAPE_VERTS + l) * 2;
+          cx = q[0]; cy = q[1];
+        } else {
+          centered_vertex(p, so, l, as_const(p.p_scale)[pe], as_const(p.p_ca)[pe], as_const(p.p_sa)[pe], cx, cy);
+        }
+        cpath[l] = make_double2(cx, cy);
+      }
+      wave_sync();
+      // sprite.py:119-120: np.min / np.max over the vertices (lanes beyond the path repeat vertex 0)
+      const double fx = readlane_d(cx, 0), fy = readlane_d(cy, 0);
+      const double vx = (l < nv) ? cx : fx, vy = (l < nv) ? cy : fy;
+      const double lo_x = wave_min_d(vx), lo_y = wave_min_d(vy), hi_x = wave_max_d(vx), hi_y = wave_max_d(vy);
+      const double w_x = __dsub_rn(hi_x, lo_x), w_y = __dsub_rn(hi_y, lo_y);
+      a0 = px; a1 = py; tries = -1;
+      for (int t = 1; t <= SWB_CONTAINED_MAX_TRIES; ++t) {
+        const double ux = rng.uniform(), uy = rng.uniform();
+        const double sx = __dadd_rn(px, __dadd_rn(lo_x, __dmul_rn(w_x, ux)));
+        const double sy = __dadd_rn(py, __dadd_rn(lo_y, __dmul_rn(w_y, uy)));
+        if (contains_point_wave(cpath, nv, __dsub_rn(sx, px), __dsub_rn(sy, py))) {   // (the test point is sample - pos)
+          a0 = sx; a1 = sy; tries = t;
+          break;
+        }
+      }
+    }
+    if (l == 0) {
+      if (a.position) { a.position[2 * (size_t)env] = a0; a.position[2 * (size_t)env + 1] = a1; }
+      if (a.sprite) a.sprite[env] = sprite;
+      if (a.tries) a.tries[env] = tries;
+    }
+  } else if (!embodied) {
+    a0 = rng.uniform(); a1 = rng.uniform();
+  }
+  if (embodied) {
+    const int carry = (int)(rng.u32() % 2u), dir = (int)(rng.u32() % 4u);
+    if (l == 0 && a.actions) {
+      int32_t* q = reinterpret_cast<int32_t*>(a.actions) + 2 * (size_t)env;
+      q[0] = carry; q[1] = dir;
+    }
+    return;
+  }
+  const double a2 = rng.uniform(), a3 = rng.uniform();
+  if (l == 0 && a.actions) {
+    if (p.action_is_f32) {
+      float* q = reinterpret_cast<float*>(a.actions) + 4 * (size_t)env;
+      q[0] = (float)a0; q[1] = (float)a1; q[2] = (float)a2; q[3] = (float)a3;
+    } else {
+      double* q = reinterpret_cast<double*>(a.actions) + 4 * (size_t)env;
+      q[0] = a0; q[1] = a1; q[2] = a2; q[3] = a3;
+    }
+  }
+}
+#endif  // SWB_WIDE_TU

@@ -188,6 +188,30 @@ class Engine(object):
     self._check(self.lib.swb_rollout(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), self._stream()))
     return res
 
+  def sample_actions(self, mode, seed, first_env=0, outputs=('actions',)):
+    """Random-agent actions drawn on the device from the sprites as they are now (swb_sample_actions: one kernel,
+    asynchronous, the handle only read).  mode: _abi.SAMPLE_UNIFORM or _abi.SAMPLE_ON_SPRITE (a click inside a randomly chosen
+    sprite); environment n draws Philox stream `first_env + n` of key `seed`.  `outputs`: which of 'actions' (f64[N, 4], f32
+    if cfg.action_is_f32, or i32[N, 2] for Embodied: what step() takes), 'position' (f64[N, 2]), 'sprite' (i32[N]) and
+    'tries' (i32[N]) to return -- the last three with SAMPLE_ON_SPRITE only.  Returns a dict of fresh device tensors."""
+    if self.cfg.action_space == _abi.ACTION_EMBODIED:
+      shape, dtype = (self.N, 2), torch.int32
+    else:
+      shape, dtype = (self.N, 4), (torch.float32 if self.cfg.action_is_f32 else torch.float64)
+    layout = {'actions': (shape, dtype), 'position': ((self.N, 2), torch.float64), 'sprite': ((self.N,), torch.int32),
+              'tries': ((self.N,), torch.int32)}
+    unknown = [k for k in outputs if k not in layout]
+    if unknown:
+      raise ValueError('sample_actions outputs must be among %s, got %s' % (sorted(layout), unknown))
+    with self._device_scope():
+      res = {k: torch.empty(layout[k][0], dtype=layout[k][1], device=self.device) for k in outputs}
+    o = _abi.SwbSampledActions()
+    for k, t in res.items():
+      setattr(o, k, t.data_ptr())
+    self._check(self.lib.swb_sample_actions(self._h, int(mode), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                            C.c_uint64(int(first_env)), C.byref(o), self._stream()))
+    return res
+
   def trim(self):
     """Cuts the hand-off lists between the two kernels of a step from their start-up reservation (any scene of convex sprites:
     133 KB per environment on 12 sprites at 128x128) down to 1.25 x what the launches so far needed, plus a shared arena for the

@@ -64,6 +64,12 @@ class Rollout(collections.namedtuple('Rollout', ['step_type', 'reward', 'discoun
     return torch.where(keep, self.reward, torch.zeros_like(self.reward)).sum(dim=2)
 
 
+_ACTION_KEY_DOMAIN = 0xA5A5C3D2E1F00F1E      # folded into the seed of the device action stream (_next_action_seed)
+
+# What `BatchedEnvironment.sample_contained_positions` returns, device tensors: position f64[N, 2], sprite i32[N], tries i32[N].
+ContainedPositions = collections.namedtuple('ContainedPositions', ['position', 'sprite', 'tries'])
+
+
 class EnvironmentError_(RuntimeError):
   pass
 
@@ -146,6 +152,7 @@ class BatchedEnvironment(object):
                                       pos_is_f32=(pos_dt == np.float32), action_dtype=action_dtype)
     self._noise_scale = None if not ns else torch.as_tensor(np.asarray(ns, dtype=np.float64))
     self._noise_gen = None
+    self._action_seed, self._action_draws = None, 0      # device action sampling (seed_actions / _next_action_seed)
     if self._sampler is not None:
       self._sampler_spec = self._sampler.lower(task, renderers)
       self._engine = _engine.Engine(self._cfg, None, device=device)
@@ -317,8 +324,55 @@ class BatchedEnvironment(object):
     """Live structure-of-arrays state (host copies): x, y [N, S], n_sprites, step_count, ..."""
     return self._engine.state()
 
-  def sample_actions(self):
-    return self._action_space.sample(self._num_envs)
+  def sample_actions(self, where='host', click='uniform'):
+    """One random-agent action per environment.  With no arguments (where='host'): `action_space.sample(num_envs)` --
+    numpy's global stream on the host, float64, uploaded by the next step().
+    where='device': drawn by a HIP kernel (swb_sample_actions) into a device tensor that step() takes as it is; no host
+    synchronisation.  click='sprite' (device only; the batched `Environment.sample_contained_position()`): the click of a
+    SelectMove / DragAndDrop action lands inside a randomly chosen sprite of its environment, as it is now; Embodied
+    actions stay uniform.  Containment holds for float64 actions; rounded to float32 (action_dtype=np.float32) a click may
+    leave its sprite at the edge.  The device stream is Philox keyed by seed_actions(), not numpy's MT19937."""
+    mode = self._sampling_mode(where, click)
+    if mode is None:
+      return self._action_space.sample(self._num_envs)
+    return self._engine.sample_actions(mode, self._next_action_seed(), first_env=self._global_env_offset)['actions']
+
+  def sample_contained_positions(self):
+    """environment.py:110-126 for every environment, on the device: a sprite drawn uniformly by index, then a position of
+    its bounding box redrawn until the sprite contains it.  Returns ContainedPositions(position f64[N, 2], sprite i32[N],
+    tries i32[N]) of device tensors: sprite -1 / tries 0 for an environment without sprites (its position is uniform in the
+    frame); tries -1 and the sprite's own position where _abi.SWB_CONTAINED_MAX_TRIES draws all missed (a degenerate sprite)."""
+    res = self._engine.sample_actions(_abi.SAMPLE_ON_SPRITE, self._next_action_seed(), first_env=self._global_env_offset,
+                                      outputs=('position', 'sprite', 'tries'))
+    return ContainedPositions(res['position'], res['sprite'], res['tries'])
+
+  def seed_actions(self, seed):
+    """Seeds the device action stream: call k after it draws with splitmix64(seed ^ a constant, k) as its Philox key (the
+    constant keeps it apart from the reset sampler's keys under the same seed).  Unseeded, the base
+    seed is drawn once from numpy's global stream at the first device call, so np.random.seed() reproduces a run."""
+    self._action_seed = int(seed)
+    self._action_draws = 0
+
+  def _sampling_mode(self, where, click):
+    if where not in ('host', 'device') or click not in ('uniform', 'sprite'):
+      raise ValueError("sample_actions: where is 'host' or 'device' and click 'uniform' or 'sprite', got %r, %r" % (where, click))
+    if where == 'host':
+      if click != 'uniform':
+        raise ValueError("sample_actions: click='sprite' is drawn on the device (where='device')")
+      return None
+    return _abi.SAMPLE_ON_SPRITE if click == 'sprite' else _abi.SAMPLE_UNIFORM
+
+  def _next_action_seed(self):
+    """A fresh 64-bit Philox key per call (splitmix64 of seed and call counter, as DeviceSampler.next_seed)."""
+    if self._action_seed is None:
+      self.seed_actions(int(np.random.randint(0, 2**31 - 1)))
+    # (the constant keeps these keys apart from DeviceSampler.next_seed's under the same seed: the kernels share the counter
+    # layout, and action call k of environment e must not replay the stream that drew pool entry e in reset draw k)
+    z = ((self._action_seed ^ _ACTION_KEY_DOMAIN) * 0x9E3779B97F4A7C15 + self._action_draws + 1) & 0xFFFFFFFFFFFFFFFF
+    self._action_draws += 1
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
 
   # ------------------------------------------------------------------ live sprites (sprite.py:152-175)
   def sprites(self, env=0):
@@ -409,6 +463,12 @@ class EnvironmentGroups(object):
     """Steps group `g` on its stream; the returned tensors are valid on `self.streams[g]`."""
     with torch.cuda.stream(self.streams[g]):
       return self.groups[g].step(actions)
+
+  def sample_actions(self, g, where='host', click='uniform'):
+    """`BatchedEnvironment.sample_actions` of group `g`; the device forms run on its stream.  The groups' global_env_offset
+    keeps their device streams apart under one seed."""
+    with torch.cuda.stream(self.streams[g]):
+      return self.groups[g].sample_actions(where=where, click=click)
 
   def synchronize(self):
     for s in self.streams:
