@@ -1,4 +1,5 @@
-"""Device-side reset sampling (swb_sample_pool): lowering on CPU, bit-for-bit draws on the GPU."""
+"""Device-side reset sampling (swb_sample_pool): lowering on CPU, bit-for-bit draws on the GPU.  The sampler configurations
+and the bodies the emulated suite shares are in tests/_sampler_cases.py."""
 import numpy as np
 import pytest
 
@@ -12,122 +13,9 @@ from spriteworld_amd import shapes
 from spriteworld_amd import sprite as sprite_lib
 from spriteworld_amd import tasks
 
+from tests import _sampler_cases as cases
 from tests import _sampler_model
-
-
-def _cobra_like(shuffle=True):
-  """Goal-finding with distractors in the style of configs/cobra/goal_finding_more_distractors.py."""
-  common = [distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-            distribs.Discrete('shape', ['square', 'triangle', 'circle']), distribs.Discrete('scale', [0.13]),
-            distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)]
-  target = distribs.Product(common + [distribs.Continuous('c0', 0., 0.4)])
-  distractor = distribs.Product(common + [distribs.Continuous('c0', 0.5, 0.9)])
-  sampler = device_sampler.DeviceSampler([(target, 2), (distractor, (1, 4))], shuffle=shuffle, seed=7)
-  task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=0.1)
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=5,
-                                            color_to_rgb=renderer_lib.color_maps.hsv_to_rgb),
-          'success': renderer_lib.Success()}
-  return sampler, task, rend
-
-
-def _mixed_types():
-  """Every factor kind: integer colours/angles, Python-float Discrete colours, Continuous scale, velocities."""
-  a = distribs.Product([
-      distribs.Continuous('x', 0.2, 0.8), distribs.Continuous('y', 0.2, 0.8),
-      distribs.Discrete('shape', ['star_5', 'spoke_4', 'pentagon', 'hexagon']),
-      distribs.Continuous('scale', 0.05, 0.15), distribs.Continuous('angle', 0, 360, dtype='int32'),
-      distribs.Continuous('c0', 64, 256, dtype='uint8'), distribs.Continuous('c1', 0, 128, dtype='int32'),
-      distribs.Discrete('c2', [255, 128, 7]),
-      distribs.Continuous('x_vel', -0.03, 0.03), distribs.Continuous('y_vel', -0.03, 0.03)])
-  b = distribs.Product([
-      distribs.Continuous('x', 0.0, 1.0), distribs.Continuous('y', 0.0, 1.0),
-      distribs.Discrete('angle', [0, 30, 45.5, 270]), distribs.Discrete('scale', [0.07, 0.2]),
-      distribs.Continuous('c0', 192, 256, dtype='int32')])
-  sampler = device_sampler.DeviceSampler([(a, (0, 3)), (b, 2), (a, 1)], shuffle=True, seed=3)
-  clusters = [distribs.Continuous('c1', 0, 128, dtype='int32'), distribs.Discrete('c1', [0])]
-  task = tasks.MetaAggregated((tasks.Clustering(clusters, terminate_bonus=0., reward_range=10.),
-                               tasks.FindGoalPosition(terminate_distance=0.05)), reward_aggregator='sum')
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=2)}
-  return sampler, task, rend
-
-
-def _hsv_mixed():
-  """hsv colour map over mixed np.float32 / Python-float channels (NEP 50 promotion inside colorsys)."""
-  groups = []
-  for c0, c1, c2 in (
-      (distribs.Continuous('c0', 0., 1.), distribs.Discrete('c1', [0.]), distribs.Continuous('c2', 0.2, 1.)),
-      (distribs.Discrete('c0', [0.05, 0.33, 0.7, 0.999]), distribs.Continuous('c1', 0.1, 1.), distribs.Continuous('c2', 0.1, 1.)),
-      (distribs.Continuous('c0', 0., 1.), distribs.Discrete('c1', [1., 0.37]), distribs.Discrete('c2', [0.9, 0.31])),
-      (distribs.Discrete('c0', [0.1, 0.6]), distribs.Discrete('c1', [0.2, 0.8]), distribs.Discrete('c2', [0.45, 1.])),
-      (distribs.Continuous('c0', 0., 1.), distribs.Continuous('c1', 0., 1.), distribs.Continuous('c2', 0., 1.)),
-  ):
-    groups.append((distribs.Product([distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-                                     c0, c1, c2]), 3))
-  sampler = device_sampler.DeviceSampler(groups, shuffle=False, seed=11)
-  task = tasks.NoReward()
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=1,
-                                            color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
-  return sampler, task, rend
-
-
-def _holdouts():
-  """SetMinus rejection in the style of cobra/goal_finding_new_position.py and examples/goal_finding_clustering.py."""
-  position = distribs.SetMinus(
-      distribs.Product((distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9))),
-      distribs.Product((distribs.Continuous('x', 0.5, 0.9), distribs.Continuous('y', 0.5, 0.9))))
-  scale = distribs.SetMinus(distribs.Continuous('scale', 0.05, 0.15), distribs.Continuous('scale', 0.08, 0.12))
-  target = distribs.Product([position, scale, distribs.Discrete('shape', ['square', 'triangle', 'circle']),
-                             distribs.Continuous('c0', 0., 0.4), distribs.Continuous('c1', 0.3, 1.),
-                             distribs.Continuous('c2', 0.9, 1.)])
-  distractor = distribs.Product([distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-                                 distribs.Discrete('shape', ['square', 'triangle', 'circle']),
-                                 distribs.Discrete('scale', [0.13]), distribs.Continuous('c0', 0.5, 0.9),
-                                 distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)])
-  sampler = device_sampler.DeviceSampler([(target, 2), (distractor, 1)], shuffle=False, seed=21)
-  task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=0.075)
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=5,
-                                            color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
-  return sampler, task, rend
-
-
-def _embodied_like():
-  """A shuffled set of objects with the agent body kept on top (examples/goal_finding_embodied.py:68-93)."""
-  obj = distribs.Product([distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-                          distribs.Discrete('shape', ['square', 'triangle', 'circle']), distribs.Discrete('scale', [0.13]),
-                          distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)])
-  target = distribs.Product([obj, distribs.Continuous('c0', 0., 0.4)])
-  distractor = distribs.Product([obj, distribs.Continuous('c0', 0.5, 0.9)])
-  body = distribs.Product([distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-                           distribs.Discrete('shape', ['circle']), distribs.Discrete('scale', [0.07]),
-                           distribs.Discrete('c0', [0.2]), distribs.Discrete('c1', [1.]), distribs.Discrete('c2', [1.])])
-  sampler = device_sampler.DeviceSampler([(target, 1), (distractor, (0, 3)), (body, 1)], shuffle=2, seed=5)
-  task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=0.1)
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=5,
-                                            color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
-  return sampler, task, rend
-
-
-def _sorting_like():
-  """shuffle(sample_generator(chains)) over shared single-sprite groups (cobra/sorting.py:75-115)."""
-  hues = [distribs.Continuous('c0', lo, lo + 0.1) for lo in (0.05, 0.25, 0.45, 0.65, 0.85)]
-  goals = [(0.75, 0.75), (0.25, 0.75), (0.25, 0.25), (0.75, 0.25), (0.5, 0.5)]
-  groups = [(distribs.Product((h, distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-                               distribs.Discrete('shape', ['square', 'triangle', 'circle']),
-                               distribs.Discrete('scale', [0.13]), distribs.Continuous('c1', 0.3, 1.),
-                               distribs.Continuous('c2', 0.9, 1.))), 1) for h in hues]
-  import itertools
-  combos = [list(c) for c in itertools.combinations(range(5), 2)][1:]
-  sampler = device_sampler.DeviceSampler(groups, shuffle=True, seed=9, alternatives=combos)
-  subtasks = [tasks.FindGoalPosition(filter_distrib=h, goal_position=g, terminate_distance=0.1, raw_reward_multiplier=20)
-              for h, g in zip(hues, goals)]
-  task = tasks.MetaAggregated(subtasks, reward_aggregator='sum', termination_criterion='all')
-  rend = {'image': renderer_lib.PILRenderer(image_size=(64, 64), anti_aliasing=5,
-                                            color_to_rgb=renderer_lib.color_maps.hsv_to_rgb)}
-  return sampler, task, rend
-
-
-CASES = {'sorting_like': _sorting_like, 'embodied_like': _embodied_like, 'cobra_like': _cobra_like, 'mixed_types': _mixed_types, 'hsv_mixed': _hsv_mixed, 'holdouts': _holdouts}
-
+from tests._sampler_cases import CASES
 
 def test_philox_known_answers():
   # Random123 kat_vectors, philox4x32-10
@@ -166,7 +54,7 @@ def test_lowering_fills_the_spec(case):
 
 
 def test_setminus_lowers_to_holdout_boxes():
-  sampler, task, rend = _holdouts()
+  sampler, task, rend = cases._holdouts()
   spec = sampler.lower(task, rend)
   grp = spec.groups[0]
   assert grp.n_holdouts == 2 and spec.groups[1].n_holdouts == 0
@@ -183,7 +71,7 @@ def test_setminus_lowers_to_holdout_boxes():
 
 
 def test_partial_shuffle_keeps_the_body_on_top():
-  sampler, task, rend = _embodied_like()
+  sampler, task, rend = cases._embodied_like()
   spec = sampler.lower(task, rend)
   assert spec.shuffle == 2 and spec.n_groups == 3
   label = lambda f: int(task._filter_distrib.contains(f))
@@ -267,7 +155,7 @@ def test_every_reference_config_lowers_to_a_device_sampler():
 
 
 def test_host_call_draws_valid_sprites():
-  sampler, _, _ = _mixed_types()
+  sampler, _, _ = cases._mixed_types()
   np.random.seed(0)
   for _ in range(20):
     sprites = sampler()
@@ -294,59 +182,15 @@ def test_unsupported_distributions_are_refused():
 
 
 # ------------------------------------------------------------------------------------- GPU
-def _make_env(case, num_envs=48, episodes_per_env=3):
-  from spriteworld_amd import environment
-  sampler, task, rend = CASES[case]()
-  env = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25),
-                                       renderers=rend, init_sprites=sampler, max_episode_length=6,
-                                       num_envs=num_envs, episodes_per_env=episodes_per_env,
-                                       refresh_every=0)      # the pool is compared / cloned below: keep it still
-  return env, sampler, task, rend
-
-
-def _model_pool(env, sampler, task, rend, seed):
-  spec = env._sampler_spec
-  subs = lowering.subtasks_of(task)
-  label_fns = [(lambda f, sub=sub: lowering._label_of(sub, sprite_lib.Sprite(**f))) for sub in subs]
-  to_rgb = rend['image']._color_to_rgb
-  return _sampler_model.sample_pool(spec, env.num_envs * env._episodes_per_env, env._max_sprites, seed,
-                                    to_rgb, label_fns, shapes.SHAPE_NAMES)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('case', sorted(CASES))
 def test_device_pool_matches_the_model_bit_for_bit(case):
-  env, sampler, task, rend = _make_env(case)
-  for refill in range(2):
-    sampler._draws -= 1
-    seed = sampler.next_seed()   # the key the last swb_sample_pool call used
-    want = _model_pool(env, sampler, task, rend, seed)
-    got = env.engine.get_pool()
-    for name in ('n_sprites', 'x', 'y', 'x_vel', 'y_vel', 'scale', 'cos_a', 'sin_a', 'angle', 'shape', 'rgb',
-                 'color', 'label'):
-      np.testing.assert_array_equal(getattr(got, name), want[name], err_msg='%s (refill %d)' % (name, refill))
-    assert np.array_equal(got.pool_base, np.arange(env.num_envs) * 3) and (got.pool_len == 3).all()
-    env.refill_pool()
-  env.close()
+  cases.pool_matches_the_model_case(case)
 
 
 @pytest.mark.gpu
 def test_shards_draw_the_episodes_of_the_whole_job():
-  """global_env_offset: two 24-env shards hold the same pool as one 48-env process (no repeated streams)."""
-  from spriteworld_amd import environment
-  whole, sampler, task, rend = _make_env('cobra_like', num_envs=48)
-  want = whole.engine.get_pool()
-  for rank in range(2):
-    s2, _, _ = CASES['cobra_like']()
-    shard = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25),
-                                           renderers=rend, init_sprites=s2, max_episode_length=6, num_envs=24,
-                                           episodes_per_env=3, global_env_offset=24 * rank)
-    got = shard.engine.get_pool()
-    sl = slice(72 * rank, 72 * (rank + 1))
-    for name in ('n_sprites', 'x', 'y', 'shape', 'rgb', 'label'):
-      np.testing.assert_array_equal(getattr(got, name), getattr(want, name)[sl], err_msg=name)
-    shard.close()
-  whole.close()
+  cases.shards_case()
 
 
 @pytest.mark.gpu
@@ -354,7 +198,7 @@ def test_sampled_environment_steps_like_one_built_from_the_same_pool():
   """Stepping a device-sampled pool == stepping the same pool uploaded from the host (swb_set_pool)."""
   import torch
   from spriteworld_amd import engine as engine_lib
-  env, sampler, task, rend = _make_env('cobra_like', num_envs=64, episodes_per_env=2)
+  env, sampler, task, rend = cases.make_env('cobra_like', num_envs=64, episodes_per_env=2)
   pool = env.engine.get_pool()
   twin = engine_lib.Engine(env._cfg, pool)
   g = torch.Generator(device='cpu').manual_seed(5)
@@ -377,8 +221,8 @@ def test_sampled_environment_steps_like_one_built_from_the_same_pool():
 @pytest.mark.gpu
 def test_device_reset_option_reads_the_generator_closures():
   from spriteworld_amd import environment
-  from tests import test_host_api
-  config = test_host_api._cobra_like_config(n_targets=2, n_distractors=1)
+  from tests import _surface_cases
+  config = _surface_cases._cobra_like_config(n_targets=2, n_distractors=1)
   env = environment.BatchedEnvironment(num_envs=256, episodes_per_env=4, device_reset=True, **config)
   assert env._sampler is not None and env._sampler.max_sprites == 3
   pool = env.engine.get_pool()
@@ -392,7 +236,7 @@ def test_device_reset_option_reads_the_generator_closures():
   ts = single.reset()
   assert ts.first() and ts.observation['image'].shape == (64, 64, 3)
   single.close()
-  config['init_sprites'] = lambda: test_host_api._cobra_like_config()['init_sprites']()
+  config['init_sprites'] = lambda: _surface_cases._cobra_like_config()['init_sprites']()
   with pytest.raises(lowering.LoweringError):
     environment.BatchedEnvironment(num_envs=4, device_reset=True, **config)
   env = environment.BatchedEnvironment(num_envs=4, device_reset='auto', **config)     # host fallback
@@ -402,32 +246,7 @@ def test_device_reset_option_reads_the_generator_closures():
 
 @pytest.mark.gpu
 def test_refresh_pool_redraws_everything_but_the_live_entries():
-  import torch
-  env, sampler, task, rend = _make_env('cobra_like', num_envs=64, episodes_per_env=4)
-  env.reset()
-  for _ in range(9):                      # max_episode_length = 6: every env is in its 2nd episode
-    env.step(env.sample_actions())
-  before = env.engine.get_pool()
-  st = env.state()
-  frame = env.observation()['image'].clone()
-  env.refresh_pool()
-  after = env.engine.get_pool()
-  live = st['pool_entry']
-  assert np.array_equal(live // 4, np.arange(64))
-  changed = (before.x != after.x).any(axis=1)
-  assert not changed[live].any() and changed[np.setdiff1d(np.arange(256), live)].all()
-  st2 = env.state()
-  assert np.array_equal(st2['step_count'], st['step_count']) and np.array_equal(st2['x'], st['x'])
-  assert torch.equal(env.observation()['image'], frame)             # nothing visible changed
-  # stepping on: the next episodes come from the refreshed entries
-  for _ in range(8):                      # a LAST and the FIRST after it, for every environment
-    env.step(env.sample_actions())
-  st3 = env.state()
-  moved = st3['pool_entry'] != live
-  assert moved.all()
-  np.testing.assert_array_equal(env.engine.get_pool().shape[st3['pool_entry']], after.shape[st3['pool_entry']])
-  env.check()
-  env.close()
+  cases.refresh_case()
 
 
 @pytest.mark.gpu
@@ -440,7 +259,7 @@ def test_refresh_every_keeps_episodes_fresh(refresh_every, early_ends):
   the 40 steps made an environment wrap to an entry not yet redrawn, and the test failed once in a while.)"""
   from spriteworld_amd import environment
   np.random.seed(11)
-  sampler, task, rend = _cobra_like()
+  sampler, task, rend = cases._cobra_like()
   if not early_ends:
     task = tasks.FindGoalPosition(filter_distrib=distribs.Continuous('c0', 0., 0.4), terminate_distance=1e-9)
   else:
@@ -470,7 +289,7 @@ def test_refresh_every_keeps_episodes_fresh(refresh_every, early_ends):
 
 @pytest.mark.gpu
 def test_refill_draws_new_statistically_uniform_episodes():
-  env, sampler, task, rend = _make_env('cobra_like', num_envs=2048, episodes_per_env=4)
+  env, sampler, task, rend = cases.make_env('cobra_like', num_envs=2048, episodes_per_env=4)
   a = env.engine.get_pool()
   env.refill_pool()
   b = env.engine.get_pool()
@@ -539,73 +358,13 @@ def test_model_matches_the_reference_generators_statistically():
   assert stats.chisquare(got_shapes[nz] * (ref_shapes[nz].sum() / got_shapes[nz].sum()), ref_shapes[nz]).pvalue > 1e-3
 
 
-def _mixed_scale_env(monkeypatch=None, emulated=False):
-  """Two groups whose `scale` factors have different types: Continuous (np.float32 in the reference) and Discrete (Python
-  floats, one of them exactly representable in float32), shuffled so that a slot's group differs from episode to episode."""
-  from spriteworld_amd import environment
-  if emulated:
-    from tests import _emu_engine
-    monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuTorchEngine)
-  common = [distribs.Continuous('x', 0.2, 0.8), distribs.Continuous('y', 0.2, 0.8), distribs.Discrete('shape', ['square', 'triangle']),
-            distribs.Continuous('c0', 0., 1.), distribs.Continuous('c1', 0.5, 1.), distribs.Continuous('c2', 0.9, 1.)]
-  cont = distribs.Product(common + [distribs.Continuous('scale', 0.3, 0.5), distribs.Continuous('angle', 0, 360, dtype='int32')])
-  disc = distribs.Product(common + [distribs.Discrete('scale', [0.1, 0.25]), distribs.Discrete('angle', [0., 45.])])
-  sampler = device_sampler.DeviceSampler([(cont, 2), (disc, 2)], shuffle=True, seed=4)
-  rend = {'image': renderer_lib.PILRenderer(image_size=(32, 32), anti_aliasing=2, color_to_rgb=renderer_lib.hsv_to_rgb)}
-  return environment.BatchedEnvironment(task=tasks.NoReward(), action_space=action_spaces.SelectMove(scale=0.25), renderers=rend,
-                                        init_sprites=sampler, max_episode_length=50, num_envs=24, episodes_per_env=2, refresh_every=0)
-
-
-def _check_recorded_types(env):
-  """swb_pool::attr_f32 as the sampler recorded it: a scale is np.float32 exactly when its group draws it from a Continuous
-  distribution -- read per live sprite (swb_get_sprite_types) and for the whole pool (swb_get_pool) -- and the setters take
-  their difference in that type (round-3 advice: a Discrete 0.25 is float32-representable and was guessed to be float32)."""
-  env.reset()
-  pool = env.engine.get_pool()
-  from_cont = pool.scale >= 0.3
-  assert ((pool.attr_f32 & 2) != 0).tolist() == from_cont.tolist()
-  assert ((pool.attr_f32 & 1) != 0).sum() == 0                     # integer degrees and Discrete angles: never float32
-  seen = set()
-  for e in range(env.num_envs):
-    entry = env.engine.env_state(e)['pool_entry']
-    for k in range(4):
-      angle_f32, scale_f32 = env.engine.sprite_types(e, k)
-      assert scale_f32 == bool(from_cont[entry, k]) and not angle_f32
-      seen.add((scale_f32, float(pool.scale[entry, k]) == 0.25))
-  assert (True, False) in seen and (False, True) in seen
-  # the setter's delta: float32 subtraction for the Continuous sprite, float64 for the Discrete one -- the reference's arithmetic
-  for e in range(6):
-    entry = env.engine.env_state(e)['pool_entry']
-    for k in range(4):
-      old = pool.scale[entry, k]
-      live = env.sprites(e)[k]
-      live.scale = 0.37
-      want = float(np.float32(0.37 - np.float32(old))) if from_cont[entry, k] else 0.37 - float(old)
-      path = live.centered_path
-      base = shapes.SHAPES[live.shape]
-      # sprite.py:171-175: the current path (scale `old`) scaled by the DIFFERENCE; the first vertex tells the factor
-      got = env.engine.get_sprite(e, k)
-      assert got['scale'] == 0.37
-      ref = _scaled_path(base, float(old), float(pool.angle[entry, k]), want)
-      assert np.array_equal(path, ref), (e, k, from_cont[entry, k])
-
-
-def _scaled_path(base, scale, angle, delta):
-  """matplotlib's arithmetic of Sprite._reset_centered_path followed by the scale setter (sprite.py:96-101,171-175)."""
-  from matplotlib import path as mpl_path
-  from matplotlib import transforms as mpl_transforms
-  p = (mpl_transforms.Affine2D().scale(scale) + mpl_transforms.Affine2D().rotate_deg(angle)).transform_path(mpl_path.Path(base))
-  return mpl_transforms.Affine2D().scale(delta).transform_path(p).vertices
-
-
 def test_emulated_sampler_records_the_type_of_every_scale(monkeypatch):
-  env = _mixed_scale_env(monkeypatch, emulated=True)
-  _check_recorded_types(env)
-  env.close()
+  from spriteworld_amd import environment
+  from tests import _emu_engine
+  monkeypatch.setattr(environment._engine, 'Engine', _emu_engine.EmuTorchEngine)
+  cases.recorded_scale_types_case()
 
 
 @pytest.mark.gpu
 def test_device_sampler_records_the_type_of_every_scale():
-  env = _mixed_scale_env()
-  _check_recorded_types(env)
-  env.close()
+  cases.recorded_scale_types_case()

@@ -3,12 +3,13 @@
 Both sides consume the same `SwbConfig`, the same pool arrays and the same
 actions.  Bar (BASELINE.json north_star): sprite positions, step types,
 discounts, success flags bit-exact; frames within +-1 LSB (we require +-0);
-rewards bit-exact.
+rewards bit-exact.  The bar is tests/_parity.py; the scenarios that are more than one
+`_parity.run` call are in tests/_kernel_cases.py, shared with tests/test_emulated_kernel.py.
 """
 import numpy as np
 import pytest
 
-from spriteworld_amd import workloads
+from tests import _kernel_cases as cases
 from tests import _parity
 
 pytestmark = pytest.mark.gpu
@@ -166,28 +167,9 @@ def test_cost_ordered_dispatch_files_every_column_group(name, aa, n_envs):
 @pytest.mark.parametrize('name,n_envs,aa', [('cluster_s5', 33, 5), ('cluster_s5', 6000, 5), ('embodied_s12', 300, 5), ('ragged_s16', 257, 5),
                                             ('geom_128x128', 700, 1), ('sorting_s4', 1001, 5), ('cluster_s5', 6000, 1), ('tiny_s6', 333, 1)])
 def test_cover_launches_in_cost_order(monkeypatch, name, n_envs, aa):
-  """Launches of more than one round of cover waves (6000 environments here) take the environments in order of what their cover
-  wave cost in the previous launch; SWB_COVER_ORDER asks for it at any batch size.  The order is only used after a launch that
-  filed every environment (a step without an observation in between: one launch in plain order)."""
-  from oracle import oracle
-  from spriteworld_amd import engine
+  """6000 environments: more than one round of cover waves."""
   monkeypatch.setenv('SWB_COVER_ORDER', '1')
-  _run(name, n_envs, 4, aa)
-  cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=1, anti_aliasing=aa)
-  ora, eng = oracle.Engine(cfg, pool), engine.Engine(cfg, pool)
-  rng = np.random.default_rng(7)
-  for t in range(6):
-    a = sample(rng)
-    want = ora.step(a)
-    eng.step(a, render=(t != 2))                     # launch 2 renders nothing and files nothing
-    if t == 2:
-      continue
-    got = eng.outputs_host()
-    assert not got['error'].any()
-    np.testing.assert_array_equal(got['step_type'], want['step_type'])
-    np.testing.assert_array_equal(_parity.bits(eng.state()['x']), _parity.bits(ora.state()['x']))
-    assert np.array_equal(got['obs'], want['obs']), t
-  eng.close()
+  cases.cover_cost_order_case(_engine, name, n_envs, aa)
 
 
 @pytest.mark.parametrize('shift', ['1', '2', '5'])
@@ -209,56 +191,20 @@ def test_without_cost_ordered_dispatch(monkeypatch):
 
 
 def test_run_list_overflow_is_flagged(monkeypatch):
-  from spriteworld_amd import _abi, engine
-  monkeypatch.setenv('SWB_RUN_CAP', '24')
-  monkeypatch.setenv('SWB_ARENA_UNITS', '0')             # (no arena for an outgrown list to move to)
-  cfg, pool, sample = workloads.build('cluster_s5', 64, episodes_per_env=2, seed=0, anti_aliasing=5)
-  eng = engine.Engine(cfg, pool)
-  eng.step(sample(np.random.default_rng(0)))
-  assert (eng.outputs_host()['error'] & _abi.ENV_ERR_SPAN_OVERFLOW).all()
-  eng.close()
+  cases.run_list_overflow_case(_engine, monkeypatch, [('cluster_s5', 5)], run_cap=24, n_envs=64, steps=1, quantifier=np.all)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('run_cap,bands', [(8, 1), (12, 4), (40, 2), (64, 8)])
 def test_run_lists_that_outgrow_their_part_move_to_the_arena(monkeypatch, run_cap, bands):
-  """Round 6: with an own part of 8 .. 64 units every run list outgrows it and moves to a segment of the shared arena (several
-  times); nothing changes in what the step returns -- both second kernels (resample, fill), every band count, 12 sprites at
-  128x128 included."""
-  monkeypatch.setenv('SWB_RUN_CAP', str(run_cap))
-  monkeypatch.setenv('SWB_ARENA_UNITS', str(1 << 22))
-  monkeypatch.setenv('SWB_BANDS', str(bands))
-  monkeypatch.setenv('SWB_BAND_TASKS', '1')         # (a moving list shifts the band starts it has recorded -- and their copy in LDS)
-  _run('cluster_s5', 96, 4, 5)
-  _run('embodied_s12', 24, 3, 5)
-  monkeypatch.setenv('SWB_NO_PAINT_IN_COVER', '1')
-  _run('geom_160x48', 33, 3, 1)
+  """12 sprites at 128x128 included."""
+  cases.arena_move_case(_engine, monkeypatch, [('cluster_s5', 96, 4, 5), ('embodied_s12', 24, 3, 5), ('geom_160x48', 33, 3, 1)], run_cap, bands,
+                        1 << 22, episodes_per_env=3, seed=0, rng_seed=100)
 
 
 @pytest.mark.gpu
 def test_run_lists_are_trimmed_after_the_third_rendering_launch():
-  """The hand-off lists start with room for any scene of convex sprites and are cut to 1.25 x the longest list written (+ the
-  arena) by the engine's third rendering step; frames stay exact across the cut (compared with the oracle every step)."""
-  from oracle import oracle
-  from spriteworld_amd import engine
-  for name, n_envs in (('embodied_s12', 256), ('cluster_s5', 1024)):
-    cfg, pool, sample = workloads.build(name, n_envs, episodes_per_env=3, seed=4, anti_aliasing=5)
-    eng, ora = engine.Engine(cfg, pool), oracle.Engine(cfg, pool)
-    rng = np.random.default_rng(8)
-    sizes = []
-    for t in range(6):
-      a = sample(rng)
-      want = ora.step(a)
-      eng.step(a)
-      got = eng.outputs_host()
-      assert not got['error'].any()
-      assert np.array_equal(got['obs'], want['obs']), (name, t)
-      v = eng.variant()
-      sizes.append((v['run_cap'], v['run_list_bytes']))
-    worst = max(4, cfg.max_sprites + 1) * cfg.anti_aliasing * cfg.image_w + 1
-    assert sizes[0][0] == sizes[1][0] == worst and sizes[2][0] < worst // 2 and sizes[-1] == sizes[2], sizes
-    assert sizes[2][1] < sizes[1][1] // 2, sizes
-    eng.close()
+  cases.trim_case(_engine, [('embodied_s12', 256, 5), ('cluster_s5', 1024, 5)], seed=4, rng_seed=8, steps=6, total_halves=True)
 
 
 @pytest.mark.parametrize('name,n_envs', [('cluster_s5', 64), ('tiny_s6', 48), ('wide_s4', 32), ('ragged_s16', 96)])
@@ -273,42 +219,4 @@ def test_fill_kernel_for_narrow_images(monkeypatch, name, n_envs):
 @pytest.mark.parametrize('f32', [True, False], ids=['f32pos', 'f64pos'])
 @pytest.mark.parametrize('name', __import__('tests._position_cases', fromlist=['CASES']).CASES)
 def test_tasks_that_filter_on_position(name, f32):
-  """Round 6: task filters / cluster distributions keyed on x, y -- the reference re-evaluates `contains(sprite.factors)` at
-  every step (tasks.py:134-137, 196-205); the kernel looks every sprite's label up in the cell of the task's position grid it
-  stands in.  HIP engine against the oracle (which tests/test_oracle_vs_reference.py pins against the unmodified reference on
-  these very cases; tests/golden/position_*.npz are the reference's own outputs, checked in tests/test_golden.py)."""
-  from oracle import oracle
-  from spriteworld_amd import engine, lowering
-  from tests import _position_cases as pc
-  ns = pc.namespace_of_mirrors()
-  task, aspace, rends, keep, max_len = pc.environment_parts(ns, name)
-  n_envs = 96
-  episodes = pc.episodes_of(ns, name, f32, n_episodes=3 * n_envs)
-  cfg = lowering.lower_config(task, aspace, rends, keep, max_len, n_envs, pc.N_SPRITES, pos_is_f32=f32)
-  pool = lowering.lower_episodes(episodes, task, rends, max_sprites=pc.N_SPRITES).assign_round_robin(n_envs, 3)
-  ora, eng = oracle.Engine(cfg, pool), engine.Engine(cfg, pool)
-  rng = np.random.default_rng(11)
-  sticky = np.zeros(n_envs, np.uint8)
-  flips, prev = 0, None
-  for t in range(40):
-    a = rng.uniform(0.0, 1.0, size=(n_envs, 4))
-    st = ora.state()
-    for i in range(0, n_envs, 2):                      # click ON a sprite in every second environment
-      k = int(rng.integers(0, max(int(st['n_sprites'][i]), 1)))
-      a[i, 0], a[i, 1] = st['x'][i, k], st['y'][i, k]
-    want = ora.step(a)
-    eng.step(a)
-    got = eng.outputs_host()
-    np.testing.assert_array_equal(got['step_type'], want['step_type'])
-    np.testing.assert_array_equal(got['success'], want['success'])
-    assert np.array_equal(np.isnan(got['reward']), np.isnan(want['reward']))
-    ok = ~np.isnan(want['reward'])
-    np.testing.assert_array_equal(got['reward'][ok].view(np.uint64), want['reward'][ok].view(np.uint64))
-    sticky |= want['error']
-    np.testing.assert_array_equal(got['error'], sticky)
-    np.testing.assert_array_equal(got['obs'], want['obs'])
-    if prev is not None:
-      flips += int((want['reward'] != prev).sum())
-    prev = want['reward']
-  assert flips > 200
-  eng.close()
+  cases.position_filter_case(_engine, name, f32, n_envs=96, min_flips=200)

@@ -2,29 +2,13 @@
 import numpy as np
 import pytest
 
-from spriteworld_amd import _abi, action_spaces, lanczos, lowering, renderers, sprite_generators, tasks
+from spriteworld_amd import _abi, action_spaces, lanczos, lowering, renderers, tasks
 from spriteworld_amd import factor_distributions as distribs
 from spriteworld_amd.sprite import Sprite
+from tests import _surface_cases as cases
+from tests._surface_cases import _cobra_like_config
 
 
-def _cobra_like_config(n_targets=2, n_distractors=1):
-  shared = distribs.Product([
-      distribs.Continuous('x', 0.1, 0.9), distribs.Continuous('y', 0.1, 0.9),
-      distribs.Discrete('shape', ['square', 'triangle', 'circle']), distribs.Discrete('scale', [0.13]),
-      distribs.Continuous('c1', 0.3, 1.), distribs.Continuous('c2', 0.9, 1.)])
-  target_hue, distractor_hue = distribs.Continuous('c0', 0., 0.4), distribs.Continuous('c0', 0.5, 0.9)
-  gen = sprite_generators.shuffle(sprite_generators.chain_generators(
-      sprite_generators.generate_sprites(distribs.Product([target_hue, shared]), num_sprites=n_targets),
-      sprite_generators.generate_sprites(distribs.Product([distractor_hue, shared]), num_sprites=n_distractors)))
-  return {
-      'task': tasks.FindGoalPosition(filter_distrib=target_hue, terminate_distance=0.075),
-      'action_space': action_spaces.SelectMove(scale=0.25),
-      'renderers': {'image': renderers.PILRenderer(image_size=(64, 64), anti_aliasing=5,
-                                                   color_to_rgb=renderers.hsv_to_rgb)},
-      'init_sprites': gen,
-      'max_episode_length': 20,
-      'metadata': {'name': 'test', 'mode': 'train'},
-  }
 
 
 def test_sprite_factors_and_position_dtype():
@@ -125,55 +109,12 @@ def test_batched_environment_runs_a_config():
 
 @pytest.mark.gpu
 def test_single_environment_follows_example_run_loop():
-  """example_run_loop.py:62-80: reset(), step(action_space.sample()) until last(), log success."""
-  from spriteworld_amd import environment
-  np.random.seed(3)
-  config = _cobra_like_config()
-  config['renderers']['success'] = renderers.Success()
-  env = environment.Environment(**config)
-  for _ in range(3):
-    timestep = env.reset()
-    assert timestep.first() and timestep.reward is None and timestep.discount is None
-    rewards, n = [], 0
-    while not timestep.last():
-      timestep = env.step(env.action_space.sample())
-      rewards.append(timestep.reward)
-      n += 1
-    assert n <= 20 and timestep.discount == 0.0
-    assert isinstance(timestep.observation['success'], bool)
-    assert timestep.observation['image'].shape == (64, 64, 3) and np.isfinite(np.nanmean(rewards))
-  env.close()
+  cases.single_environment_run_loop_case()
 
 
 @pytest.mark.gpu
 def test_sprite_factors_observation_and_action_noise():
-  """handcrafted.SpriteFactors as a batched tensor, and SelectMove(noise_scale=...) noise."""
-  import torch
-  from spriteworld_amd import environment, shapes
-  np.random.seed(4)
-  config = _cobra_like_config()
-  config['renderers'] = {'factors': renderers.SpriteFactors(), 'xy': renderers.SpriteFactors(factors=('y', 'x', 'shape'))}
-  config['action_space'] = action_spaces.SelectMove(scale=0.25, noise_scale=0.05)
-  env = environment.BatchedEnvironment(num_envs=32, episodes_per_env=2, device_reset=False, **config)   # host pool: compared below
-  env.seed_noise(0)
-  ts = env.reset()
-  f = ts.observation['factors'].cpu().numpy()
-  assert f.shape == (32, 3, 10) and ts.observation['xy'].shape == (32, 3, 3)
-  pool, st = env.engine.pool, env.state()
-  for n in range(32):
-    e = st['pool_entry'][n]
-    assert np.array_equal(f[n, :, 0], st['x'][n]) and np.array_equal(f[n, :, 1], st['y'][n])
-    assert np.array_equal(f[n, :, 2], pool.shape[e] + 1) and np.array_equal(f[n, :, 4], pool.scale[e])
-    assert np.array_equal(f[n, :, 5:8], pool.color[e]) and np.array_equal(f[n, :, 3], pool.angle[e])
-  assert np.array_equal(ts.observation['xy'].cpu().numpy(), f[:, :, [1, 0, 2]])
-  # noise: the same clean action moves sprites by different amounts in different environments
-  a = np.tile(np.array([[0.5, 0.5, 0.9, 0.9]]), (32, 1))
-  env.engine.set_positions(np.full((32, 3), 0.5), np.full((32, 3), 0.5))
-  ts = env.step(a)
-  moved = ts.observation['factors'][:, 2, 0].cpu().numpy() - 0.5
-  hit = moved != 0                      # a noised click may miss the sprite
-  assert hit.sum() >= 8 and np.all(np.abs(moved[hit] - 0.1) < 0.1) and np.std(moved[hit]) > 1e-3
-  env.close()
+  cases.sprite_factors_and_action_noise_case()
 
 
 @pytest.mark.gpu

@@ -1,86 +1,40 @@
 """Pins the oracle against the UNMODIFIED reference imported from /root/reference (build
 container only; skipped where the reference tree is absent, e.g. on the GPU box)."""
-import copy
 import importlib
 
 import numpy as np
 import pytest
 
 from oracle import ref_harness
+from tests import _parity
+from tests import _reference_cases
+from tests._reference_cases import CONFIGS, fresh_episodes
 
 pytestmark = pytest.mark.skipif(not ref_harness.reference_available(),
                                 reason='reference tree not present')
 
-_MODULES = [
-    'spriteworld.configs.cobra.goal_finding_new_position',
-    'spriteworld.configs.cobra.goal_finding_new_shape',
-    'spriteworld.configs.cobra.goal_finding_more_distractors',
-    'spriteworld.configs.cobra.goal_finding_more_targets',
-    'spriteworld.configs.cobra.clustering',
-    'spriteworld.configs.cobra.sorting',
-    'spriteworld.configs.cobra.exploration',
-    'spriteworld.configs.examples.goal_finding_embodied',
-    'spriteworld.configs.examples.goal_finding_clustering',
-]
-# every shipped config in both modes (tests/configs/configs_test.py:33-58 runs the same grid)
-CONFIGS = [(m, mode) for m in _MODULES for mode in ('train', 'test')]
 
+class _OracleAsEngine(object):
+  """The oracle behind the four members tests/_reference_cases.side_by_side drives an engine through."""
 
-def _fresh_episodes(episodes):
-  """What the reference's init_sprites must return to follow the pool: the constructor's own draw
-  (environment.py:68), then the episodes in order, wrapping around, as NEW sprite objects every time."""
-  yield copy.deepcopy(episodes[0])
-  while True:
-    for e in episodes:
-      yield copy.deepcopy(e)
+  def __init__(self, cfg, pool):
+    from oracle import oracle
+    self._ora = oracle.Engine(cfg, pool)
+    self.state = self._ora.state
 
+  def step(self, actions):
+    self._out = self._ora.step(actions)
 
-def _bits(v):
-  return np.float64(v).view(np.uint64)
+  def outputs_host(self):
+    return self._out
+
+  def close(self):
+    pass
 
 
 @pytest.mark.parametrize('module,mode', CONFIGS)
-def test_oracle_equals_reference_environment(module, mode, capsys):
-  ref_harness.load_reference()
-  from spriteworld import environment
-  from spriteworld import renderers as ref_renderers
-  from oracle import oracle
-  from spriteworld_amd import lowering
-  seed, n_eps, n_steps = 21, 30, 250
-  with capsys.disabled():
-    pass
-  np.random.seed(seed)
-  config = importlib.import_module(module).get_config(mode)
-  episodes = [config['init_sprites']() for _ in range(n_eps)]
-  task, aspace, rends = config['task'], config['action_space'], config['renderers']
-  S = max(len(e) for e in episodes)
-  cfg = lowering.lower_config(task, aspace, rends, True, config['max_episode_length'], 1, S,
-                              pos_is_f32=(lowering.position_dtype(episodes) == np.float32))
-  pool = lowering.lower_episodes(episodes, task, rends, max_sprites=S).assign_round_robin(1)
-  eng = oracle.Engine(cfg, pool)
-  it = _fresh_episodes(episodes)
-  config = dict(config, init_sprites=lambda: next(it))
-  config['renderers'] = dict(rends, success=ref_renderers.Success())
-  env = environment.Environment(**config)
-  rng = np.random.RandomState(seed + 1)
-  for t in range(n_steps):
-    if cfg.action_space == 2:
-      a = np.array([rng.randint(0, 2), rng.randint(0, 4)])
-      ts = env.step([int(a[0]), int(a[1])])
-    else:
-      a = rng.uniform(0, 1, 4)
-      ts = env.step(a)
-    out = eng.step(a[None])
-    assert int(ts.step_type) == int(out['step_type'][0]), t
-    r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r)
-    assert bool(ts.observation['success']) == bool(out['success'][0]), t
-    assert np.array_equal(ts.observation['image'], out['obs'][0]), t
-    st = eng.state()
-    pos = np.array([s.position for s in env._sprites], dtype=np.float64).reshape(-1, 2)
-    n = st['n_sprites'][0]
-    assert n == len(pos)
-    assert np.array_equal(pos[:, 0], st['x'][0, :n]) and np.array_equal(pos[:, 1], st['y'][0, :n]), t
+def test_oracle_equals_reference_environment(module, mode):
+  _reference_cases.side_by_side(_OracleAsEngine, module, mode, seed=21, n_eps=30, n_steps=250)
 
 
 def test_float64_sprites_and_motion_cost():
@@ -110,7 +64,7 @@ def test_float64_sprites_and_motion_cost():
     assert cfg.pos_is_f32 == 0
     pool = lowering.lower_episodes(episodes, task, rends, max_sprites=4).assign_round_robin(1)
     eng = oracle.Engine(cfg, pool)
-    it = _fresh_episodes(episodes)
+    it = fresh_episodes(episodes)
     env = environment.Environment(task=task, action_space=aspace, renderers=rends,
                                   init_sprites=lambda: next(it), keep_in_frame=False, max_episode_length=15)
     arng = np.random.RandomState(9)
@@ -120,7 +74,7 @@ def test_float64_sprites_and_motion_cost():
       out = eng.step(a[None])
       assert int(ts.step_type) == int(out['step_type'][0]), t
       r = np.nan if ts.reward is None else float(ts.reward)
-      assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r, out['reward'][0])
+      assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r, out['reward'][0])
       assert np.array_equal(ts.observation['image'], out['obs'][0]), t
 
 
@@ -151,7 +105,7 @@ def test_float32_actions_match_reference(module, mode, motion_cost):
   assert cfg.action_is_f32 == 1
   pool = lowering.lower_episodes(episodes, task, rends, max_sprites=S).assign_round_robin(1)
   eng = oracle.Engine(cfg, pool)
-  it = _fresh_episodes(episodes)
+  it = fresh_episodes(episodes)
   config = dict(config, init_sprites=lambda: next(it))
   config['renderers'] = dict(rends, success=ref_renderers.Success())
   env = environment.Environment(**config)
@@ -162,7 +116,7 @@ def test_float32_actions_match_reference(module, mode, motion_cost):
     out = eng.step(a[None])
     assert int(ts.step_type) == int(out['step_type'][0]), t
     r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r, out['reward'][0])
+    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r, out['reward'][0])
     assert np.array_equal(ts.observation['image'], out['obs'][0]), t
     pos = np.array([s.position for s in env._sprites], dtype=np.float64).reshape(-1, 2)
     st = eng.state()
@@ -198,7 +152,7 @@ def test_ragged_episodes_from_empty_to_sixteen_sprites(space):
   cfg = lowering.lower_config(task, aspace, rends, True, 6, 1, 16, pos_is_f32=True)
   pool = lowering.lower_episodes(episodes, task, rends, max_sprites=16).assign_round_robin(1)
   eng = oracle.Engine(cfg, pool)
-  it = _fresh_episodes(episodes)
+  it = fresh_episodes(episodes)
   env = environment.Environment(task=task, action_space=aspace, renderers=rends, init_sprites=lambda: next(it),
                                 max_episode_length=6)
   arng = np.random.RandomState(3)
@@ -212,7 +166,7 @@ def test_ragged_episodes_from_empty_to_sixteen_sprites(space):
     out = eng.step(a[None])
     assert int(ts.step_type) == int(out['step_type'][0]), t
     r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r, out['reward'][0])
+    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r, out['reward'][0])
     assert bool(ts.observation['success']) == bool(out['success'][0]), t
     st = eng.state()
     pos = np.array([sp.position for sp in env._sprites], dtype=np.float64).reshape(-1, 2)
@@ -305,7 +259,7 @@ def test_randomised_reference_configurations(seed):
                               pos_is_f32=(lowering.position_dtype(episodes) == np.float32))
   pool = lowering.lower_episodes(episodes, task, rends, max_sprites=S).assign_round_robin(1)
   eng = oracle.Engine(cfg, pool)
-  it = _fresh_episodes(episodes)
+  it = fresh_episodes(episodes)
   env = environment.Environment(task=task, action_space=aspace, renderers=rends, init_sprites=lambda: next(it),
                                 keep_in_frame=keep, max_episode_length=max_len)
   arng = np.random.RandomState(seed)
@@ -328,7 +282,7 @@ def test_randomised_reference_configurations(seed):
     assert not out['error'][0], t
     assert int(ts.step_type) == int(out['step_type'][0]), t
     r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r, out['reward'][0])
+    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r, out['reward'][0])
     assert bool(ts.observation['success']) == bool(out['success'][0]), t
     st = eng.state()
     pos = np.array([sp.position for sp in env._sprites], dtype=np.float64).reshape(-1, 2)
@@ -361,7 +315,7 @@ def test_tasks_that_filter_on_position_match_the_reference(name, f32):
   pool = lowering.lower_episodes(episodes, task, rends, max_sprites=pc.N_SPRITES).assign_round_robin(1)
   assert pool.cell_label is not None
   eng = oracle.Engine(cfg, pool)
-  it = _fresh_episodes(episodes)
+  it = fresh_episodes(episodes)
   env = environment.Environment(task=task, action_space=aspace, renderers=dict(rends, success=ref_renderers.Success()),
                                 init_sprites=lambda: next(it), keep_in_frame=keep, max_episode_length=max_len)
   rng = np.random.RandomState(77)
@@ -382,7 +336,7 @@ def test_tasks_that_filter_on_position_match_the_reference(name, f32):
     out = eng.step(a[None])
     assert int(ts.step_type) == int(out['step_type'][0]), t
     r = np.nan if ts.reward is None else float(ts.reward)
-    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _bits(r) == _bits(out['reward'][0]), (t, r, out['reward'][0])
+    assert (np.isnan(r) and np.isnan(out['reward'][0])) or _parity.bits(r) == _parity.bits(out['reward'][0]), (t, r, out['reward'][0])
     assert bool(ts.observation['success']) == bool(out['success'][0]), t
     assert np.array_equal(ts.observation['image'], out['obs'][0]), t
     # how often membership really changed inside an episode (the case must exercise what it is for)

@@ -11,7 +11,12 @@ import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests import test_gpu_parity as T  # noqa: E402
+from spriteworld_amd import engine  # noqa: E402
+from tests import _parity  # noqa: E402
+
+
+def _run(seed):
+  _parity.run(engine.Engine, 'fuzz_%d' % seed, 64, 10, 5, seed=seed)
 
 
 def main():
@@ -28,9 +33,9 @@ def main():
         from tests import _util
         n_big += 1
         with _util.swapped_shape('circle', shapes.polygon(33 + seed % 32)):
-          T._run('fuzz_%d' % seed, 64, 10, 5, seed=seed)
+          _run(seed)
       else:
-        T._run('fuzz_%d' % seed, 64, 10, 5, seed=seed)
+        _run(seed)
     except Exception:  # pylint: disable=broad-except
       bad.append(seed)
       out.write('seed %d FAILED\n%s\n' % (seed, traceback.format_exc()[-1500:]))

@@ -1,7 +1,7 @@
 import time, sys
 sys.path.insert(0, '.')
 import numpy as np, torch
-from tests import test_device_sampler as T
+from tests import _sampler_cases as T
 from spriteworld_amd import environment, action_spaces, sprite_generators
 sampler, task, rend = T._cobra_like()
 env = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25), renderers=rend,

@@ -2,7 +2,7 @@
 import sys, time
 sys.path.insert(0, '.')
 import numpy as np, torch
-from tests import test_device_sampler as T
+from tests import _sampler_cases as T
 from spriteworld_amd import environment, action_spaces, gym_wrapper
 sampler, task, rend = T._cobra_like()
 env = environment.BatchedEnvironment(task=task, action_space=action_spaces.SelectMove(scale=0.25), renderers=rend,
