@@ -321,8 +321,8 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream);
  * type and success, and the same auto-reset -- a candidate that reaches LAST plays FIRST on the next step, from pool entry
  * pool_base + (episode mod pool_len), as the live environment would (it is not stopped at its first LAST).
  * The handle is left as it was: positions, step counts, episodes, entries, reset flags, the pool, and the run lists and
- * dispatch bookkeeping of the render path; nothing is rendered.  N * M virtual environments step on a scratch copy of the
- * state (N * M * (16 * max_sprites + 32) bytes, owned by the handle, grown on demand); two kernels, asynchronous on `stream`
+ * dispatch bookkeeping of the render path; nothing is rendered (swb_rollout_frames below draws the end states).
+ * N * M virtual environments step on a scratch copy of the state (N * M * (16 * max_sprites + 32) bytes, owned by the handle, grown on demand); two kernels, asynchronous on `stream`
  * -- only growing the scratch (or, when K grows, the K per-step parameter blocks of 2 KB kept beside it) blocks.
  * Limits: M, K >= 1, N * M <= 2^24, K <= 65536; SWB_ERR_INVALID beyond them.
  * The scratch belongs to the handle: ONE stream at a time per handle.  A rollout must not be issued on another stream while an
@@ -340,6 +340,33 @@ typedef struct swb_rollout_outputs {   /* device memory, caller-owned; any point
   int32_t* n_sprites;  /* i32[N,M]    sprites of the episode the candidate ends in                     */
 } swb_rollout_outputs;
 int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream);
+
+/* Frames of a rollout: what the agent would SEE after step K of every candidate.  Renders the states the LAST swb_rollout of
+ * this handle left in its scratch; asynchronous on `stream`, which must be that rollout's stream or ordered with it (the
+ * scratch belongs to the handle).
+ *   cand_dev == NULL   obs_dev is u8[N, M, H, W, 3]: frame [n, m] is, to the byte, what swb_step number K would have written to
+ *                      swb_outputs::obs for environment n had the K steps been taken with actions[:, n, m].  A candidate whose
+ *                      step K was LAST shows its terminal sprites (as swb_render does of a live environment about to reset), one
+ *                      whose step K was FIRST the fresh episode.  error_dev: u8[N, M].
+ *   cand_dev i32[N]    (device) obs_dev is u8[N, H, W, 3]: the frame of candidate cand[n] of environment n only -- a planner's
+ *                      argmax, for the cost of one step's rendering.  A value outside [0, M) is CLAMPED into it (negative: 0,
+ *                      M and above: M - 1).  error_dev: u8[N].  One gather kernel (swb_rollout_pick_kernel) into a staging block
+ *                      of N environments owned by the handle, then one render launch; only growing that block blocks.
+ * error_dev may be NULL; else the swb_env_error bits of the render phases (SWB_ENV_ERR_SPAN_OVERFLOW) are ORed INTO it (sticky).
+ * M must equal the M of that rollout: it guards the size of the caller's buffers.
+ * How: the render path of the handle (tuned two-kernel, painting cover kernel, fill kernel, large frames, many sprites) with
+ * its state pointers moved to the scratch, in M chunks of N consecutive virtual environments v = n * M + m -- each chunk one
+ * launch like swb_render's: N is what the run lists, dispatch tables and overflow slots are sized for.  No kernel differs.
+ * Untouched: the live state, the pool, the caller's step outputs and sticky error buffer, any frame buffer but obs_dev.  The
+ * render path's dispatch bookkeeping (parity, phase, cost lists, which launch listed runs) advances as for swb_render --
+ * results never depend on it --, so swb_trim_run_lists called straight afterwards sizes the lists from candidate scenes: a
+ * list that outgrows its part moves to the arena, an exhausted arena is flagged in error_dev.  Never a counted step of
+ * swb_timing_enable.  Frames of intermediate steps k < K do not exist: the scratch holds the end states only.
+ * SWB_ERR_INVALID: null handle, obs_dev NULL, M different from the last rollout's.  SWB_ERR_STATE: no rollout has run on the
+ * handle; swb_set_pool, swb_sample_pool or swb_resample_pool was called since (a candidate may sit in an entry that was just
+ * redrawn: roll out again); swb_set_sprite_attr has been called on the handle (overrides are indexed by live environment, as
+ * for swb_rollout); shapes, pool or resampling tables missing. */
+int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev, void* stream);
 
 /* Random-agent actions drawn on the device: one action per environment, ready for swb_step, without a host round trip.
  * SWB_SAMPLE_UNIFORM is action_space.sample() (uniform in [0, 1)^4; Embodied: carry in {0, 1}, direction in {0 .. 3}).

@@ -237,6 +237,7 @@ PROTOTYPES = {
     'swb_render': (None, [_h, _p, _h]),
     'swb_evaluate': (None, [_h, _p, _h]),
     'swb_rollout': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _h]),
+    'swb_rollout_frames': (None, [_h, _i32, _p, _p, _p, _h]),
     'swb_sample_actions': (None, [_h, _i32, _u64, _u64, _P(SwbSampledActions), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_factors': (None, [_h, _p, _h]),

@@ -154,6 +154,11 @@ struct swb_engine {
   // swb_rollout: the scratch state of the virtual environments (one allocation, grown on demand)
   dev_buf<unsigned char> d_rollout;
   dev_buf<swb_params> d_rollout_steps;     // ... and the K per-step copies of swb_params swb_rollout_fork_kernel writes
+  // swb_rollout_frames: candidates of the last swb_rollout, whose end states the scratch holds (0: none has run); whether a
+  // pool call since then has made them describe entries that may have been redrawn; the staging block of picked candidates
+  int rollout_M = 0;
+  bool rollout_stale = false;
+  dev_buf<unsigned char> d_rollout_pick;
 };
 
 namespace {
@@ -372,6 +377,14 @@ swb_params bind_step(const swb_engine* h, const void* actions, const swb_outputs
   return p;
 }
 
+// swb_rollout_frames: the launch draws the environments of `view` (a chunk of N virtual environments of a rollout's scratch, or
+// the staging block of picked candidates) in place of the live ones.  Such a launch is never a counted step of swb_timing_enable.
+void bind_view(swb_params* p, const swb_state_view* view) {
+  if (!view) return;
+  p->x = view->x; p->y = view->y; p->nspr = view->nspr; p->entry = view->entry; p->step_count = view->step_count;
+  p->episode = view->episode; p->pool_base = view->pool_base; p->pool_len = view->pool_len; p->reset_next = view->reset_next;
+}
+
 // Launch configuration of cover build `fn` of variant `v`: the dynamic LDS of a wave, and how the kernel finds its way in it.
 int cover_launch_config(const swb_engine* h, const variant* v, kernel_fn fn, swb_params* p, size_t* lds_out) {
   int cpath_in_masks = 0;
@@ -426,10 +439,12 @@ bool paints_in_cover(const swb_engine* h, const variant* v, bool honour_switch =
   return h->p.AA == 1 && h->p.ncg == 1 && v && v->fn_paint && !(honour_switch && h->no_paint_in_cover);
 }
 
-int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream);
+int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
+                 const swb_state_view* view);
 
-int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
-  if (h->large_frames) return launch_large(h, actions, out, render_only, stream);
+int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
+           const swb_state_view* view = nullptr) {
+  if (h->large_frames) return launch_large(h, actions, out, render_only, stream, view);
   if (int rc = check_ready(h, actions, render_only)) return rc;
   const variant* v = pick_variant(h->p.Wc);
   if (!v) return fail(SWB_ERR_INVALID, "canvas %dx%d not supported", h->p.Wc, h->p.Hc);
@@ -437,6 +452,7 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   int vs = 0;
   const kernel_fn fn2 = pick_resample(h->p.AA, h->vslots, &vs);
   swb_params p = bind_step(h, actions, out, render_only);
+  bind_view(&p, view);
   if (p.v_tab && vs == 8) {                                           // slot tables of this VS
     p.v_tab += (size_t)p.Hc * SWB_VSLOTS;
     p.v_pfx += (size_t)(p.Hc + 1) * SWB_VSLOTS;
@@ -501,7 +517,7 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   h->lists_valid = p.obs && !p.paint_in_cover;
   h->launch_phase = (h->launch_phase + 1) % 3;
   h->launch_parity ^= 1;
-  return timer.end(true);
+  return timer.end(view == nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -566,9 +582,11 @@ int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
   return 0;
 }
 
-int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream) {
+int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
+                 const swb_state_view* view) {
   if (int rc = check_ready(h, actions, render_only)) return rc;
   swb_params p = bind_step(h, actions, out, render_only);
+  bind_view(&p, view);
   // the state phase: the cover kernel of the narrowest build with obs = NULL, or (many sprites) swb_ms_state_kernel, whose LDS
   // does not depend on the scene
   kernel_fn fn;
@@ -592,7 +610,7 @@ int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int
   if (int rc = timer.mid()) return rc;
   if (p.obs && render_only != 2)
     if (int rc = lf_render(h, p, stream)) return rc;
-  return timer.end(render_only != 2);          // (swb_evaluate: not a timed launch, as on the tuned path)
+  return timer.end(render_only != 2 && !view); // (swb_evaluate: not a timed launch, as on the tuned path)
 }
 
 // swb_upload_resample of a large-frame handle: the raw Pillow tables, and per output column the prefix sums of its
@@ -979,6 +997,7 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
   for (size_t i = 0; i < PS; ++i)
     if (pool->shape[i] < 0 || (h->have_shapes && pool->shape[i] >= SWB_MAX_SHAPES)) return fail(SWB_ERR_INVALID, "bad shape index in pool");
   int rc = 0;
+  h->rollout_stale = true;                        // (swb_rollout_frames: a candidate may sit in an entry that is replaced here)
   rc |= h->d_p_n.fill(pool->n_sprites, P);
   rc |= h->d_p_x.fill(pool->x, PS); rc |= h->d_p_y.fill(pool->y, PS);
   rc |= h->d_p_xv.fill(pool->x_vel, PS); rc |= h->d_p_yv.fill(pool->y_vel, PS);
@@ -1089,6 +1108,7 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
       return fail(SWB_ERR_INVALID, "env %d: pool range [%d, +%d) outside the pool of %d", i, pool_base_host[i], pool_len_host[i], P);
   const size_t PS = (size_t)P * S;
   int rc = 0;
+  h->rollout_stale = true;                        // (swb_rollout_frames: as in swb_set_pool)
   if (h->pool_entries != P || !h->d_p_angle || !h->d_p_color) {
     rc |= h->d_p_n.fill(nullptr, P);
     rc |= h->d_p_x.fill(nullptr, PS); rc |= h->d_p_y.fill(nullptr, PS);
@@ -1128,6 +1148,7 @@ int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* s
   if (!h->pool_uniform)
     return fail(SWB_ERR_STATE, "swb_resample_pool needs the env-major layout pool_base[n] = n * pool_len, equal pool_len");
   HIP_TRY(hipSetDevice(h->device));
+  h->rollout_stale = true;      // (swb_rollout_frames: only entries the LIVE environments play are kept, a candidate's may be redrawn)
   const swb_sampler_args a = sampler_args(h, seed, first_entry, true);
   hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((h->pool_entries + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
@@ -1201,6 +1222,18 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream) {
 // swb_rollout_kernel steps them K times.  Neither touches the live state, the run lists or the dispatch bookkeeping of launch().
 #define SWB_ROLLOUT_MAX_VENVS (1 << 24)      // N * M: one workgroup each, and N * M * S fits an int
 #define SWB_ROLLOUT_MAX_STEPS (1 << 16)      // K: one copy of swb_params each
+// The state arrays of `nv` environments of S sprites in a block of nv * (16 * S + 32) bytes: the rollout's scratch, and the
+// staging block of swb_rollout_frames' picked candidates.
+static swb_state_view rollout_state_view(unsigned char* base, size_t nv, size_t S) {
+  swb_state_view v;
+  v.x = reinterpret_cast<double*>(base);
+  v.y = v.x + nv * S;
+  v.nspr = reinterpret_cast<int32_t*>(v.y + nv * S);
+  v.entry = v.nspr + nv; v.step_count = v.entry + nv; v.episode = v.step_count + nv;
+  v.pool_base = v.episode + nv; v.pool_len = v.pool_base + nv;
+  v.reset_next = reinterpret_cast<uint8_t*>(v.pool_len + nv);      // (nv bytes of the last 8 nv)
+  return v;
+}
 int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "swb_rollout: M and K must be positive (M = %d, K = %d)", M, K);
@@ -1218,6 +1251,7 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
   const hipStream_t st = (hipStream_t)stream;
   const size_t NV = (size_t)p.N * M, S = (size_t)p.S;
   const size_t bytes = NV * (16 * S + 32);
+  h->rollout_M = 0;                          // (until both kernels are in the stream, the scratch holds no rollout's end states)
   if (bytes > h->d_rollout.count || (size_t)K > h->d_rollout_steps.count) {   // (the one blocking case: an earlier rollout may still use the old scratch)
     HIP_TRY(hipStreamSynchronize(st));
     if (bytes > h->d_rollout.count && h->d_rollout.fill(nullptr, bytes)) return SWB_ERR_HIP;
@@ -1226,12 +1260,9 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
   swb_rollout_args a;
   memset(&a, 0, sizeof(a));
   a.M = M; a.K = K;
-  a.x = reinterpret_cast<double*>(h->d_rollout.ptr);
-  a.y = a.x + NV * S;
-  a.nspr = reinterpret_cast<int32_t*>(a.y + NV * S);
-  a.entry = a.nspr + NV; a.step_count = a.entry + NV; a.episode = a.step_count + NV;
-  a.pool_base = a.episode + NV; a.pool_len = a.pool_base + NV;
-  a.reset_next = reinterpret_cast<uint8_t*>(a.pool_len + NV);      // (NV bytes of the last 8 NV)
+  const swb_state_view sv = rollout_state_view(h->d_rollout.ptr, NV, S);
+  a.x = sv.x; a.y = sv.y; a.nspr = sv.nspr; a.entry = sv.entry; a.step_count = sv.step_count; a.episode = sv.episode;
+  a.pool_base = sv.pool_base; a.pool_len = sv.pool_len; a.reset_next = sv.reset_next;
   a.steps = h->d_rollout_steps;
   a.actions = actions_dev;
   if (out) {
@@ -1243,6 +1274,54 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(swb_rollout_kernel, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S);
   HIP_TRY(hipGetLastError());
+  h->rollout_M = M;
+  h->rollout_stale = false;
+  return SWB_OK;
+}
+
+// Frames of a rollout's end states (include/swb.h): render launches of the path the handle renders with, their state pointers
+// moved to the scratch -- M chunks of N consecutive virtual environments, what the run lists, dispatch tables and overflow
+// slots are sized for --, or one launch on a staging block swb_rollout_pick_kernel gathers the picked candidates into.
+int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev, void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (!h->rollout_M) return fail(SWB_ERR_STATE, "swb_rollout_frames: no rollout has run on this handle (swb_rollout first)");
+  if (!obs_dev) return fail(SWB_ERR_INVALID, "swb_rollout_frames: obs is NULL");
+  if (M != h->rollout_M)
+    return fail(SWB_ERR_INVALID, "swb_rollout_frames: M = %d, but the last rollout of this handle had %d candidates", M, h->rollout_M);
+  if (h->rollout_stale)
+    return fail(SWB_ERR_STATE, "swb_rollout_frames: the pool has changed since the last rollout (swb_set_pool, swb_sample_pool or "
+                "swb_resample_pool): its candidates may sit in entries that have been redrawn; roll out again");
+  if (h->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_rollout_frames: sprite setters have been called on this handle; rollouts under live overrides are not supported");
+  if (int rc = check_ready(h, nullptr, 1)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t N = (size_t)h->p.N, S = (size_t)h->p.S, frame = (size_t)h->p.Wo * h->p.Ho * 3;
+  const swb_state_view all = rollout_state_view(h->d_rollout.ptr, N * M, S);
+  swb_outputs out;
+  memset(&out, 0, sizeof(out));
+  if (cand_dev) {
+    const size_t bytes = N * (16 * S + 32);
+    if (bytes > h->d_rollout_pick.count) {     // (blocking, once: an earlier call may still use the old block)
+      HIP_TRY(hipStreamSynchronize(st));
+      if (h->d_rollout_pick.fill(nullptr, bytes)) return SWB_ERR_HIP;
+    }
+    const swb_state_view picked = rollout_state_view(h->d_rollout_pick.ptr, N, S);
+    hipLaunchKernelGGL(swb_rollout_pick_kernel, dim3((unsigned)((N * S + 255) / 256)), dim3(256), 0, st, all, picked, cand_dev, (int)N,
+                       (int)S, (int)M);
+    HIP_TRY(hipGetLastError());
+    out.obs = obs_dev; out.error = error_dev;
+    return launch(h, nullptr, &out, 1, st, &picked);
+  }
+  for (size_t c = 0; c < (size_t)M; ++c) {     // virtual environments [c N, (c + 1) N)
+    swb_state_view chunk = all;
+    chunk.x += c * N * S; chunk.y += c * N * S;
+    chunk.nspr += c * N; chunk.entry += c * N; chunk.step_count += c * N; chunk.episode += c * N;
+    chunk.pool_base += c * N; chunk.pool_len += c * N; chunk.reset_next += c * N;
+    out.obs = obs_dev + c * N * frame;
+    out.error = error_dev ? error_dev + c * N : nullptr;
+    if (int rc = launch(h, nullptr, &out, 1, st, &chunk)) return rc;
+  }
   return SWB_OK;
 }
 

@@ -2998,6 +2998,32 @@ swb_rollout_fork_kernel(const swb_params p, const swb_rollout_args a) {
   }
 }
 
+// The per-environment state arrays a launch reads and writes (swb_params "live state", and the pool range beside it): the live
+// ones, the scratch of a rollout's virtual environments, or a staging block of picked candidates (swb_rollout_frames).
+struct swb_state_view {
+  double *x, *y;                 // [n][S]
+  int32_t *nspr, *entry, *step_count, *episode, *pool_base, *pool_len;   // [n]
+  uint8_t* reset_next;           // [n]
+};
+
+// swb_rollout_frames with picked candidates: one thread per (environment, sprite) copies the state of virtual environment
+// n * M + clamp(cand[n], 0, M - 1) from the rollout's scratch `src` into block `dst` of N environments, which one render launch
+// then draws.  Plain vector loads and stores, like the fork kernel.
+__global__ void __launch_bounds__(256)
+swb_rollout_pick_kernel(const swb_state_view src, const swb_state_view dst, const int32_t* cand, int N, int S, int M) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);         // (N * S <= N * M * S < 2^31: swb_rollout checked)
+  if (idx >= N * S) return;
+  const int n = idx / S, s = idx - n * S;
+  const size_t v = (size_t)n * M + (size_t)min(max(cand[n], 0), M - 1);
+  dst.x[idx] = src.x[v * S + s];
+  dst.y[idx] = src.y[v * S + s];
+  if (s == 0) {
+    dst.nspr[n] = src.nspr[v]; dst.entry[n] = src.entry[v]; dst.step_count[n] = src.step_count[v]; dst.episode[n] = src.episode[v];
+    dst.reset_next[n] = src.reset_next[v];
+    dst.pool_base[n] = src.pool_base[v]; dst.pool_len[n] = src.pool_len[v];
+  }
+}
+
 // Register budget: the state phase is latency-bound (dependent loads, LDS round trips), so more resident waves win although the
 // kernel then spills: measured at N = 1024, M = 64, K = 16 (goal_s5 / embodied_s12), 4 waves per SIMD (105 VGPRs, no spills)
 // 1.430 / 1.338 ms, 5 waves (94 VGPRs, 2 spilled) 1.259 / 1.179 ms, 6 waves (80 VGPRs, 16 spilled) 1.194 / 1.121 ms.

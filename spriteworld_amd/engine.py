@@ -72,6 +72,7 @@ class Engine(object):
     self._outs = self._make_outs(render=True)
     self._outs_norender = self._make_outs(render=False)
     self._rendered = 0        # rendering launches so far (the run lists are trimmed after TRIM_AFTER of them)
+    self._rollout_M = 0       # candidates of the last rollout (rollout_frames)
 
   TRIM_AFTER = 3
 
@@ -186,6 +187,34 @@ class Engine(object):
       setattr(o, k, t.data_ptr())
     self._last_rollout_actions = actions  # keep alive until the launch is consumed
     self._check(self.lib.swb_rollout(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), self._stream()))
+    self._rollout_M = int(M)
+    return res
+
+  def rollout_frames(self, candidates=None):
+    """The frames the candidates of the LAST rollout end in (swb_rollout_frames: the render path of this engine on the
+    rollout's scratch state, asynchronous, on the rollout's stream; the live state, `self.obs`, `self.error` and the pool
+    untouched).  Returns a dict of fresh device tensors: obs u8[N, M, H, W, 3] -- frame [n, m] what step K of environment n
+    would have rendered under candidate m -- and error u8[N, M] (swb_env_error bits of the render phases, zero-initialised).
+    With `candidates` (int[N], tensor or array; values outside [0, M) are clamped into it) only the frame of candidate
+    candidates[n] of environment n is rendered: obs u8[N, H, W, 3], error u8[N].  Raises when no rollout preceded it, or the
+    pool has changed since.  Not a rendering step as far as `trim()` after TRIM_AFTER launches is concerned."""
+    M = self._rollout_M
+    if not M:                 # (the library refuses: no rollout has run on the handle)
+      self._check(self.lib.swb_rollout_frames(self._h, 0, None, None, None, self._stream()))
+    cand = None
+    if candidates is not None:
+      cand = candidates if isinstance(candidates, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(candidates))
+      if cand.dim() != 1 or cand.shape[0] != self.N or cand.is_floating_point():
+        raise ValueError('rollout_frames candidates must be int[%d], got %s %s' % (self.N, cand.dtype, tuple(cand.shape)))
+      cand = cand.to(device=self.device, dtype=torch.int32).contiguous()
+    lead = (self.N,) if cand is not None else (self.N, M)
+    with self._device_scope():
+      res = {'obs': torch.empty(lead + self.obs_shape, dtype=torch.uint8, device=self.device),
+             'error': torch.zeros(lead, dtype=torch.uint8, device=self.device)}
+    self._last_rollout_candidates = cand  # keep alive until the launch is consumed
+    self._check(self.lib.swb_rollout_frames(self._h, M, None if cand is None else C.c_void_p(cand.data_ptr()),
+                                            C.c_void_p(res['obs'].data_ptr()), C.c_void_p(res['error'].data_ptr()),
+                                            self._stream()))
     return res
 
   def sample_actions(self, mode, seed, first_env=0, outputs=('actions',)):

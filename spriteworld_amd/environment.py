@@ -305,6 +305,16 @@ class BatchedEnvironment(object):
     per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
     return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']]))
 
+  def rollout_frames(self, candidates=None):
+    """The frames the candidates of the last `rollout` end in, a fresh device tensor u8[N, M, H, W, 3]: entry [n, m] is to the
+    byte the image observation step K of environment n would have returned had the K steps been actions[n, m, :] (a candidate
+    that ended on step K shows its terminal sprites, one that restarted on it the new episode).  With `candidates` (int[N],
+    e.g. `rollout.episode_return().argmax(1)`; values outside [0, M) are clamped) only the frame of candidate candidates[n] of
+    environment n, u8[N, H, W, 3], for the cost of one step's rendering.  Call it after `rollout(...)`, on the same stream
+    (swb_rollout_frames: the engine's render path on the rollout's scratch state, no host synchronisation; the live
+    environments, their last observation and the pool are untouched).  Frames of intermediate steps do not exist."""
+    return self._engine.rollout_frames(candidates)['obs']
+
   def observation(self):
     """environment.py:136-142: every renderer's view of the sprites AS THEY ARE NOW -- the frame is rendered now (swb_render)
     and a Success renderer evaluates the task now (swb_evaluate; environment.py:128-131 `state()` calls `success()` on the
