@@ -78,7 +78,8 @@ enum swb_step_type { SWB_STEP_FIRST = 0, SWB_STEP_MID = 1, SWB_STEP_LAST = 2 };
  * the reward of that step is NaN and success is 0.) */
 enum swb_env_error {
   SWB_ENV_OK = 0,
-  SWB_ENV_ERR_DB_ZERO = 1,       /* Davies-Bouldin score 0 => reference raises ZeroDivisionError (tasks.py:215) */
+  SWB_ENV_ERR_DB_ZERO = 1,       /* Davies-Bouldin score exactly 0.0, by sklearn's early-outs or its regular path => reference raises
+                                    ZeroDivisionError (tasks.py:215); reward NaN, success 0 */
   SWB_ENV_ERR_DB_LABELS = 2,     /* sklearn check_number_of_labels => reference raises ValueError            */
   SWB_ENV_ERR_SPAN_OVERFLOW = 4  /* internal raster span list overflow (never expected)                      */
 };

@@ -524,7 +524,13 @@ static void task_find_goal(const swb_task* t, int n, const double* x, const doub
  *                                  n >= 2 (gemv kernel)       fma(a0, b0, a1*b1)
  *   X @ X.T (syrk/gemm), x.dot(x) (ddot)                      fma(a1, b1, a0*b0)
  * For float32 positions (the config-sampled case) every product of two upcast float32 values
- * is exact in float64, so all of these orders give identical results. */
+ * is exact in float64, so all of these orders give identical results.
+ * Where this holds: the member products (X @ Y.T) for every n = 1 .. 64; the centroid Gram matrix (X @ X.T) for fewer than
+ * 12 clusters.  From 12 clusters on, numpy's BLAS tiles the Gram matrix and evaluates some entries as fma(a0, b0, a1*b1) or
+ * unfused (k = 12..15, 20..23, 28..31, ... on the build container's CPU), so with float64 positions the reference's score can
+ * differ from this one in the last bits (19 % of uniform random scenes there); the tiling is not replicated.
+ * tests/test_davies_bouldin_cpu.py holds this function to scikit-learn with exactly these orders written out
+ * (tests/_davies_bouldin_model.py) everywhere, and to scikit-learn as it runs on the domain above. */
 static double norm2(double a0, double a1) { return a0 * a0 + a1 * a1; }
 static double dot2_hi(double a0, double a1, double b0, double b1) { return fma(a1, b1, a0 * b0); }
 static double dot2_lo(double a0, double a1, double b0, double b1) { return fma(a0, b0, a1 * b1); }
@@ -630,6 +636,9 @@ static int davies_bouldin(int pos_f32, int n, const double* x, const double* y, 
     scores[a] = best;
   }
   *score_out = np_pairwise_sum(scores, k) / (double)k;
+  /* a score of exactly 0.0 by the regular path (clusters within about 1e-8 of each other, float64 positions: every pair with
+   * a non-zero intra sum has centroid distance 0 -> inf) raises ZeroDivisionError at `1. / score` like the early-outs */
+  if (*score_out == 0.0) return SWB_ENV_ERR_DB_ZERO;
   return 0;
 }
 

@@ -304,7 +304,7 @@ __device__ __forceinline__ double move1(int pos_f32, double pv, double motion, i
   return q;
 }
 
-// numpy pairwise sum (float64 / float32) for n <= 16 elements held in LDS.
+// numpy pairwise sum (float64 / float32) of up to SWB_MAX_SPRITES (64) elements held in LDS; the code is numpy's for n <= 128.
 __device__ __forceinline__ double np_sum_d(const double* a, int n) {
   if (n < 8) {
     double r = -0.0;
@@ -542,8 +542,10 @@ __device__ __forceinline__ int davies_bouldin_wave(int pos_f32, int n, double px
   }
   wave_sync();
   if (all_i_zero || all_d_zero) { *score_out = 0.0; return SWB_ENV_ERR_DB_ZERO; }
-  *score_out = __ddiv_rn(np_sum_d(sc->tmp, k), (double)k);
+  const double score = __ddiv_rn(np_sum_d(sc->tmp, k), (double)k);
+  *score_out = score;
   wave_sync();
+  if (score == 0.0) return SWB_ENV_ERR_DB_ZERO;                      // exactly 0.0 by the regular path: `1. / score` raises too
   return 0;
 }
 

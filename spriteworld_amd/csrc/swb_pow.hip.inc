@@ -9,8 +9,8 @@
 // 128-entry 2^(i/128) table.  The operation order below is that of the compiled function; it is
 // specialised to y = 0.5 and to finite x >= 0.  Constants: swb_pow_tables.inc (generated from
 // the system libm by tools/extract_glibc_pow_tables.py).  tests/test_pow_half.py compiles this
-// file for the host and checks it bit-for-bit against libm pow over 10^7 inputs; the GPU test
-// does the same on device.
+// file for the host and checks it bit-for-bit against libm pow over 10^7 inputs; on the device
+// the function is exercised through the FindGoalPosition parity tests (rewards bit-exact against the oracle's libm pow).
 //
 // The file is plain C++ apart from three macros so that the host test can include it.
 #ifndef SWB_POW_FN

@@ -1,5 +1,6 @@
 """The bar every engine-against-oracle test holds a step to (TEST INFRASTRUCTURE ONLY): sprite positions, the state arrays,
-step types, success flags, discounts and rewards bit-exact (rewards with the same NaN pattern), frames +-0, no error flag.
+step types, success flags, discounts and rewards bit-exact (rewards with the same NaN pattern), frames +-0, no error flag -- or,
+for scenes the reference raises on, exactly the flags the caller expects.
 The emulated suites and the `-m gpu` suites call the same three functions with an engine factory of their own."""
 import numpy as np
 
@@ -10,13 +11,17 @@ def bits(a):
   return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what=''):
+def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what='', errors=None):
   """One step's outputs (`want`: the oracle's, `got`: the engine's, on the host) and the state after it; returns the
   engine's state.  reward_ulp: a bound in units of the last place in place of bit-equal rewards; `what`: the caller's case, put
-  in front of the step in every message."""
+  in front of the step in every message; `errors`: the error buffer expected in place of an empty one (the engine's flags are sticky:
+  the OR of the oracle's per-step flags so far)."""
   at = '%st=%d' % (what and what + ', ', t)
   st_o, st_g = ora.state(), eng.state()
-  assert not got['error'].any(), ('error flags ' + at, np.flatnonzero(got['error'])[:8])
+  if errors is None:
+    assert not got['error'].any(), ('error flags ' + at, np.flatnonzero(got['error'])[:8])
+  else:
+    np.testing.assert_array_equal(got['error'], errors, err_msg='error flags ' + at)
   np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type ' + at)
   np.testing.assert_array_equal(bits(st_g['x']), bits(st_o['x']), err_msg='x ' + at)
   np.testing.assert_array_equal(bits(st_g['y']), bits(st_o['y']), err_msg='y ' + at)
