@@ -322,7 +322,8 @@ int swb_evaluate(swb_handle h, uint8_t* success_dev, void* stream);
  * type and success, and the same auto-reset -- a candidate that reaches LAST plays FIRST on the next step, from pool entry
  * pool_base + (episode mod pool_len), as the live environment would (it is not stopped at its first LAST).
  * The handle is left as it was: positions, step counts, episodes, entries, reset flags, the pool, and the run lists and
- * dispatch bookkeeping of the render path; nothing is rendered (swb_rollout_frames below draws the end states).
+ * dispatch bookkeeping of the render path; nothing is rendered (swb_rollout_frames below draws the end states,
+ * swb_rollout_trajectory and swb_rollout_step_frames the states after every step).
  * N * M virtual environments step on a scratch copy of the state (N * M * (16 * max_sprites + 32) bytes, owned by the handle, grown on demand); two kernels, asynchronous on `stream`
  * -- only growing the scratch (or, when K grows, the K per-step parameter blocks of 2 KB kept beside it) blocks.
  * Limits: M, K >= 1, N * M <= 2^24, K <= 65536; SWB_ERR_INVALID beyond them.
@@ -362,12 +363,53 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
  * render path's dispatch bookkeeping (parity, phase, cost lists, which launch listed runs) advances as for swb_render --
  * results never depend on it --, so swb_trim_run_lists called straight afterwards sizes the lists from candidate scenes: a
  * list that outgrows its part moves to the arena, an exhausted arena is flagged in error_dev.  Never a counted step of
- * swb_timing_enable.  Frames of intermediate steps k < K do not exist: the scratch holds the end states only.
+ * swb_timing_enable.  The scratch holds the end states only: frames of the steps k < K are swb_rollout_step_frames', after a
+ * swb_rollout_trajectory.
  * SWB_ERR_INVALID: null handle, obs_dev NULL, M different from the last rollout's.  SWB_ERR_STATE: no rollout has run on the
  * handle; swb_set_pool, swb_sample_pool or swb_resample_pool was called since (a candidate may sit in an entry that was just
  * redrawn: roll out again); swb_set_sprite_attr has been called on the handle (overrides are indexed by live environment, as
  * for swb_rollout); shapes, pool or resampling tables missing. */
 int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev, void* stream);
+
+/* A rollout that keeps every step: swb_rollout in every respect -- arguments, outputs, limits, refusals, the one-stream rule,
+ * what it leaves untouched, and the end states in the scratch (swb_rollout_frames works after it unchanged) -- that also keeps
+ * the state of every virtual environment after each of the K steps, for swb_rollout_step_frames below and for `steps`:
+ * per environment n, candidate m and step k the positions and the sprite count after step k + 1, the per-step targets of a
+ * state-space model (steps may be NULL, and so may any pointer in it).  What swb_rollout's x, y, n_sprites are for step K.
+ * The K states live in a trajectory block owned by the handle, K * N * M * (16 * max_sprites + 24) bytes, laid out like the
+ * scratch with [K][N * M] in front of every array (positions, sprite count, pool entry, step count, episode, reset flag;
+ * pool_base / pool_len do not change during a rollout and stay in the scratch); grown on demand behind a stream synchronise,
+ * like the scratch.  One kernel differs from swb_rollout's: the build of the rollout kernel that copies the state out after
+ * every step.
+ * SWB_ERR_INVALID besides swb_rollout's: K * N * M * max_sprites does not fit an int.  SWB_ERR_HIP with the byte count in the
+ * message when the block cannot be allocated: the handle stays usable, and holds no rollout (swb_rollout_frames refuses).
+ * A plain swb_rollout afterwards keeps no steps: it invalidates the trajectory. */
+typedef struct swb_rollout_step_outputs {   /* device memory, caller-owned; any pointer may be NULL */
+  double* x;           /* f64[K,N,M,S]  positions after step k + 1                                     */
+  double* y;           /* f64[K,N,M,S]                                                                 */
+  int32_t* n_sprites;  /* i32[K,N,M]    sprites of the episode the candidate is in after step k + 1    */
+} swb_rollout_step_outputs;
+int swb_rollout_trajectory(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
+                           const swb_rollout_step_outputs* steps, void* stream);
+
+/* Frames of the steps inside a rollout: what the agent would SEE after step `step` + 1 of the candidates of the last
+ * swb_rollout_trajectory of this handle.  swb_rollout_frames in every respect but where the states come from (the trajectory
+ * block) -- the stream, error_dev ORed into, the clamping of cand, M as a guard, the render path re-pointed in chunks of N, what
+ * is untouched, the dispatch bookkeeping advancing per chunk, never a counted step of swb_timing_enable.
+ *   step in [0, K), cand_dev == NULL   obs_dev u8[N, M, H, W, 3], error_dev u8[N, M]: every candidate after step `step` + 1
+ *   step in [0, K), cand_dev i32[N]    obs_dev u8[N, H, W, 3],    error_dev u8[N]:    candidate cand[n] after step `step` + 1
+ *   SWB_ALL_STEPS,  cand_dev i32[N]    obs_dev u8[K, N, H, W, 3], error_dev u8[K, N]: candidate cand[n] after every step -- the
+ *                                      K frames of the plan an agent has chosen: one gather kernel
+ *                                      (swb_rollout_pick_steps_kernel) into the staging block, K render launches
+ * Each frame is, to the byte, what swb_step number `step` + 1 would have written to swb_outputs::obs under that candidate: a
+ * step that was LAST shows the terminal sprites, one that was FIRST the fresh episode.  step = K - 1 is swb_rollout_frames.
+ * SWB_ERR_INVALID: null handle, obs_dev NULL, M different from the last rollout's, step outside [-1, K), SWB_ALL_STEPS with
+ * cand_dev NULL (loop over the steps for that).  SWB_ERR_STATE: no rollout has run on the handle; the last one was a plain
+ * swb_rollout, which kept no steps; the pool has changed since; swb_set_sprite_attr has been called on the handle; shapes,
+ * pool or resampling tables missing. */
+#define SWB_ALL_STEPS (-1)
+int swb_rollout_step_frames(swb_handle h, int32_t M, int32_t step, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev,
+                            void* stream);
 
 /* Random-agent actions drawn on the device: one action per environment, ready for swb_step, without a host round trip.
  * SWB_SAMPLE_UNIFORM is action_space.sample() (uniform in [0, 1)^4; Embodied: carry in {0, 1}, direction in {0 .. 3}).

@@ -118,6 +118,17 @@ class SwbRolloutOutputs(C.Structure):
   ]
 
 
+class SwbRolloutStepOutputs(C.Structure):
+  _fields_ = [
+      ('x', C.c_void_p),
+      ('y', C.c_void_p),
+      ('n_sprites', C.c_void_p),
+  ]
+
+
+SWB_ALL_STEPS = -1
+
+
 class SwbSampledActions(C.Structure):
   _fields_ = [
       ('actions', C.c_void_p),
@@ -238,6 +249,8 @@ PROTOTYPES = {
     'swb_evaluate': (None, [_h, _p, _h]),
     'swb_rollout': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _h]),
     'swb_rollout_frames': (None, [_h, _i32, _p, _p, _p, _h]),
+    'swb_rollout_trajectory': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _P(SwbRolloutStepOutputs), _h]),
+    'swb_rollout_step_frames': (None, [_h, _i32, _i32, _p, _p, _p, _h]),
     'swb_sample_actions': (None, [_h, _i32, _u64, _u64, _P(SwbSampledActions), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_factors': (None, [_h, _p, _h]),

@@ -159,6 +159,10 @@ struct swb_engine {
   int rollout_M = 0;
   bool rollout_stale = false;
   dev_buf<unsigned char> d_rollout_pick;
+  // swb_rollout_trajectory: the states after each of the K steps of the last rollout (one allocation, grown on demand), and that
+  // K (0: the last rollout was a plain swb_rollout, which kept no steps)
+  dev_buf<unsigned char> d_rollout_traj;
+  int rollout_kept_K = 0;
 };
 
 namespace {
@@ -1234,28 +1238,61 @@ static swb_state_view rollout_state_view(unsigned char* base, size_t nv, size_t 
   v.reset_next = reinterpret_cast<uint8_t*>(v.pool_len + nv);      // (nv bytes of the last 8 nv)
   return v;
 }
-int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream) {
+// The trajectory block of swb_rollout_trajectory (swb_rollout_keep::traj): the scratch's arrays with [K][nv] in front, K * nv *
+// (16 * S + 24) bytes; pool_base / pool_len are the scratch's own (they do not change during a rollout).
+static swb_state_view rollout_trajectory_view(unsigned char* base, size_t K, size_t nv, size_t S, const swb_state_view& scratch) {
+  swb_state_view v;
+  const size_t e = K * nv;
+  v.x = reinterpret_cast<double*>(base);
+  v.y = v.x + e * S;
+  v.nspr = reinterpret_cast<int32_t*>(v.y + e * S);
+  v.entry = v.nspr + e; v.step_count = v.entry + e; v.episode = v.step_count + e;
+  v.reset_next = reinterpret_cast<uint8_t*>(v.episode + e);        // (e bytes of the last 8 e)
+  v.pool_base = scratch.pool_base; v.pool_len = scratch.pool_len;
+  return v;
+}
+// `v` moved on by `e` environments in the arrays a step writes and by `e_pool` in pool_base / pool_len.
+static swb_state_view advanced(swb_state_view v, size_t e, size_t e_pool, size_t S) {
+  v.x += e * S; v.y += e * S;
+  v.nspr += e; v.entry += e; v.step_count += e; v.episode += e; v.reset_next += e;
+  v.pool_base += e_pool; v.pool_len += e_pool;
+  return v;
+}
+
+// swb_rollout (steps == nullptr, keep == false) and swb_rollout_trajectory (`name` is the caller's, for the messages).
+static int rollout_launch(swb_handle h, const char* name, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
+                          bool keep, const swb_rollout_step_outputs* steps, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
-  if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "swb_rollout: M and K must be positive (M = %d, K = %d)", M, K);
-  if (!actions_dev) return fail(SWB_ERR_INVALID, "swb_rollout: actions is NULL");
+  if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "%s: M and K must be positive (M = %d, K = %d)", name, M, K);
+  if (!actions_dev) return fail(SWB_ERR_INVALID, "%s: actions is NULL", name);
   const swb_params& p = h->p;
   if ((long long)p.N * M > SWB_ROLLOUT_MAX_VENVS)
-    return fail(SWB_ERR_INVALID, "swb_rollout: %d environments x %d candidates exceed the grid limit of %d virtual environments", p.N, M,
+    return fail(SWB_ERR_INVALID, "%s: %d environments x %d candidates exceed the grid limit of %d virtual environments", name, p.N, M,
                 SWB_ROLLOUT_MAX_VENVS);
-  if (K > SWB_ROLLOUT_MAX_STEPS) return fail(SWB_ERR_INVALID, "swb_rollout: K = %d exceeds the limit of %d steps", K, SWB_ROLLOUT_MAX_STEPS);
+  if (K > SWB_ROLLOUT_MAX_STEPS) return fail(SWB_ERR_INVALID, "%s: K = %d exceeds the limit of %d steps", name, K, SWB_ROLLOUT_MAX_STEPS);
+  if (keep && (long long)K * p.N * M * p.S > 0x7fffffffll)
+    return fail(SWB_ERR_INVALID, "%s: K x N x M x max_sprites = %d x %d x %d x %d does not fit an int (the kept steps are indexed with one)",
+                name, K, p.N, M, p.S);
   if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
   if (h->d_ov_flag)
-    return fail(SWB_ERR_STATE, "swb_rollout: sprite setters have been called on this handle; rollouts under live overrides are not supported");
+    return fail(SWB_ERR_STATE, "%s: sprite setters have been called on this handle; rollouts under live overrides are not supported", name);
   HIP_TRY(hipSetDevice(h->device));
   const hipStream_t st = (hipStream_t)stream;
   const size_t NV = (size_t)p.N * M, S = (size_t)p.S;
-  const size_t bytes = NV * (16 * S + 32);
+  const size_t bytes = NV * (16 * S + 32), traj_bytes = keep ? (size_t)K * NV * (16 * S + 24) : 0;
   h->rollout_M = 0;                          // (until both kernels are in the stream, the scratch holds no rollout's end states)
-  if (bytes > h->d_rollout.count || (size_t)K > h->d_rollout_steps.count) {   // (the one blocking case: an earlier rollout may still use the old scratch)
-    HIP_TRY(hipStreamSynchronize(st));
+  h->rollout_kept_K = 0;
+  if (bytes > h->d_rollout.count || (size_t)K > h->d_rollout_steps.count || traj_bytes > h->d_rollout_traj.count) {
+    HIP_TRY(hipStreamSynchronize(st));       // (the one blocking case: an earlier rollout may still use the old buffers)
     if (bytes > h->d_rollout.count && h->d_rollout.fill(nullptr, bytes)) return SWB_ERR_HIP;
     if ((size_t)K > h->d_rollout_steps.count && h->d_rollout_steps.fill(nullptr, K)) return SWB_ERR_HIP;
+    if (traj_bytes > h->d_rollout_traj.count && h->d_rollout_traj.fill(nullptr, traj_bytes)) {
+      (void)hipGetLastError();               // (not left for the next launch to find: the handle stays usable)
+      const std::string why = g_err;
+      return fail(SWB_ERR_HIP, "%s: could not allocate %zu bytes for the states of %d steps of %zu virtual environments (%s)", name,
+                  traj_bytes, K, NV, why.c_str());
+    }
   }
   swb_rollout_args a;
   memset(&a, 0, sizeof(a));
@@ -1269,14 +1306,31 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
     a.reward = out->reward; a.discount = out->discount; a.step_type = out->step_type; a.success = out->success;
     a.error = out->error; a.out_x = out->x; a.out_y = out->y; a.out_n = out->n_sprites;
   }
+  swb_rollout_keep kp;
+  memset(&kp, 0, sizeof(kp));
+  if (keep) {
+    kp.traj = rollout_trajectory_view(h->d_rollout_traj.ptr, (size_t)K, NV, S, sv);
+    if (steps) { kp.out_x = steps->x; kp.out_y = steps->y; kp.out_n = steps->n_sprites; }
+  }
   const size_t threads = std::max(NV * S, (size_t)K);
   hipLaunchKernelGGL(swb_rollout_fork_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, a);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(swb_rollout_kernel, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S);
+  if (keep) hipLaunchKernelGGL(swb_rollout_kernel<true>, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S, kp);
+  else hipLaunchKernelGGL(swb_rollout_kernel<false>, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S, kp);
   HIP_TRY(hipGetLastError());
   h->rollout_M = M;
+  h->rollout_kept_K = keep ? K : 0;
   h->rollout_stale = false;
   return SWB_OK;
+}
+
+int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out, void* stream) {
+  return rollout_launch(h, "swb_rollout", actions_dev, M, K, out, false, nullptr, stream);
+}
+
+int swb_rollout_trajectory(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
+                           const swb_rollout_step_outputs* steps, void* stream) {
+  return rollout_launch(h, "swb_rollout_trajectory", actions_dev, M, K, out, true, steps, stream);
 }
 
 // Frames of a rollout's end states (include/swb.h): render launches of the path the handle renders with, their state pointers
@@ -1318,6 +1372,67 @@ int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t
     chunk.x += c * N * S; chunk.y += c * N * S;
     chunk.nspr += c * N; chunk.entry += c * N; chunk.step_count += c * N; chunk.episode += c * N;
     chunk.pool_base += c * N; chunk.pool_len += c * N; chunk.reset_next += c * N;
+    out.obs = obs_dev + c * N * frame;
+    out.error = error_dev ? error_dev + c * N : nullptr;
+    if (int rc = launch(h, nullptr, &out, 1, st, &chunk)) return rc;
+  }
+  return SWB_OK;
+}
+
+// Frames of the steps inside a rollout (include/swb.h): swb_rollout_frames' render launches with their state pointers on a slot of
+// the trajectory block swb_rollout_trajectory kept -- M chunks of N virtual environments of one step, or a staging block that
+// swb_rollout_pick_steps_kernel gathers the picked candidates of one step (N environments) or of every step (K * N) into, drawn N at a time.
+int swb_rollout_step_frames(swb_handle h, int32_t M, int32_t step, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev,
+                            void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (!h->rollout_M) return fail(SWB_ERR_STATE, "swb_rollout_step_frames: no rollout has run on this handle (swb_rollout_trajectory first)");
+  if (!h->rollout_kept_K)
+    return fail(SWB_ERR_STATE, "swb_rollout_step_frames: the last rollout of this handle was a plain swb_rollout, which kept no steps "
+                "(swb_rollout_trajectory keeps them)");
+  if (!obs_dev) return fail(SWB_ERR_INVALID, "swb_rollout_step_frames: obs is NULL");
+  if (M != h->rollout_M)
+    return fail(SWB_ERR_INVALID, "swb_rollout_step_frames: M = %d, but the last rollout of this handle had %d candidates", M, h->rollout_M);
+  const int K = h->rollout_kept_K;
+  if (step < SWB_ALL_STEPS || step >= K)
+    return fail(SWB_ERR_INVALID, "swb_rollout_step_frames: step = %d is outside [0, %d), the steps of the last rollout (SWB_ALL_STEPS = -1: "
+                "every step)", step, K);
+  if (step == SWB_ALL_STEPS && !cand_dev)
+    return fail(SWB_ERR_INVALID, "swb_rollout_step_frames: SWB_ALL_STEPS needs picked candidates (cand is NULL): loop over the steps for "
+                "the frames of all candidates");
+  if (h->rollout_stale)
+    return fail(SWB_ERR_STATE, "swb_rollout_step_frames: the pool has changed since the last rollout (swb_set_pool, swb_sample_pool or "
+                "swb_resample_pool): its candidates may sit in entries that have been redrawn; roll out again");
+  if (h->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_rollout_step_frames: sprite setters have been called on this handle; rollouts under live overrides are not supported");
+  if (int rc = check_ready(h, nullptr, 1)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t N = (size_t)h->p.N, S = (size_t)h->p.S, NV = N * M, frame = (size_t)h->p.Wo * h->p.Ho * 3;
+  const swb_state_view scratch = rollout_state_view(h->d_rollout.ptr, NV, S);
+  const swb_state_view traj = rollout_trajectory_view(h->d_rollout_traj.ptr, (size_t)K, NV, S, scratch);
+  swb_outputs out;
+  memset(&out, 0, sizeof(out));
+  if (cand_dev) {
+    const int k0 = step == SWB_ALL_STEPS ? 0 : step, nk = step == SWB_ALL_STEPS ? K : 1;
+    const size_t bytes = (size_t)nk * N * (16 * S + 32);
+    if (bytes > h->d_rollout_pick.count) {     // (blocking, once: an earlier call may still use the old block)
+      HIP_TRY(hipStreamSynchronize(st));
+      if (h->d_rollout_pick.fill(nullptr, bytes)) return SWB_ERR_HIP;
+    }
+    const swb_state_view picked = rollout_state_view(h->d_rollout_pick.ptr, (size_t)nk * N, S);
+    hipLaunchKernelGGL(swb_rollout_pick_steps_kernel, dim3((unsigned)(((size_t)nk * N * S + 255) / 256)), dim3(256), 0, st, traj, scratch,
+                       picked, cand_dev, (int)N, (int)S, (int)M, k0, nk);
+    HIP_TRY(hipGetLastError());
+    for (size_t kk = 0; kk < (size_t)nk; ++kk) {   // environments [kk N, (kk + 1) N) of the staging block: step k0 + kk
+      const swb_state_view chunk = advanced(picked, kk * N, kk * N, S);
+      out.obs = obs_dev + kk * N * frame;
+      out.error = error_dev ? error_dev + kk * N : nullptr;
+      if (int rc = launch(h, nullptr, &out, 1, st, &chunk)) return rc;
+    }
+    return SWB_OK;
+  }
+  for (size_t c = 0; c < (size_t)M; ++c) {     // virtual environments [c N, (c + 1) N) of slot `step`
+    const swb_state_view chunk = advanced(traj, (size_t)step * NV + c * N, c * N, S);
     out.obs = obs_dev + c * N * frame;
     out.error = error_dev ? error_dev + c * N : nullptr;
     if (int rc = launch(h, nullptr, &out, 1, st, &chunk)) return rc;

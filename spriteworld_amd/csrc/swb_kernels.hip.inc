@@ -3026,6 +3026,39 @@ swb_rollout_pick_kernel(const swb_state_view src, const swb_state_view dst, cons
   }
 }
 
+// swb_rollout_trajectory: where swb_rollout_kernel<true> keeps the state every step leaves.  `traj` is laid out like the scratch
+// with [K][N * M] in front of every array -- slot k of virtual environment v is element k * N * M + v --, so that the view
+// advanced by k * N * M + c * N is a valid swb_state_view of N environments for a render launch.  pool_base / pool_len do not
+// change during a rollout and are not replicated (traj.pool_base / traj.pool_len are not used: a render view takes the scratch's).
+// out_x, out_y [K][N * M][S] and out_n [K][N * M] are the caller's swb_rollout_step_outputs, any of them NULL.
+struct swb_rollout_keep {
+  swb_state_view traj;
+  double *out_x, *out_y;
+  int32_t* out_n;
+};
+static_assert(sizeof(swb_params) + sizeof(swb_rollout_args) + sizeof(swb_rollout_keep) <= 4096, "kernel arguments of the rollout kernels");
+
+// swb_rollout_step_frames with picked candidates: one thread per (step, environment, sprite) copies slot k0 + kk of virtual
+// environment n * M + clamp(cand[n], 0, M - 1) from the trajectory block `src` into environment kk * N + n of block `dst` (nk * N
+// environments, drawn in nk render launches of N); pool_base / pool_len come from the rollout's scratch `pool`.  Plain vector
+// loads and stores, like swb_rollout_pick_kernel.
+__global__ void __launch_bounds__(256)
+swb_rollout_pick_steps_kernel(const swb_state_view src, const swb_state_view pool, const swb_state_view dst, const int32_t* cand, int N,
+                              int S, int M, int k0, int nk) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);         // (nk * N * S <= K * N * M * S < 2^31: swb_rollout_trajectory checked)
+  if (idx >= nk * N * S) return;
+  const int e = idx / S, s = idx - e * S, kk = e / N, n = e - kk * N;
+  const size_t v = (size_t)n * M + (size_t)min(max(cand[n], 0), M - 1);
+  const size_t slot = (size_t)(k0 + kk) * N * M + v;
+  dst.x[idx] = src.x[slot * S + s];
+  dst.y[idx] = src.y[slot * S + s];
+  if (s == 0) {
+    dst.nspr[e] = src.nspr[slot]; dst.entry[e] = src.entry[slot]; dst.step_count[e] = src.step_count[slot];
+    dst.episode[e] = src.episode[slot]; dst.reset_next[e] = src.reset_next[slot];
+    dst.pool_base[e] = pool.pool_base[v]; dst.pool_len[e] = pool.pool_len[v];
+  }
+}
+
 // Register budget: the state phase is latency-bound (dependent loads, LDS round trips), so more resident waves win although the
 // kernel then spills: measured at N = 1024, M = 64, K = 16 (goal_s5 / embodied_s12), 4 waves per SIMD (105 VGPRs, no spills)
 // 1.430 / 1.338 ms, 5 waves (94 VGPRs, 2 spilled) 1.259 / 1.179 ms, 6 waves (80 VGPRs, 16 spilled) 1.194 / 1.121 ms.
@@ -3033,8 +3066,20 @@ swb_rollout_pick_kernel(const swb_state_view src, const swb_state_view dst, cons
 #ifndef SWB_ROLLOUT_WAVES_PER_SIMD
 #define SWB_ROLLOUT_WAVES_PER_SIMD 6
 #endif
-__global__ void __launch_bounds__(SWB_WAVE, SWB_ROLLOUT_WAVES_PER_SIMD)
-swb_rollout_kernel(const swb_rollout_args a, int S) {
+// KEEP (swb_rollout_trajectory): every step the wave also writes its virtual environment's state into slot k of `keep`, from
+// the registers the step's own stores were made from -- es.px / es.py are the words lanes < S hold in x, y (act_and_move stores
+// them, a FIRST step's load_env_state does), es.n, es.en and the step count are what lane 0 stored or left, the episode number is
+// counted along (a FIRST step adds one) -- so nothing just written is read back, and the stores are issued BEFORE the wave_sync()
+// that ends the iteration: they drain together with the step's own (re-reading behind the wave_sync() was measured 24 to 35 %
+// slower than swb_rollout, profiles/r14_rollout_trajectory.md).  reset_next after step k is whether step k + 1 is FIRST, which
+// only the next iteration's load_env_state knows: slot k's byte is written then, the last slot's after the loop from memory
+// (a plain load behind the wave_sync(): THE RULE).
+#ifndef SWB_ROLLOUT_KEEP_WAVES_PER_SIMD
+#define SWB_ROLLOUT_KEEP_WAVES_PER_SIMD 6
+#endif
+template <bool KEEP>
+__global__ void __launch_bounds__(SWB_WAVE, KEEP ? SWB_ROLLOUT_KEEP_WAVES_PER_SIMD : SWB_ROLLOUT_WAVES_PER_SIMD)
+swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int l = lane_id();
   const int v = blockIdx.x;
@@ -3042,6 +3087,8 @@ swb_rollout_kernel(const swb_rollout_args a, int S) {
   task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
   double2* cpath = M->path;
   uint32_t err = 0;
+  int ep = 0;                                           // KEEP: the episode number the virtual environment is in
+  if constexpr (KEEP) ep = a.episode[v];                // (written by the fork launch)
   for (int k = 0; k < a.K; ++k) {
     const swb_params& q = *(const swb_params*)as_const(a.steps + k);
     env_state es = load_env_state<false>(q, v, tscratch);
@@ -3061,7 +3108,26 @@ swb_rollout_kernel(const swb_rollout_args a, int S) {
     };
     const step_cost sc = act_and_move(q, v, es, hit);
     err |= finish_step<false>(q, v, es, sc, tscratch);
+    if constexpr (KEEP) {
+      const size_t slot = (size_t)k * gridDim.x + v;    // (one workgroup per virtual environment: gridDim.x = N * M)
+      ep += es.first ? 1 : 0;
+      if (l < S) {
+        keep.traj.x[slot * S + l] = es.px;
+        keep.traj.y[slot * S + l] = es.py;
+        if (keep.out_x) keep.out_x[slot * S + l] = es.px;
+        if (keep.out_y) keep.out_y[slot * S + l] = es.py;
+      }
+      if (l == 0) {
+        keep.traj.nspr[slot] = es.n; keep.traj.entry[slot] = es.en; keep.traj.step_count[slot] = sc.step_count;
+        keep.traj.episode[slot] = ep;
+        if (k > 0) keep.traj.reset_next[slot - gridDim.x] = es.first ? 1 : 0;
+        if (keep.out_n) keep.out_n[slot] = es.n;
+      }
+    }
     wave_sync();                                        // the next iteration reads what this one stored (state words, LDS scratch)
+  }
+  if constexpr (KEEP) {
+    if (l == 0) keep.traj.reset_next[(size_t)(a.K - 1) * gridDim.x + v] = a.reset_next[v];
   }
   if (l < S) {
     if (a.out_x) a.out_x[(size_t)v * S + l] = a.x[(size_t)v * S + l];

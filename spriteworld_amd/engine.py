@@ -73,6 +73,7 @@ class Engine(object):
     self._outs_norender = self._make_outs(render=False)
     self._rendered = 0        # rendering launches so far (the run lists are trimmed after TRIM_AFTER of them)
     self._rollout_M = 0       # candidates of the last rollout (rollout_frames)
+    self._rollout_K = 0       # ... and its steps, when it kept them (rollout(keep_steps=True); 0: it did not)
 
   TRIM_AFTER = 3
 
@@ -155,14 +156,16 @@ class Engine(object):
       if self._rendered == self.TRIM_AFTER:
         self.trim()
 
-  def rollout(self, actions, positions=False):
+  def rollout(self, actions, positions=False, keep_steps=False):
     """Scores M candidate action sequences of K steps per environment from the CURRENT state without stepping it
     (swb_rollout: two kernels, asynchronous, the live state untouched).  actions: [K, N, M, 4] float (f32 if
     cfg.action_is_f32) or [K, N, M, 2] int32 (Embodied).  Returns a dict of fresh device tensors in the C layout: reward
     f64, discount f32, step_type u8, success u8 -- all [K, N, M], entry [k, n, m] what step k + 1 of environment n would
     return under actions[k, n, m] -- and error u8[N, M] (swb_env_error bits of the K steps); with `positions`, also x, y
-    f64[N, M, S] and n_sprites i32[N, M] after step K.  The scratch state belongs to the handle: issue the rollouts of one
-    engine on one stream (or order the streams yourself)."""
+    f64[N, M, S] and n_sprites i32[N, M] after step K.  With `keep_steps` (swb_rollout_trajectory) the engine also keeps the
+    state after every step, for `rollout_frames(step=...)`, and with `positions` returns x_steps, y_steps f64[K, N, M, S]
+    and n_sprites_steps i32[K, N, M] too: entry [k] the state after step k + 1.  The scratch state belongs to the handle:
+    issue the rollouts of one engine on one stream (or order the streams yourself)."""
     if self.cfg.action_space == _abi.ACTION_EMBODIED:
       want, width = torch.int32, 2
     else:
@@ -182,25 +185,52 @@ class Engine(object):
       if positions:
         res.update(x=new((self.N, M, self.S), torch.float64), y=new((self.N, M, self.S), torch.float64),
                    n_sprites=new((self.N, M), torch.int32))
+      steps = {}
+      if positions and keep_steps:
+        steps = {'x': new((K, self.N, M, self.S), torch.float64), 'y': new((K, self.N, M, self.S), torch.float64),
+                 'n_sprites': new((K, self.N, M), torch.int32)}
     o = _abi.SwbRolloutOutputs()
     for k, t in res.items():
       setattr(o, k, t.data_ptr())
     self._last_rollout_actions = actions  # keep alive until the launch is consumed
-    self._check(self.lib.swb_rollout(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), self._stream()))
+    self._rollout_M = self._rollout_K = 0
+    if keep_steps:
+      so = _abi.SwbRolloutStepOutputs()
+      for k, t in steps.items():
+        setattr(so, k, t.data_ptr())
+      self._check(self.lib.swb_rollout_trajectory(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), C.byref(so),
+                                                  self._stream()))
+      self._rollout_K = int(K)
+      res.update((k + '_steps', t) for k, t in steps.items())
+    else:
+      self._check(self.lib.swb_rollout(self._h, C.c_void_p(actions.data_ptr()), int(M), int(K), C.byref(o), self._stream()))
     self._rollout_M = int(M)
     return res
 
-  def rollout_frames(self, candidates=None):
+  def rollout_frames(self, candidates=None, step=None):
     """The frames the candidates of the LAST rollout end in (swb_rollout_frames: the render path of this engine on the
     rollout's scratch state, asynchronous, on the rollout's stream; the live state, `self.obs`, `self.error` and the pool
     untouched).  Returns a dict of fresh device tensors: obs u8[N, M, H, W, 3] -- frame [n, m] what step K of environment n
     would have rendered under candidate m -- and error u8[N, M] (swb_env_error bits of the render phases, zero-initialised).
     With `candidates` (int[N], tensor or array; values outside [0, M) are clamped into it) only the frame of candidate
     candidates[n] of environment n is rendered: obs u8[N, H, W, 3], error u8[N].  Raises when no rollout preceded it, or the
-    pool has changed since.  Not a rendering step as far as `trim()` after TRIM_AFTER launches is concerned."""
+    pool has changed since.  Not a rendering step as far as `trim()` after TRIM_AFTER launches is concerned.
+    `step` (swb_rollout_step_frames, after `rollout(keep_steps=True)`): an int k in [0, K) renders the states after step k + 1
+    in the same two forms; 'all' needs `candidates` and renders candidates[n] after every step: obs u8[K, N, H, W, 3], error
+    u8[K, N].  Raises when the last rollout kept no steps."""
+    if isinstance(step, str):
+      if step != 'all':
+        raise ValueError("rollout_frames step must be an int or 'all', got %r" % (step,))
+      if candidates is None:
+        raise ValueError("rollout_frames step='all' needs candidates: loop over the steps for the frames of all candidates")
+      step = _abi.SWB_ALL_STEPS
+    elif step is not None and int(step) < 0:     # (not an index from the end: -1 is SWB_ALL_STEPS in the C ABI)
+      raise ValueError('rollout_frames step must be in [0, K), got %d' % int(step))
     M = self._rollout_M
-    if not M:                 # (the library refuses: no rollout has run on the handle)
-      self._check(self.lib.swb_rollout_frames(self._h, 0, None, None, None, self._stream()))
+    if not M or (step is not None and not self._rollout_K):     # (the library refuses: no rollout has run, or it kept no steps)
+      if step is None:
+        self._check(self.lib.swb_rollout_frames(self._h, 0, None, None, None, self._stream()))
+      self._check(self.lib.swb_rollout_step_frames(self._h, M, int(step), None, None, None, self._stream()))
     cand = None
     if candidates is not None:
       cand = candidates if isinstance(candidates, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(candidates))
@@ -208,13 +238,18 @@ class Engine(object):
         raise ValueError('rollout_frames candidates must be int[%d], got %s %s' % (self.N, cand.dtype, tuple(cand.shape)))
       cand = cand.to(device=self.device, dtype=torch.int32).contiguous()
     lead = (self.N,) if cand is not None else (self.N, M)
+    if step == _abi.SWB_ALL_STEPS:
+      lead = (self._rollout_K,) + lead
     with self._device_scope():
       res = {'obs': torch.empty(lead + self.obs_shape, dtype=torch.uint8, device=self.device),
              'error': torch.zeros(lead, dtype=torch.uint8, device=self.device)}
     self._last_rollout_candidates = cand  # keep alive until the launch is consumed
-    self._check(self.lib.swb_rollout_frames(self._h, M, None if cand is None else C.c_void_p(cand.data_ptr()),
-                                            C.c_void_p(res['obs'].data_ptr()), C.c_void_p(res['error'].data_ptr()),
-                                            self._stream()))
+    cand_p, obs_p, err_p = (None if cand is None else C.c_void_p(cand.data_ptr()), C.c_void_p(res['obs'].data_ptr()),
+                            C.c_void_p(res['error'].data_ptr()))
+    if step is None:
+      self._check(self.lib.swb_rollout_frames(self._h, M, cand_p, obs_p, err_p, self._stream()))
+    else:
+      self._check(self.lib.swb_rollout_step_frames(self._h, M, int(step), cand_p, obs_p, err_p, self._stream()))
     return res
 
   def sample_actions(self, mode, seed, first_env=0, outputs=('actions',)):

@@ -64,6 +64,11 @@ class Rollout(collections.namedtuple('Rollout', ['step_type', 'reward', 'discoun
     return torch.where(keep, self.reward, torch.zeros_like(self.reward)).sum(dim=2)
 
 
+# What `BatchedEnvironment.rollout_positions` returns, device tensors in the planner's layout: x, y f64[N, M, K, S] and n_sprites
+# i32[N, M, K] views, entry [n, m, k] the sprites of environment n after step k + 1 of candidate m.
+RolloutSteps = collections.namedtuple('RolloutSteps', ['x', 'y', 'n_sprites'])
+
+
 _ACTION_KEY_DOMAIN = 0xA5A5C3D2E1F00F1E      # folded into the seed of the device action stream (_next_action_seed)
 
 # What `BatchedEnvironment.sample_contained_positions` returns, device tensors: position f64[N, 2], sprite i32[N], tries i32[N].
@@ -287,7 +292,7 @@ class BatchedEnvironment(object):
         self.refresh_pool()
     return self._timestep()
 
-  def rollout(self, actions):
+  def rollout(self, actions, keep_steps=False):
     """Scores candidate action sequences from where every environment is now, without stepping: actions is [N, M, K, A]
     (tensor or array; A = 4, or 2 for Embodied) -- M candidates of K steps per environment.  Returns a `Rollout` whose
     [n, m, k] entries are exactly what step k + 1 of environment n would return had the next K steps been actions[n, m, :]
@@ -295,25 +300,43 @@ class BatchedEnvironment(object):
     first LAST).  One permute to the engine's [K, N, M, A] layout, two kernels (swb_rollout), no host synchronisation; the
     live environments, their error flags and the pool are untouched.
     A rollout is of the NOISELESS dynamics: a SelectMove `noise_scale` is not applied to the candidates (`step()` draws its
-    noise per call; the candidates are scored as given)."""
+    noise per call; the candidates are scored as given).
+    With `keep_steps` (swb_rollout_trajectory) the same `Rollout` is returned and the state after every step is kept:
+    `rollout_frames(step=...)` draws it and `rollout_positions()` returns the sprite positions per step."""
     e = self._engine
     if not isinstance(actions, torch.Tensor):
       actions = torch.as_tensor(np.ascontiguousarray(actions))
     if actions.dim() != 4 or actions.shape[0] != self._num_envs:
       raise ValueError('rollout actions must be [N, M, K, A] with N = %d, got %s' % (self._num_envs, tuple(actions.shape)))
-    res = e.rollout(actions.to(device=e.device).permute(2, 0, 1, 3), positions=True)
+    self._rollout_steps = None
+    res = e.rollout(actions.to(device=e.device).permute(2, 0, 1, 3), positions=True, keep_steps=keep_steps)
+    if keep_steps:
+      self._rollout_steps = RolloutSteps(res['x_steps'].permute(1, 2, 0, 3), res['y_steps'].permute(1, 2, 0, 3),
+                                         res['n_sprites_steps'].permute(1, 2, 0))
     per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
     return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']]))
 
-  def rollout_frames(self, candidates=None):
+  def rollout_positions(self):
+    """`RolloutSteps(x, y, n_sprites)` of the last `rollout(..., keep_steps=True)`: x, y f64[N, M, K, S] and n_sprites
+    i32[N, M, K] views of device tensors, entry [n, m, k] the sprites of environment n after step k + 1 of candidate m
+    ([..., K - 1, :] is the `Rollout`'s x, y).  Raises when the last rollout kept no steps."""
+    if getattr(self, '_rollout_steps', None) is None:
+      raise EnvironmentError_('rollout_positions: the last rollout kept no steps (call rollout(actions, keep_steps=True) first)')
+    return self._rollout_steps
+
+  def rollout_frames(self, candidates=None, step=None):
     """The frames the candidates of the last `rollout` end in, a fresh device tensor u8[N, M, H, W, 3]: entry [n, m] is to the
     byte the image observation step K of environment n would have returned had the K steps been actions[n, m, :] (a candidate
     that ended on step K shows its terminal sprites, one that restarted on it the new episode).  With `candidates` (int[N],
     e.g. `rollout.episode_return().argmax(1)`; values outside [0, M) are clamped) only the frame of candidate candidates[n] of
     environment n, u8[N, H, W, 3], for the cost of one step's rendering.  Call it after `rollout(...)`, on the same stream
     (swb_rollout_frames: the engine's render path on the rollout's scratch state, no host synchronisation; the live
-    environments, their last observation and the pool are untouched).  Frames of intermediate steps do not exist."""
-    return self._engine.rollout_frames(candidates)['obs']
+    environments, their last observation and the pool are untouched).
+    `step`, after `rollout(..., keep_steps=True)` (swb_rollout_step_frames): an int k in [0, K) gives the same two forms for
+    the states after step k + 1; 'all' gives the K frames of the picked candidates, a u8[N, K, H, W, 3] view, and raises
+    ValueError without `candidates`."""
+    obs = self._engine.rollout_frames(candidates, step=step)['obs']
+    return obs.permute(1, 0, 2, 3, 4) if isinstance(step, str) else obs
 
   def observation(self):
     """environment.py:136-142: every renderer's view of the sprites AS THEY ARE NOW -- the frame is rendered now (swb_render)

@@ -32,6 +32,9 @@ def kernels_of(asm):
         m = re.search(r'swb_ms_state_kernelILb([01])E', name)
         key = 'swb_ms_state_kernel' + ('<OV>' if m.group(1) == '1' else '') if m else None
       if key is None:
+        m = re.search(r'swb_rollout_kernelILb([01])E', name)
+        key = 'swb_rollout_kernel' + ('<KEEP>' if m.group(1) == '1' else '') if m else None
+      if key is None:
         m = re.search(r'_Z\d+(swb_\w+?_kernel)', name)
         key = m.group(1) if m else name
     f = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))
