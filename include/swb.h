@@ -444,6 +444,39 @@ typedef struct swb_sampled_actions {   /* device memory, caller-owned */
 } swb_sampled_actions;
 int swb_sample_actions(swb_handle h, int32_t mode, uint64_t seed, uint64_t first_env, const swb_sampled_actions* out, void* stream);
 
+/* A rollout that draws its own candidates: swb_rollout (keep_steps == 0) or swb_rollout_trajectory (keep_steps != 0) in every
+ * respect -- outputs, limits, refusals, the one-stream rule, the scratch and the trajectory block, what is left untouched, and
+ * the handle "holding a rollout" afterwards (swb_rollout_frames works; with keep_steps swb_rollout_step_frames too; the
+ * stale-pool refusals apply) -- except that the K * N * M actions are not the caller's: the rollout kernel draws the action of
+ * step k of candidate m from the state that candidate has REACHED, and hands it back in sampled->actions, in swb_rollout's own
+ * layout: feeding that buffer to swb_rollout (swb_rollout_trajectory) reproduces every output bit for bit, and
+ * actions[0, n, m] is what to give swb_step to execute the first step of the chosen plan.
+ * mode (enum swb_action_sampling) is swb_sample_actions' per step: SWB_SAMPLE_UNIFORM, or SWB_SAMPLE_ON_SPRITE -- a click
+ * inside a sprite drawn by index among those the candidate's step acts on, where they are at that step (inside a rollout the
+ * sprites move per candidate: no sequence of swb_sample_actions and swb_rollout calls can place such a click).
+ * Random numbers: Philox4x32-10, key = seed, counter = (entry lo, block, entry hi, 1 + m) with entry = first_env + n: ONE stream
+ * per virtual environment for the whole rollout, consumed step by step, k = 0 .. K - 1.  The fourth counter word is 0 in
+ * swb_sample_pool and swb_sample_actions, so no candidate replays those streams under the same seed, and a candidate's stream
+ * depends neither on M nor on K: the first K' steps of the first M' candidates of a larger call are the smaller call's.
+ * Per step the draw order is swb_sample_actions' for the mode, taken after the step's state is loaded: on a FIRST step from the
+ * fresh episode's sprites -- the draw is made although the dynamics ignore a FIRST step's action, so the stream's position never
+ * depends on step types.  A float32-action handle stores (float) of the float64 draw and steps with that float; containment is
+ * guaranteed for FLOAT64 actions only.  The cap of SWB_CONTAINED_MAX_TRIES holds as documented above.  A SelectMove
+ * noise_scale is the caller's, as for swb_rollout: none is applied.
+ * Two kernels, asynchronous on `stream`: the fork kernel of swb_rollout and the builds of the rollout kernel that draw
+ * (swb_rollout_kernel<KEEP, SAMPLE>: the same step code, a register budget of its own).
+ * SWB_ERR_INVALID besides swb_rollout's / swb_rollout_trajectory's: unknown mode; sampled or sampled->actions NULL; sprite / tries
+ * given with SWB_SAMPLE_UNIFORM; steps given with keep_steps == 0.  SWB_ERR_STATE after swb_set_sprite_attr, as for swb_rollout. */
+typedef struct swb_rollout_sampled_outputs {  /* device memory, caller-owned */
+  void*    actions;  /* REQUIRED. [K,N,M,4] f64 (f32 when cfg.action_is_f32) or [K,N,M,2] i32 (Embodied): what was drawn, in
+                        swb_rollout's own layout -- feeding it to swb_rollout reproduces every output bit for bit            */
+  int32_t* sprite;   /* [K,N,M] ON_SPRITE only, may be NULL: index of the chosen sprite, -1 if the environment had none      */
+  int32_t* tries;    /* [K,N,M] ON_SPRITE only, may be NULL: as swb_sampled_actions::tries (>= 1; 0 no sprite; -1 cap)        */
+} swb_rollout_sampled_outputs;
+int swb_rollout_sampled(swb_handle h, int32_t mode /* enum swb_action_sampling */, uint64_t seed, uint64_t first_env,
+                        int32_t M, int32_t K, int32_t keep_steps, const swb_rollout_outputs* out,
+                        const swb_rollout_step_outputs* steps, const swb_rollout_sampled_outputs* sampled, void* stream);
+
 /* Memory of the hand-off lists (what the cover kernel hands the resample / fill kernel: swb_variant_info::run_list_bytes).
  * A handle starts with a list of max(4, max_sprites + 1) units of 8 bytes per canvas row for every environment and group of 64
  * output columns -- enough for ANY scene of convex sprites, about ten times what the usual scene needs (133 KB per environment

@@ -138,6 +138,14 @@ class SwbSampledActions(C.Structure):
   ]
 
 
+class SwbRolloutSampledOutputs(C.Structure):
+  _fields_ = [
+      ('actions', C.c_void_p),
+      ('sprite', C.c_void_p),
+      ('tries', C.c_void_p),
+  ]
+
+
 class SwbState(C.Structure):
   _fields_ = [
       ('x', C.c_void_p),
@@ -252,6 +260,8 @@ PROTOTYPES = {
     'swb_rollout_trajectory': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _P(SwbRolloutStepOutputs), _h]),
     'swb_rollout_step_frames': (None, [_h, _i32, _i32, _p, _p, _p, _h]),
     'swb_sample_actions': (None, [_h, _i32, _u64, _u64, _P(SwbSampledActions), _h]),
+    'swb_rollout_sampled': (None, [_h, _i32, _u64, _u64, _i32, _i32, _i32, _P(SwbRolloutOutputs), _P(SwbRolloutStepOutputs),
+                                   _P(SwbRolloutSampledOutputs), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_factors': (None, [_h, _p, _h]),
     'swb_get_env_state': (None, [_h, _i32, _p, _h]),

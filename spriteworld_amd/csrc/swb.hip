@@ -1259,9 +1259,10 @@ static swb_state_view advanced(swb_state_view v, size_t e, size_t e_pool, size_t
   return v;
 }
 
-// swb_rollout (steps == nullptr, keep == false) and swb_rollout_trajectory (`name` is the caller's, for the messages).
+// swb_rollout (steps == nullptr, keep == false), swb_rollout_trajectory and swb_rollout_sampled (`name` is the caller's, for the
+// messages).  `sampled` (swb_rollout_sampled; its `actions` is actions_dev): the rollout kernel's builds that draw the actions.
 static int rollout_launch(swb_handle h, const char* name, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
-                          bool keep, const swb_rollout_step_outputs* steps, void* stream) {
+                          bool keep, const swb_rollout_step_outputs* steps, void* stream, const swb_rollout_sample_args* sampled = nullptr) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "%s: M and K must be positive (M = %d, K = %d)", name, M, K);
   if (!actions_dev) return fail(SWB_ERR_INVALID, "%s: actions is NULL", name);
@@ -1315,8 +1316,14 @@ static int rollout_launch(swb_handle h, const char* name, const void* actions_de
   const size_t threads = std::max(NV * S, (size_t)K);
   hipLaunchKernelGGL(swb_rollout_fork_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, a);
   HIP_TRY(hipGetLastError());
-  if (keep) hipLaunchKernelGGL(swb_rollout_kernel<true>, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S, kp);
-  else hipLaunchKernelGGL(swb_rollout_kernel<false>, dim3((unsigned)NV), dim3(SWB_WAVE), sizeof(swb_ms_lds), st, a, p.S, kp);
+  swb_rollout_sample_args sa;
+  memset(&sa, 0, sizeof(sa));
+  if (sampled) sa = *sampled;
+  const dim3 grid((unsigned)NV), block(SWB_WAVE);
+  if (sampled && keep) hipLaunchKernelGGL((swb_rollout_kernel<true, true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
+  else if (sampled) hipLaunchKernelGGL((swb_rollout_kernel<false, true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
+  else if (keep) hipLaunchKernelGGL((swb_rollout_kernel<true, false>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
+  else hipLaunchKernelGGL((swb_rollout_kernel<false, false>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
   HIP_TRY(hipGetLastError());
   h->rollout_M = M;
   h->rollout_kept_K = keep ? K : 0;
@@ -1331,6 +1338,25 @@ int swb_rollout(swb_handle h, const void* actions_dev, int32_t M, int32_t K, con
 int swb_rollout_trajectory(swb_handle h, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
                            const swb_rollout_step_outputs* steps, void* stream) {
   return rollout_launch(h, "swb_rollout_trajectory", actions_dev, M, K, out, true, steps, stream);
+}
+
+// A rollout that draws its candidates' actions in the kernel (include/swb.h): rollout_launch with the sampling arguments.
+int swb_rollout_sampled(swb_handle h, int32_t mode, uint64_t seed, uint64_t first_env, int32_t M, int32_t K, int32_t keep_steps,
+                        const swb_rollout_outputs* out, const swb_rollout_step_outputs* steps, const swb_rollout_sampled_outputs* sampled,
+                        void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (mode != SWB_SAMPLE_UNIFORM && mode != SWB_SAMPLE_ON_SPRITE) return fail(SWB_ERR_INVALID, "swb_rollout_sampled: unknown mode %d", mode);
+  if (!sampled || !sampled->actions)
+    return fail(SWB_ERR_INVALID, "swb_rollout_sampled: sampled->actions is NULL (the drawn actions are a required output)");
+  if (mode == SWB_SAMPLE_UNIFORM && (sampled->sprite || sampled->tries))
+    return fail(SWB_ERR_INVALID, "swb_rollout_sampled: sprite and tries are outputs of SWB_SAMPLE_ON_SPRITE only");
+  if (!keep_steps && steps)
+    return fail(SWB_ERR_INVALID, "swb_rollout_sampled: per-step outputs (steps) need keep_steps != 0");
+  swb_rollout_sample_args sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.mode = mode; sa.seed = seed; sa.first_env = first_env;
+  sa.actions = sampled->actions; sa.sprite = sampled->sprite; sa.tries = sampled->tries;
+  return rollout_launch(h, "swb_rollout_sampled", sampled->actions, M, K, out, keep_steps != 0, steps, stream, &sa);
 }
 
 // Frames of a rollout's end states (include/swb.h): render launches of the path the handle renders with, their state pointers

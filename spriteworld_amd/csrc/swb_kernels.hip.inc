@@ -3077,9 +3077,29 @@ swb_rollout_pick_steps_kernel(const swb_state_view src, const swb_state_view poo
 #ifndef SWB_ROLLOUT_KEEP_WAVES_PER_SIMD
 #define SWB_ROLLOUT_KEEP_WAVES_PER_SIMD 6
 #endif
-template <bool KEEP>
-__global__ void __launch_bounds__(SWB_WAVE, KEEP ? SWB_ROLLOUT_KEEP_WAVES_PER_SIMD : SWB_ROLLOUT_WAVES_PER_SIMD)
-swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep) {
+// SAMPLE (swb_rollout_sampled): the wave draws every step's action itself, after load_env_state, from the sprites the step acts
+// on -- rollout_drawer<true>, written beside swb_sample_actions_kernel in swb_sampler.hip.inc (the Philox stream is defined
+// there) -- and the drawn action replaces es.act / es.acti in registers.  Builds of their own, with a register budget of their
+// own: measured at N = 1024, M = 64, K = 16 (goal_s5 / embodied_s12), uniform draws, 4 waves per SIMD 1.594 / 1.438 ms, 5 waves
+// (96 VGPRs, 10 spilled) 1.490 / 1.299 ms, 6 waves (80 VGPRs, 26 spilled) 1.397 / 1.231 ms; clicks on sprites 1.884 / 1.960,
+// 1.716 / 1.735, 1.584 / 1.614 ms.  (profiles/r15_rollout_random.md, section 2)
+#ifndef SWB_ROLLOUT_SAMPLED_WAVES_PER_SIMD
+#define SWB_ROLLOUT_SAMPLED_WAVES_PER_SIMD 6
+#endif
+struct swb_rollout_sample_args {
+  int32_t mode;                // enum swb_action_sampling
+  uint64_t seed, first_env;
+  void* actions;               // [K][N * M][4] f64 / f32 or [K][N * M][2] i32: what was drawn
+  int32_t *sprite, *tries;     // [K][N * M], ON_SPRITE only, may be NULL
+};
+static_assert(sizeof(swb_rollout_args) + sizeof(swb_rollout_keep) + sizeof(swb_rollout_sample_args) + 8 <= 4096,
+              "kernel arguments of swb_rollout_kernel");
+template <bool SAMPLE> struct rollout_drawer {};        // (the actions are the caller's: nothing to draw)
+template <> struct rollout_drawer<true>;                // swb_sampler.hip.inc
+template <bool KEEP, bool SAMPLE>
+__global__ void __launch_bounds__(SWB_WAVE, SAMPLE ? SWB_ROLLOUT_SAMPLED_WAVES_PER_SIMD
+                                                   : (KEEP ? SWB_ROLLOUT_KEEP_WAVES_PER_SIMD : SWB_ROLLOUT_WAVES_PER_SIMD))
+swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep, const swb_rollout_sample_args sa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int l = lane_id();
   const int v = blockIdx.x;
@@ -3089,9 +3109,12 @@ swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep)
   uint32_t err = 0;
   int ep = 0;                                           // KEEP: the episode number the virtual environment is in
   if constexpr (KEEP) ep = a.episode[v];                // (written by the fork launch)
+  rollout_drawer<SAMPLE> drawer;
+  if constexpr (SAMPLE) drawer.start(sa, v / a.M, v % a.M);
   for (int k = 0; k < a.K; ++k) {
     const swb_params& q = *(const swb_params*)as_const(a.steps + k);
     env_state es = load_env_state<false>(q, v, tscratch);
+    if constexpr (SAMPLE) drawer.draw(sa, q, k, es, cpath);
     // sprite.py:113-115 contains_point of sprite s2 (wave-uniform), as in swb_ms_state_kernel: its centred path into LDS,
     // lanes = vertices, then the even-odd test
     auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {

@@ -4,7 +4,8 @@
 // sprite_generators.generate_sprites / chain_generators / shuffle over Product-of-Continuous/Discrete
 // factor distributions (reference sprite_generators.py:27-70,101-128, factor_distributions.py:81-158).
 // Random numbers: Philox4x32-10 (Salmon et al., SC'11), key = seed, counter = (entry lo, block, entry hi, 0)
-// with entry = first_entry + pool index.
+// with entry = first_entry + pool index.  (The fourth counter word, philox_stream::word3, is 0 here and in swb_sample_actions;
+// swb_rollout_sampled's candidate m draws with 1 + m.)
 //
 // Draw order per entry (tests/_sampler_model.py restates it and is compared bit for bit):
 //   0. if n_alternatives > 1: alternative = u32 % n_alternatives (the groups generated, in order)
@@ -21,9 +22,10 @@ struct philox_stream {
   uint32_t key0, key1, entry, entry_hi, block;
   uint32_t out[4];
   int have;
+  uint32_t word3 = 0u;
 
   __device__ void refill() {
-    uint32_t c0 = entry, c1 = block, c2 = entry_hi, c3 = 0u, k0 = key0, k1 = key1;
+    uint32_t c0 = entry, c1 = block, c2 = entry_hi, c3 = word3, k0 = key0, k1 = key1;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
       const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
@@ -343,4 +345,130 @@ swb_sample_actions_kernel(const swb_params p, const swb_sample_actions_args a) {
     }
   }
 }
+
+// --------------------------------------------------------------------------------------------
+// Rollouts that draw their own candidates (swb_rollout_sampled, include/swb.h): what the SAMPLE builds of swb_rollout_kernel
+// (swb_kernels.hip.inc) call.  After every load_env_state, draw() replaces the step's action by one drawn from the sprites the
+// step acts on -- `es`, the registers of the wave: on a FIRST step the fresh episode's (the dynamics ignore that action; it is
+// drawn all the same, so the stream's position never depends on step types).  Virtual environment (n, m) owns ONE stream for the
+// K steps: key = seed, counter = (entry lo, block, entry hi, 1 + m), entry = first_env + n -- every lane reads the same values
+// of it (rollout_rng below), so the draws are wave-uniform.
+// Per step the draw order is swb_sample_actions_kernel's above, with es.n for nspr, cross-lane reads of es for the chosen
+// sprite's position, scale, rotation and shape, and the path buffer of the hit test (its first wave_sync() orders our reads).
+// Lanes 0..3 (0..1: Embodied) keep the drawn component in es.act / es.acti and store it to slot [k][v] of `actions`; a float32
+// handle stores (float) of the float64 draw and steps with that float, what swb_rollout would load back.  Nothing stored here
+// is read again by this launch.  The stream's state is wave-uniform and lives across the K steps.
+// The draw is written out beside swb_sample_actions_kernel's, not shared with it: that kernel reads memory (as_const, setter
+// overrides), this one registers.
+// --------------------------------------------------------------------------------------------
+// The stream is philox_stream's, value for value, but generated 64 values at a time by the lanes: lane l computes block
+// (next / 4 + l / 4) and keeps its word l % 4, a draw is a cross-lane read with a wave-uniform index.  philox_stream itself, run
+// by every lane on wave-uniform values, is compiled to scalar multiplies -- 40 per block, two blocks per uniform step --, and
+// the scalar unit, one for the four SIMDs of a compute unit, then bounds the kernel: measured at N = 1024, M = 64, K = 16 and 5
+// waves per SIMD, 1.80 ms against 1.22 ms for a torch.rand tensor and swb_rollout; this form takes 1.49 ms
+// (profiles/r15_rollout_random.md, section 2).
+struct rollout_rng {
+  uint32_t key0, key1, entry, entry_hi, word3;
+  uint32_t next;               // (uniform) values of the stream consumed so far
+  uint32_t word;               // lane l: value number (next rounded down to 64) + l of the stream
+
+  __device__ __forceinline__ uint32_t u32() {
+    const uint32_t i = next & 63u;
+    if (i == 0u) {                                      // (wave-uniform)
+      const int l = lane_id();
+      uint32_t c0 = entry, c1 = (next >> 2) + (uint32_t)(l >> 2), c2 = entry_hi, c3 = word3, k0 = key0, k1 = key1;
+#pragma unroll
+      for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+      }
+      const int w = l & 3;
+      word = w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
+    }
+    next += 1u;
+    return (uint32_t)__builtin_amdgcn_readlane((int)word, (int)i);
+  }
+  __device__ __forceinline__ double uniform() {
+    const uint32_t a = u32() >> 5, b = u32() >> 6;
+    return __dmul_rn(__dadd_rn(__dmul_rn((double)a, 67108864.0), (double)b), 1.0 / 9007199254740992.0);
+  }
+};
+
+template <>
+struct rollout_drawer<true> {
+  rollout_rng rng;
+
+  __device__ __forceinline__ void start(const swb_rollout_sample_args& sa, int n_env, int m) {
+    rng.key0 = (uint32_t)sa.seed; rng.key1 = (uint32_t)(sa.seed >> 32); rng.next = 0u; rng.word = 0u;
+    const uint64_t ge = sa.first_env + (uint64_t)n_env;
+    rng.entry = (uint32_t)ge; rng.entry_hi = (uint32_t)(ge >> 32);
+    rng.word3 = 1u + (uint32_t)m;
+  }
+
+  __device__ __forceinline__ void draw(const swb_rollout_sample_args& sa, const swb_params& q, int k, env_state& es, double2* cpath) {
+    const int l = lane_id();
+    const int v = blockIdx.x;
+    const size_t slot = (size_t)k * gridDim.x + v;      // (one workgroup per virtual environment: gridDim.x = N * M)
+    const bool embodied = q.action_space == SWB_ACTION_EMBODIED;
+    double a0 = 0.0, a1 = 0.0;
+    if (sa.mode == SWB_SAMPLE_ON_SPRITE) {
+      const int n = es.n;
+      int sprite = -1, tries = 0;
+      if (n == 0) {
+        a0 = rng.uniform(); a1 = rng.uniform();
+      } else {
+        sprite = (int)(rng.u32() % (uint32_t)n);
+        const int nv = min(__builtin_amdgcn_readlane(es.nv_l, sprite), SWB_MAX_SHAPE_VERTS), so = __builtin_amdgcn_readlane(es.so_l, sprite);
+        const double sc = readlane_d(es.scale_l, sprite), ca = readlane_d(es.ca_l, sprite), sn = readlane_d(es.sa_l, sprite);
+        const double px = readlane_d(es.px, sprite), py = readlane_d(es.py, sprite);
+        double cx = 0.0, cy = 0.0;
+        wave_sync();                                    // (the previous step's hit tests have read the path)
+        if (l < nv) {
+          centered_vertex(q, so, l, sc, ca, sn, cx, cy);
+          cpath[l] = make_double2(cx, cy);
+        }
+        wave_sync();
+        // sprite.py:119-120: np.min / np.max over the vertices (lanes beyond the path repeat vertex 0)
+        const double fx = readlane_d(cx, 0), fy = readlane_d(cy, 0);
+        const double vx = (l < nv) ? cx : fx, vy = (l < nv) ? cy : fy;
+        const double lo_x = wave_min_d(vx), lo_y = wave_min_d(vy), hi_x = wave_max_d(vx), hi_y = wave_max_d(vy);
+        const double w_x = __dsub_rn(hi_x, lo_x), w_y = __dsub_rn(hi_y, lo_y);
+        a0 = px; a1 = py; tries = -1;
+        for (int t = 1; t <= SWB_CONTAINED_MAX_TRIES; ++t) {
+          const double ux = rng.uniform(), uy = rng.uniform();
+          const double sx = __dadd_rn(px, __dadd_rn(lo_x, __dmul_rn(w_x, ux)));
+          const double sy = __dadd_rn(py, __dadd_rn(lo_y, __dmul_rn(w_y, uy)));
+          if (contains_point_wave(cpath, nv, __dsub_rn(sx, px), __dsub_rn(sy, py))) {   // (the test point is sample - pos)
+            a0 = sx; a1 = sy; tries = t;
+            break;
+          }
+        }
+      }
+      if (l == 0) {
+        if (sa.sprite) sa.sprite[slot] = sprite;
+        if (sa.tries) sa.tries[slot] = tries;
+      }
+    } else if (!embodied) {
+      a0 = rng.uniform(); a1 = rng.uniform();
+    }
+    if (embodied) {
+      const int carry = (int)(rng.u32() % 2u), dir = (int)(rng.u32() % 4u);
+      es.acti = (l == 0) ? carry : dir;
+      if (l < 2) reinterpret_cast<int32_t*>(sa.actions)[2 * slot + l] = es.acti;
+      return;
+    }
+    const double a2 = rng.uniform(), a3 = rng.uniform();
+    const double mine = (l == 0) ? a0 : ((l == 1) ? a1 : ((l == 2) ? a2 : a3));
+    if (q.action_is_f32) {
+      const float f = (float)mine;
+      es.act = (double)f;
+      if (l < 4) reinterpret_cast<float*>(sa.actions)[4 * slot + l] = f;
+    } else {
+      es.act = mine;
+      if (l < 4) reinterpret_cast<double*>(sa.actions)[4 * slot + l] = mine;
+    }
+  }
+};
 #endif  // SWB_WIDE_TU

@@ -207,6 +207,56 @@ class Engine(object):
     self._rollout_M = int(M)
     return res
 
+  def rollout_sampled(self, mode, seed, M, K, first_env=0, positions=False, keep_steps=False, outputs=('actions',)):
+    """A rollout whose M x K candidate actions per environment are drawn by the rollout kernel itself, step by step, from the
+    state each candidate has reached (swb_rollout_sampled: two kernels, asynchronous, the live state untouched).  mode:
+    _abi.SAMPLE_UNIFORM or _abi.SAMPLE_ON_SPRITE (every click inside a randomly chosen sprite, where the candidate's sprites
+    are at that step); candidate m of environment n draws Philox stream (`first_env + n`, 1 + m) of key `seed`.  Returns the
+    dict of `rollout(..., positions, keep_steps)` plus the `outputs` asked for among 'actions' ([K, N, M, 4] f64, f32 if
+    cfg.action_is_f32, or [K, N, M, 2] i32 for Embodied: what was drawn, the layout `rollout` takes -- always drawn, the
+    library requires the buffer), 'sprite' and 'tries' (i32[K, N, M], SAMPLE_ON_SPRITE only).  Afterwards the engine holds a
+    rollout as after `rollout`: `rollout_frames` works."""
+    if self.cfg.action_space == _abi.ACTION_EMBODIED:
+      a_dtype, width = torch.int32, 2
+    else:
+      a_dtype, width = (torch.float32 if self.cfg.action_is_f32 else torch.float64), 4
+    M, K = int(M), int(K)
+    layout = {'actions': ((K, self.N, M, width), a_dtype), 'sprite': ((K, self.N, M), torch.int32), 'tries': ((K, self.N, M), torch.int32)}
+    unknown = [k for k in outputs if k not in layout]
+    if unknown:
+      raise ValueError('rollout_sampled outputs must be among %s, got %s' % (sorted(layout), unknown))
+    if M <= 0 or K <= 0:
+      raise ValueError('rollout_sampled: M and K must be positive, got M = %d, K = %d' % (M, K))
+    self._rollout_M = self._rollout_K = 0
+    with self._device_scope():
+      new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+      res = {'reward': new((K, self.N, M), torch.float64), 'discount': new((K, self.N, M), torch.float32),
+             'step_type': new((K, self.N, M), torch.uint8), 'success': new((K, self.N, M), torch.uint8),
+             'error': torch.zeros((self.N, M), dtype=torch.uint8, device=self.device)}
+      if positions:
+        res.update(x=new((self.N, M, self.S), torch.float64), y=new((self.N, M, self.S), torch.float64),
+                   n_sprites=new((self.N, M), torch.int32))
+      steps = {}
+      if positions and keep_steps:
+        steps = {'x': new((K, self.N, M, self.S), torch.float64), 'y': new((K, self.N, M, self.S), torch.float64),
+                 'n_sprites': new((K, self.N, M), torch.int32)}
+      drawn = {k: new(*layout[k]) for k in set(outputs) | {'actions'}}
+    o, so, sa = _abi.SwbRolloutOutputs(), _abi.SwbRolloutStepOutputs(), _abi.SwbRolloutSampledOutputs()
+    for k, t in res.items():
+      setattr(o, k, t.data_ptr())
+    for k, t in steps.items():
+      setattr(so, k, t.data_ptr())
+    for k, t in drawn.items():
+      setattr(sa, k, t.data_ptr())
+    self._last_rollout_actions = drawn['actions']  # keep alive until the launch is consumed
+    self._check(self.lib.swb_rollout_sampled(self._h, int(mode), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(first_env)),
+                                             M, K, int(bool(keep_steps)), C.byref(o), C.byref(so) if keep_steps else None, C.byref(sa),
+                                             self._stream()))
+    self._rollout_M, self._rollout_K = M, (K if keep_steps else 0)
+    res.update((k + '_steps', t) for k, t in steps.items())
+    res.update((k, drawn[k]) for k in outputs)
+    return res
+
   def rollout_frames(self, candidates=None, step=None):
     """The frames the candidates of the LAST rollout end in (swb_rollout_frames: the render path of this engine on the
     rollout's scratch state, asynchronous, on the rollout's stream; the live state, `self.obs`, `self.error` and the pool

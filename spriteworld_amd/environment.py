@@ -316,6 +316,34 @@ class BatchedEnvironment(object):
     per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
     return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']]))
 
+  def rollout_random(self, num_candidates, num_steps, click='uniform', keep_steps=False):
+    """A random-shooting planner's rollout: `num_candidates` (M) sequences of `num_steps` (K) random actions per environment,
+    drawn by the rollout kernel itself, step by step, from the state each candidate has reached (swb_rollout_sampled: two
+    kernels, no host synchronisation, no action tensor generated, permuted and loaded back).  Returns `(Rollout, actions)`:
+    the `Rollout` of `rollout(actions)` -- bit for bit what that call returns for these actions -- and actions [N, M, K, A], a
+    view of the engine's tensor in the layout `rollout()` accepts (A = 4 float64, float32 with action_dtype=np.float32, or 2
+    int32 for Embodied): `actions[torch.arange(N), best, 0]` is the first step of the chosen plans, ready for `step()`.
+    click='uniform': every action is `action_space.sample()`.  click='sprite': the click of every SelectMove / DragAndDrop
+    action lands inside a sprite drawn by index among those of its candidate, where they are at that step -- inside a
+    rollout the sprites move per candidate, so no `sample_actions` call can place such clicks; Embodied actions stay uniform.
+    Containment is guaranteed for float64 actions only: rounded to float32 a click may leave its sprite at the edge.
+    The rollout is of the NOISELESS dynamics, as `rollout`'s: a SelectMove `noise_scale` is not applied to the drawn actions.
+    The draws are Philox streams keyed by `seed_actions()` (one key per call, as `sample_actions(where='device')`), one stream
+    per (global environment, candidate): `seed_actions(s)` or `np.random.seed` reproduces a call, and a candidate's stream
+    depends neither on M nor on K.  `rollout_frames()` works afterwards and, with `keep_steps`, `rollout_frames(step=...)`
+    and `rollout_positions()`, as after `rollout`."""
+    if click not in ('uniform', 'sprite'):
+      raise ValueError("rollout_random: click is 'uniform' or 'sprite', got %r" % (click,))
+    mode = _abi.SAMPLE_ON_SPRITE if click == 'sprite' else _abi.SAMPLE_UNIFORM
+    self._rollout_steps = None
+    res = self._engine.rollout_sampled(mode, self._next_action_seed(), int(num_candidates), int(num_steps),
+                                       first_env=self._global_env_offset, positions=True, keep_steps=keep_steps)
+    if keep_steps:
+      self._rollout_steps = RolloutSteps(res['x_steps'].permute(1, 2, 0, 3), res['y_steps'].permute(1, 2, 0, 3),
+                                         res['n_sprites_steps'].permute(1, 2, 0))
+    per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
+    return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']])), res['actions'].permute(1, 2, 0, 3)
+
   def rollout_positions(self):
     """`RolloutSteps(x, y, n_sprites)` of the last `rollout(..., keep_steps=True)`: x, y f64[N, M, K, S] and n_sprites
     i32[N, M, K] views of device tensors, entry [n, m, k] the sprites of environment n after step k + 1 of candidate m
@@ -502,6 +530,12 @@ class EnvironmentGroups(object):
     keeps their device streams apart under one seed."""
     with torch.cuda.stream(self.streams[g]):
       return self.groups[g].sample_actions(where=where, click=click)
+
+  def rollout_random(self, g, num_candidates, num_steps, click='uniform', keep_steps=False):
+    """`BatchedEnvironment.rollout_random` of group `g`, on its stream; the returned tensors are valid on `self.streams[g]`.
+    The groups' global_env_offset keeps their candidates' streams apart under one seed."""
+    with torch.cuda.stream(self.streams[g]):
+      return self.groups[g].rollout_random(num_candidates, num_steps, click=click, keep_steps=keep_steps)
 
   def synchronize(self):
     for s in self.streams:
