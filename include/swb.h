@@ -239,6 +239,95 @@ typedef struct swb_sampler {
   swb_sprite_group groups[SWB_MAX_GROUPS];
 } swb_sampler;
 
+/* The general device sampler (swb_sample_pool_tree): any tree of the reference's factor distributions
+ * (factor_distributions.py: Continuous, Discrete, Product, Mixture, Intersection, SetMinus, Selection), lowered by the caller to
+ *   LEAVES      one Continuous / Discrete distribution each, over one factor: what a DRAW samples and what a predicate tests;
+ *   PREDICATES  `distribution.contains(factors)` as a postfix program over leaf tests; and
+ *   PROGRAMS    one linear bytecode per sprite group that visits the tree in the order the reference's sample() does.
+ * Groups, counts, the z-order shuffle, sample_generator alternatives (optionally weighted), the colour map, attr_f32 and the
+ * Philox streams are swb_sampler's.  Task labels are evaluated PER SPRITE from the values drawn (and per cell of the position
+ * grid for tasks that key on position: keyed handles are accepted).
+ *
+ * Types (numpy under NEP 50, as everywhere in the engine): a drawn value is an np.float32 (UNIFORM_F32), a Python number (a
+ * DISCRETE candidate, a Sprite default) or an integer (UNIFORM_INT).  A leaf TEST compares an np.float32 value with its bounds /
+ * candidates rounded to float32 (lo32 / hi32 / cand32, prepared by the caller) and every other value in float64 (lo / hi / cand):
+ *   INTERVAL  lo <= v < hi            (Continuous.contains)
+ *   MEMBER    v == one of cand[0..n)  (Discrete.contains); for the factor SWB_F_SHAPE: bit `shape index` of shape_mask.
+ * A DRAW of a leaf: UNIFORM_* as swb_factor; DISCRETE index = u32 % n, or with `weighted` one uniform() u and
+ * index = #{i : cdf[i] <= u} (numpy's choice(p=...): cdf = p.cumsum() / sum, computed by the caller).  For SWB_F_SHAPE cand[] holds
+ * shape table indices; for SWB_F_ANGLE cos_a / sin_a those of the candidates. */
+#define SWB_TREE_MAX_LEAVES 64
+#define SWB_TREE_MAX_PRED_NODES 128
+#define SWB_TREE_MAX_PREDS 64
+#define SWB_TREE_MAX_OPS 128
+#define SWB_TREE_MAX_CHOICES 16
+#define SWB_TREE_MAX_STACK 32      /* predicate evaluation stack: the bits of one 32-bit word */
+#define SWB_TREE_MAX_CLUSTERS 16   /* predicates per (sub-)task */
+#define SWB_F_SHAPE SWB_N_FACTORS  /* `shape` as a tree factor: its value is the shape table index */
+#define SWB_TREE_N_FACTORS (SWB_N_FACTORS + 1)
+#define SWB_TREE_DEFAULT_MAX_TRIES 10000   /* the reference's _MAX_TRIES */
+typedef struct swb_tree_leaf {
+  int32_t factor;                     /* swb_factor_index, or SWB_F_SHAPE                              */
+  int32_t kind;                       /* swb_factor_kind: UNIFORM_* = INTERVAL, DISCRETE = MEMBER      */
+  int32_t n;                          /* candidates (DISCRETE)                                         */
+  int32_t weighted;                   /* DISCRETE: draw through cdf[]                                  */
+  uint32_t shape_mask, reserved;      /* SWB_F_SHAPE: bit i = shape table index i is a candidate       */
+  double lo, hi, lo32, hi32;
+  double cand[SWB_MAX_CANDIDATES], cand32[SWB_MAX_CANDIDATES], cdf[SWB_MAX_CANDIDATES];
+  double cos_a[SWB_MAX_CANDIDATES], sin_a[SWB_MAX_CANDIDATES];
+} swb_tree_leaf;
+/* Predicates: nodes [first, first + n) evaluated left to right on a stack of bits.  LEAF pushes the test of leaf `leaf`, TRUE
+ * pushes 1 (an empty Product); AND / OR / ANDNOT pop b, then a, and push a & b / a | b / a & ~b.  The program leaves one bit. */
+enum swb_pred_op { SWB_PRED_LEAF = 0, SWB_PRED_AND = 1, SWB_PRED_OR = 2, SWB_PRED_ANDNOT = 3, SWB_PRED_TRUE = 4 };
+typedef struct swb_pred_node { int16_t op, leaf; } swb_pred_node;
+typedef struct swb_tree_pred { int16_t first, n; } swb_tree_pred;
+/* Sampling programs.  DRAW a: draw leaf a into its factor.  CHOOSE a (Mixture): one uniform() u against choices[a].cdf, jump to
+ * its target[#{i : cdf[i] <= u}].  JUMP a: forward only.  TEST a, b, c closes a rejection loop: predicate a is evaluated on the
+ * factors as drawn so far; when its value equals b the program goes on, else it jumps BACK to c (Intersection: b = 1 over all
+ * components; SetMinus: b = 0 over hold_out; Selection: b = 1 over filtering) -- an outer loop restarts its inner loops.
+ * Every failed TEST of one sprite counts against ONE budget, swb_tree_sampler::max_tries: when it is used up the last draw is
+ * kept, every later TEST of the sprite passes, and the sprite is counted in swb_sampler_exhausted (the reference raises
+ * ValueError after _MAX_TRIES per loop).  The budget bounds the work of a sprite at max_tries x program length. */
+enum swb_tree_op_kind { SWB_OP_DRAW = 0, SWB_OP_CHOOSE = 1, SWB_OP_JUMP = 2, SWB_OP_TEST = 3 };
+typedef struct swb_tree_op { int16_t kind, a, b, c; } swb_tree_op;
+typedef struct swb_tree_choice {
+  int32_t n, reserved;
+  int32_t target[SWB_MAX_CANDIDATES];  /* op index (absolute), inside the group's program */
+  double cdf[SWB_MAX_CANDIDATES];
+} swb_tree_choice;
+typedef struct swb_tree_group {
+  int32_t count_min, count_max;
+  int32_t first_op, n_ops;             /* the group's program: ops[first_op .. first_op + n_ops), ends by running off its end */
+  /* factors the tree does not mention: the Sprite defaults (Python numbers; `shape` as its table index) */
+  double defaults[SWB_TREE_N_FACTORS];
+  double default_cos, default_sin;     /* math.cos / sin(math.radians(defaults[SWB_F_ANGLE])) */
+} swb_tree_group;
+/* Labels of (sub-)task t from its predicates: FIND_GOAL: pred[0] (n_preds = 0: no filter, label 1); CLUSTERING: the index of
+ * the first predicate that holds, else -1; NO_REWARD: 0.  For a task of the handle with n_xcuts + n_ycuts > 0 the same is
+ * evaluated once per cell of its grid with x / y replaced by the cell's representative (-inf below the first cut, else the
+ * cut, as an np.float32) into swb_pool::cell_label. */
+typedef struct swb_tree_task {
+  int32_t kind;                        /* swb_task_kind */
+  int32_t n_preds;
+  int16_t pred[SWB_TREE_MAX_CLUSTERS];
+} swb_tree_task;
+typedef struct swb_tree_sampler {
+  int32_t n_groups, shuffle, color_map, n_alternatives;       /* as swb_sampler */
+  int32_t alternatives_weighted;       /* 1: one uniform() against alternative_cdf; 0: u32 % n_alternatives */
+  int32_t max_tries;                   /* failed TESTs per sprite (>= 1; SWB_TREE_DEFAULT_MAX_TRIES) */
+  int32_t n_leaves, n_pred_nodes, n_preds, n_ops, n_choices, n_tasks;   /* n_tasks must equal the handle's */
+  swb_alternative alternatives[SWB_MAX_ALTERNATIVES];
+  double alternative_cdf[SWB_MAX_ALTERNATIVES];
+  double deg_cos[360], deg_sin[360];
+  swb_tree_group groups[SWB_MAX_GROUPS];
+  swb_tree_task tasks[SWB_MAX_TASKS];
+  swb_tree_choice choices[SWB_TREE_MAX_CHOICES];
+  swb_tree_pred preds[SWB_TREE_MAX_PREDS];
+  swb_pred_node pred_nodes[SWB_TREE_MAX_PRED_NODES];
+  swb_tree_op ops[SWB_TREE_MAX_OPS];
+  swb_tree_leaf leaves[SWB_TREE_MAX_LEAVES];
+} swb_tree_sampler;
+
 /* Per-step outputs, device memory, caller-owned.  Any pointer may be NULL. */
 typedef struct swb_outputs {
   uint8_t* obs;        /* u8 [N, H, W, 3]  PILRenderer.render (pil_renderer.py:67-91)      */
@@ -296,8 +385,24 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
  * (the same stream as swb_step, or ordered with it). */
 int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* stream);
 
+/* swb_sample_pool for a swb_tree_sampler (swb_sample_tree_kernel: one thread per entry, the same Philox streams): the same
+ * contract, and handles with a task that keys on position are accepted -- swb_pool::cell_label is filled on the device.
+ * swb_resample_pool afterwards redraws with the tree kernel (with whichever sampler filled the pool last).
+ * The whole program is validated on the host before anything is launched (SWB_ERR_INVALID): every index in range; jumps and
+ * choice targets inside the group's program; backward jumps only from TEST, forward ones only from JUMP / CHOOSE; predicate
+ * stacks at most SWB_TREE_MAX_STACK deep and left with one bit; x and y drawn, and only by UNIFORM_F32 leaves; angle DISCRETE or
+ * integer degrees within [0, 360]; no UNIFORM_INT colour channel under the hsv colour map; cdfs non-decreasing. */
+int swb_sample_pool_tree(swb_handle h, const swb_tree_sampler* spec, int32_t n_entries, const int32_t* pool_base_host,
+                         const int32_t* pool_len_host, uint64_t seed, uint64_t first_entry, void* stream);
+
+/* Sprites of the last swb_sample_pool_tree / swb_resample_pool whose retry budget (swb_tree_sampler::max_tries) ran out: the
+ * reference would have raised ValueError.  Each (re)sample call clears the counter first.  Synchronous (synchronises `stream`);
+ * 0 on a handle that never sampled a tree. */
+int swb_sampler_exhausted(swb_handle h, int64_t* sprites, void* stream);
+
 /* Copies the device pool into caller-allocated HOST arrays laid out like swb_set_pool's input
- * (pool->n_entries must equal the device pool's; angle/color may be NULL).  Synchronous. */
+ * (pool->n_entries must equal the device pool's; angle/color may be NULL; cell_label, when given, is copied on handles with a
+ * task that keys on position).  Synchronous. */
 int swb_get_pool(swb_handle h, const swb_pool* pool_host);
 
 /* Environment.reset() for all envs: the next swb_step is a FIRST step. */

@@ -236,6 +236,107 @@ class SwbSampler(C.Structure):
   ]
 
 
+# swb_tree_sampler (swb_sample_pool_tree): leaves, postfix predicates and one bytecode program per sprite group
+SWB_TREE_MAX_LEAVES, SWB_TREE_MAX_PRED_NODES, SWB_TREE_MAX_PREDS, SWB_TREE_MAX_OPS = 64, 128, 64, 128
+SWB_TREE_MAX_CHOICES, SWB_TREE_MAX_STACK, SWB_TREE_MAX_CLUSTERS = 16, 32, 16
+SWB_F_SHAPE = SWB_N_FACTORS
+SWB_TREE_N_FACTORS = SWB_N_FACTORS + 1
+TREE_FACTOR_ORDER = FACTOR_ORDER + ('shape',)
+SWB_TREE_DEFAULT_MAX_TRIES = 10000
+# enum swb_pred_op / swb_tree_op_kind
+PRED_LEAF, PRED_AND, PRED_OR, PRED_ANDNOT, PRED_TRUE = 0, 1, 2, 3, 4
+OP_DRAW, OP_CHOOSE, OP_JUMP, OP_TEST = 0, 1, 2, 3
+
+
+class SwbTreeLeaf(C.Structure):
+  _fields_ = [
+      ('factor', C.c_int32),
+      ('kind', C.c_int32),
+      ('n', C.c_int32),
+      ('weighted', C.c_int32),
+      ('shape_mask', C.c_uint32),
+      ('reserved', C.c_uint32),
+      ('lo', C.c_double),
+      ('hi', C.c_double),
+      ('lo32', C.c_double),
+      ('hi32', C.c_double),
+      ('cand', C.c_double * SWB_MAX_CANDIDATES),
+      ('cand32', C.c_double * SWB_MAX_CANDIDATES),
+      ('cdf', C.c_double * SWB_MAX_CANDIDATES),
+      ('cos_a', C.c_double * SWB_MAX_CANDIDATES),
+      ('sin_a', C.c_double * SWB_MAX_CANDIDATES),
+  ]
+
+
+class SwbPredNode(C.Structure):
+  _fields_ = [('op', C.c_int16), ('leaf', C.c_int16)]
+
+
+class SwbTreePred(C.Structure):
+  _fields_ = [('first', C.c_int16), ('n', C.c_int16)]
+
+
+class SwbTreeOp(C.Structure):
+  _fields_ = [('kind', C.c_int16), ('a', C.c_int16), ('b', C.c_int16), ('c', C.c_int16)]
+
+
+class SwbTreeChoice(C.Structure):
+  _fields_ = [
+      ('n', C.c_int32),
+      ('reserved', C.c_int32),
+      ('target', C.c_int32 * SWB_MAX_CANDIDATES),
+      ('cdf', C.c_double * SWB_MAX_CANDIDATES),
+  ]
+
+
+class SwbTreeGroup(C.Structure):
+  _fields_ = [
+      ('count_min', C.c_int32),
+      ('count_max', C.c_int32),
+      ('first_op', C.c_int32),
+      ('n_ops', C.c_int32),
+      ('defaults', C.c_double * SWB_TREE_N_FACTORS),
+      ('default_cos', C.c_double),
+      ('default_sin', C.c_double),
+  ]
+
+
+class SwbTreeTask(C.Structure):
+  _fields_ = [
+      ('kind', C.c_int32),
+      ('n_preds', C.c_int32),
+      ('pred', C.c_int16 * SWB_TREE_MAX_CLUSTERS),
+  ]
+
+
+class SwbTreeSampler(C.Structure):
+  _fields_ = [
+      ('n_groups', C.c_int32),
+      ('shuffle', C.c_int32),
+      ('color_map', C.c_int32),
+      ('n_alternatives', C.c_int32),
+      ('alternatives_weighted', C.c_int32),
+      ('max_tries', C.c_int32),
+      ('n_leaves', C.c_int32),
+      ('n_pred_nodes', C.c_int32),
+      ('n_preds', C.c_int32),
+      ('n_ops', C.c_int32),
+      ('n_choices', C.c_int32),
+      ('n_tasks', C.c_int32),
+      ('alternatives', SwbAlternative * SWB_MAX_ALTERNATIVES),
+      ('alternative_cdf', C.c_double * SWB_MAX_ALTERNATIVES),
+      ('deg_cos', C.c_double * 360),
+      ('deg_sin', C.c_double * 360),
+      ('groups', SwbTreeGroup * SWB_MAX_GROUPS),
+      ('tasks', SwbTreeTask * SWB_MAX_TASKS),
+      ('choices', SwbTreeChoice * SWB_TREE_MAX_CHOICES),
+      ('preds', SwbTreePred * SWB_TREE_MAX_PREDS),
+      ('pred_nodes', SwbPredNode * SWB_TREE_MAX_PRED_NODES),
+      ('ops', SwbTreeOp * SWB_TREE_MAX_OPS),
+      ('leaves', SwbTreeLeaf * SWB_TREE_MAX_LEAVES),
+  ]
+
+
 _P, _h, _p, _i32, _u64, _f64 = C.POINTER, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_double
 
 # Every function include/swb.h declares: name -> (restype, or None for the int status; argtypes).  `_h` is the handle or
@@ -250,6 +351,8 @@ PROTOTYPES = {
     'swb_set_pool': (None, [_h, _P(SwbPool)]),
     'swb_sample_pool': (None, [_h, _P(SwbSampler), _i32, _p, _p, _u64, _u64, _h]),
     'swb_resample_pool': (None, [_h, _u64, _u64, _h]),
+    'swb_sample_pool_tree': (None, [_h, _P(SwbTreeSampler), _i32, _p, _p, _u64, _u64, _h]),
+    'swb_sampler_exhausted': (None, [_h, _P(C.c_int64), _h]),
     'swb_get_pool': (None, [_h, _P(SwbPool)]),
     'swb_reset_all': (None, [_h, _h]),
     'swb_step': (None, [_h, _p, _P(SwbOutputs), _h]),

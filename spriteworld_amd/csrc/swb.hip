@@ -104,6 +104,11 @@ struct swb_engine {
   dev_buf<swb_sampler> d_sampler;
   int pool_entries = 0;
   bool pool_sampled = false, pool_uniform = false;   // pool came from swb_sample_pool / env-major fixed-length layout
+  // swb_sample_pool_tree: the spec with the handle's position grids, the sprites that ran out of tries, and whether the tree
+  // kernel filled the pool last (swb_resample_pool redraws with it)
+  dev_buf<swb_tree_dev> d_tree;
+  dev_buf<unsigned long long> d_exhausted;
+  bool pool_tree = false;
   dev_buf<double> d_x, d_y;
   dev_buf<int32_t> d_nspr, d_entry, d_step_count, d_episode;
   dev_buf<uint8_t> d_reset_next;
@@ -691,6 +696,179 @@ swb_sampler_args sampler_args(const swb_engine* h, uint64_t seed, uint64_t first
           h->d_p_label, h->d_p_attr};
 }
 
+
+// The device arrays of a pool of P entries that a sampler kernel is about to fill (swb_sample_pool, swb_sample_pool_tree), and
+// the environments' ranges in it; bound to the kernels' parameters.
+int alloc_sampled_pool(swb_engine* h, int P, const int32_t* pool_base_host, const int32_t* pool_len_host) {
+  const int S = h->p.S, T = h->p.n_tasks, N = h->p.N;
+  const size_t PS = (size_t)P * S;
+  int rc = 0;
+  h->rollout_stale = true;                        // (swb_rollout_frames: as in swb_set_pool)
+  if (h->pool_entries != P || !h->d_p_angle || !h->d_p_color || (h->keyed && !h->d_p_cell_label)) {
+    rc |= h->d_p_n.fill(nullptr, P);
+    rc |= h->d_p_x.fill(nullptr, PS); rc |= h->d_p_y.fill(nullptr, PS);
+    rc |= h->d_p_xv.fill(nullptr, PS); rc |= h->d_p_yv.fill(nullptr, PS);
+    rc |= h->d_p_scale.fill(nullptr, PS); rc |= h->d_p_ca.fill(nullptr, PS);
+    rc |= h->d_p_sa.fill(nullptr, PS);
+    rc |= h->d_p_shape.fill(nullptr, PS); rc |= h->d_p_rgb.fill(nullptr, PS);
+    rc |= h->d_p_label.fill(nullptr, (size_t)P * T * S);
+    if (h->keyed) rc |= h->d_p_cell_label.fill(nullptr, (size_t)P * T * S * SWB_MAX_CELLS);
+    rc |= h->d_p_attr.fill(nullptr, PS);
+    rc |= h->d_p_angle.fill(nullptr, PS); rc |= h->d_p_color.fill(nullptr, PS * 3);
+  }
+  rc |= h->d_pool_base.fill(pool_base_host, N);
+  rc |= h->d_pool_len.fill(pool_len_host, N);
+  if (rc) return SWB_ERR_HIP;
+  h->pool_entries = P;
+  bind_pool(h, true, true);
+  return 0;
+}
+
+// ... and once the kernel is launched: every environment resets on its next step (environment.py:70), the run lists get
+// their full reservation back, and the layout is remembered for swb_resample_pool.
+int finish_sampled_pool(swb_engine* h, const int32_t* pool_base_host, const int32_t* pool_len_host, hipStream_t st) {
+  const int N = h->p.N;
+  HIP_TRY(hipMemsetAsync(h->d_reset_next, 1, N, st));
+  HIP_TRY(hipMemsetAsync(h->d_episode, 0, sizeof(int32_t) * N, st));
+  HIP_TRY(hipMemsetAsync(h->d_step_count, 0, sizeof(int32_t) * N, st));
+  h->have_pool = true;
+  if (int rc2 = restore_run_list_reservation(h)) return rc2;
+  h->pool_sampled = true;
+  h->pool_uniform = true;
+  for (int i = 0; i < N; ++i)
+    if (pool_len_host[i] != pool_len_host[0] || pool_base_host[i] != i * pool_len_host[0]) h->pool_uniform = false;
+  return SWB_OK;
+}
+
+// swb_sample_tree_kernel over the whole pool (swb_sample_pool_tree), or over all but the live entries (swb_resample_pool).
+int launch_tree_sampler(swb_engine* h, uint64_t seed, uint64_t first_entry, bool skip_live, hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(h->d_exhausted, 0, sizeof(unsigned long long), st));
+  const swb_tree_args a = {sampler_args(h, seed, first_entry, skip_live), h->d_tree, h->keyed ? h->d_p_cell_label.ptr : nullptr,
+                           h->d_exhausted};
+  hipLaunchKernelGGL(swb_sample_tree_kernel, dim3((h->pool_entries + 255) / 256), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
+}
+
+bool cdf_ok(const double* cdf, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!(cdf[i] >= (i ? cdf[i - 1] : 0.0)) || !(cdf[i] <= 1.0)) return false;
+  return true;
+}
+
+// Everything swb_sample_tree_kernel relies on (include/swb.h, swb_sample_pool_tree): indices, jumps, stack depths, factor kinds.
+int check_tree_sampler(const swb_engine* h, const swb_tree_sampler* sp) {
+  if (sp->n_groups < 1 || sp->n_groups > SWB_MAX_GROUPS) return fail(SWB_ERR_INVALID, "n_groups must be in [1, %d]", SWB_MAX_GROUPS);
+  if (sp->shuffle < 0) return fail(SWB_ERR_INVALID, "shuffle must be >= 0");
+  if (sp->max_tries < 1) return fail(SWB_ERR_INVALID, "max_tries must be >= 1");
+  if (sp->n_tasks != h->p.n_tasks) return fail(SWB_ERR_INVALID, "the sampler labels %d tasks, the handle has %d", sp->n_tasks, h->p.n_tasks);
+  if (sp->n_leaves < 0 || sp->n_leaves > SWB_TREE_MAX_LEAVES) return fail(SWB_ERR_INVALID, "at most %d leaves", SWB_TREE_MAX_LEAVES);
+  if (sp->n_pred_nodes < 0 || sp->n_pred_nodes > SWB_TREE_MAX_PRED_NODES)
+    return fail(SWB_ERR_INVALID, "at most %d predicate nodes", SWB_TREE_MAX_PRED_NODES);
+  if (sp->n_preds < 0 || sp->n_preds > SWB_TREE_MAX_PREDS) return fail(SWB_ERR_INVALID, "at most %d predicates", SWB_TREE_MAX_PREDS);
+  if (sp->n_ops < 0 || sp->n_ops > SWB_TREE_MAX_OPS) return fail(SWB_ERR_INVALID, "at most %d ops", SWB_TREE_MAX_OPS);
+  if (sp->n_choices < 0 || sp->n_choices > SWB_TREE_MAX_CHOICES) return fail(SWB_ERR_INVALID, "at most %d choices", SWB_TREE_MAX_CHOICES);
+  if (sp->n_alternatives < 0 || sp->n_alternatives > SWB_MAX_ALTERNATIVES)
+    return fail(SWB_ERR_INVALID, "n_alternatives must be in [0, %d]", SWB_MAX_ALTERNATIVES);
+  for (int i = 0; i < sp->n_alternatives; ++i) {
+    const swb_alternative& alt = sp->alternatives[i];
+    if (alt.n < 1 || alt.n > SWB_MAX_GROUPS) return fail(SWB_ERR_INVALID, "alternative %d: 1..%d groups", i, SWB_MAX_GROUPS);
+    for (int g = 0; g < alt.n; ++g)
+      if (alt.group[g] < 0 || alt.group[g] >= sp->n_groups) return fail(SWB_ERR_INVALID, "alternative %d: bad group index", i);
+  }
+  if (sp->alternatives_weighted && (sp->n_alternatives < 1 || !cdf_ok(sp->alternative_cdf, sp->n_alternatives)))
+    return fail(SWB_ERR_INVALID, "alternative_cdf must be non-decreasing within [0, 1]");
+  for (int i = 0; i < sp->n_leaves; ++i) {
+    const swb_tree_leaf& lf = sp->leaves[i];
+    if (lf.factor < 0 || lf.factor >= SWB_TREE_N_FACTORS) return fail(SWB_ERR_INVALID, "leaf %d: bad factor index", i);
+    if (lf.kind < SWB_FACTOR_UNIFORM_F32 || lf.kind > SWB_FACTOR_DISCRETE) return fail(SWB_ERR_INVALID, "leaf %d: bad kind", i);
+    if (lf.kind == SWB_FACTOR_DISCRETE && (lf.n < 1 || lf.n > SWB_MAX_CANDIDATES))
+      return fail(SWB_ERR_INVALID, "leaf %d: Discrete leaves take 1..%d candidates", i, SWB_MAX_CANDIDATES);
+    if (lf.kind == SWB_FACTOR_DISCRETE && lf.weighted && !cdf_ok(lf.cdf, lf.n))
+      return fail(SWB_ERR_INVALID, "leaf %d: cdf must be non-decreasing within [0, 1]", i);
+    if (lf.factor == SWB_F_SHAPE) {
+      if (lf.kind != SWB_FACTOR_DISCRETE) return fail(SWB_ERR_INVALID, "leaf %d: shape must be a Discrete leaf", i);
+      for (int k = 0; k < lf.n; ++k)
+        if (!(lf.cand[k] >= 0.0 && lf.cand[k] < (double)SWB_MAX_SHAPES && lf.cand[k] == (double)(int)lf.cand[k]))
+          return fail(SWB_ERR_INVALID, "leaf %d: bad shape index", i);
+    }
+  }
+  for (int i = 0; i < sp->n_preds; ++i) {
+    const swb_tree_pred& pr = sp->preds[i];
+    if (pr.first < 0 || pr.n < 1 || pr.first + pr.n > sp->n_pred_nodes) return fail(SWB_ERR_INVALID, "predicate %d: nodes out of range", i);
+    int depth = 0;
+    for (int k = pr.first; k < pr.first + pr.n; ++k) {
+      const swb_pred_node& nd = sp->pred_nodes[k];
+      if (nd.op == SWB_PRED_LEAF) {
+        if (nd.leaf < 0 || nd.leaf >= sp->n_leaves) return fail(SWB_ERR_INVALID, "predicate %d: bad leaf index", i);
+        ++depth;
+      } else if (nd.op == SWB_PRED_TRUE) {
+        ++depth;
+      } else if (nd.op == SWB_PRED_AND || nd.op == SWB_PRED_OR || nd.op == SWB_PRED_ANDNOT) {
+        if (depth < 2) return fail(SWB_ERR_INVALID, "predicate %d: stack underflow at node %d", i, k - pr.first);
+        --depth;
+      } else {
+        return fail(SWB_ERR_INVALID, "predicate %d: bad op", i);
+      }
+      if (depth > SWB_TREE_MAX_STACK) return fail(SWB_ERR_INVALID, "predicate %d: stack deeper than %d", i, SWB_TREE_MAX_STACK);
+    }
+    if (depth != 1) return fail(SWB_ERR_INVALID, "predicate %d leaves %d values on the stack", i, depth);
+  }
+  for (int t = 0; t < sp->n_tasks; ++t) {
+    const swb_tree_task& tk = sp->tasks[t];
+    if (tk.kind != h->cfg.tasks[t].kind) return fail(SWB_ERR_INVALID, "task %d: kind differs from the handle's", t);
+    if (tk.n_preds < 0 || tk.n_preds > SWB_TREE_MAX_CLUSTERS || (tk.kind == SWB_TASK_FIND_GOAL && tk.n_preds > 1))
+      return fail(SWB_ERR_INVALID, "task %d: bad predicate count", t);
+    for (int k = 0; k < tk.n_preds; ++k)
+      if (tk.pred[k] < 0 || tk.pred[k] >= sp->n_preds) return fail(SWB_ERR_INVALID, "task %d: bad predicate index", t);
+  }
+  for (int i = 0; i < sp->n_choices; ++i) {
+    const swb_tree_choice& ch = sp->choices[i];
+    if (ch.n < 1 || ch.n > SWB_MAX_CANDIDATES || !cdf_ok(ch.cdf, ch.n))
+      return fail(SWB_ERR_INVALID, "choice %d: 1..%d targets, cdf non-decreasing within [0, 1]", i, SWB_MAX_CANDIDATES);
+  }
+  for (int g = 0; g < sp->n_groups; ++g) {
+    const swb_tree_group& grp = sp->groups[g];
+    if (grp.count_min < 0 || grp.count_max < grp.count_min) return fail(SWB_ERR_INVALID, "group %d: bad sprite count range", g);
+    if (grp.first_op < 0 || grp.n_ops < 0 || grp.first_op + grp.n_ops > sp->n_ops) return fail(SWB_ERR_INVALID, "group %d: program out of range", g);
+    const double dsh = grp.defaults[SWB_F_SHAPE];
+    if (!(dsh >= 0.0 && dsh < (double)SWB_MAX_SHAPES && dsh == (double)(int)dsh)) return fail(SWB_ERR_INVALID, "group %d: bad default shape", g);
+    const int end = grp.first_op + grp.n_ops;
+    bool draws_x = false, draws_y = false;
+    for (int pc = grp.first_op; pc < end; ++pc) {
+      const swb_tree_op& op = sp->ops[pc];
+      if (op.kind == SWB_OP_DRAW) {
+        if (op.a < 0 || op.a >= sp->n_leaves) return fail(SWB_ERR_INVALID, "group %d, op %d: bad leaf index", g, pc);
+        const swb_tree_leaf& lf = sp->leaves[op.a];
+        if (lf.factor == SWB_F_X || lf.factor == SWB_F_Y) {
+          if (lf.kind != SWB_FACTOR_UNIFORM_F32) return fail(SWB_ERR_INVALID, "group %d: x and y must be float32 Continuous factors", g);
+          (lf.factor == SWB_F_X ? draws_x : draws_y) = true;
+        }
+        if (lf.factor == SWB_F_ANGLE && (lf.kind == SWB_FACTOR_UNIFORM_F32 ||
+                                        (lf.kind == SWB_FACTOR_UNIFORM_INT && !(lf.lo >= 0.0 && lf.hi <= 360.0 && lf.lo <= lf.hi))))
+          return fail(SWB_ERR_INVALID, "group %d: angle must be Discrete or integer degrees within [0, 360]", g);
+        if (sp->color_map == 1 && lf.kind == SWB_FACTOR_UNIFORM_INT && lf.factor >= SWB_F_C0 && lf.factor <= SWB_F_C2)
+          return fail(SWB_ERR_INVALID, "group %d: hsv colours must be float factors", g);
+      } else if (op.kind == SWB_OP_CHOOSE) {
+        if (op.a < 0 || op.a >= sp->n_choices) return fail(SWB_ERR_INVALID, "group %d, op %d: bad choice index", g, pc);
+        const swb_tree_choice& ch = sp->choices[op.a];
+        for (int k = 0; k < ch.n; ++k)
+          if (ch.target[k] <= pc || ch.target[k] > end) return fail(SWB_ERR_INVALID, "group %d, op %d: choice target %d outside (%d, %d]", g, pc, ch.target[k], pc, end);
+      } else if (op.kind == SWB_OP_JUMP) {
+        if (op.a > end) return fail(SWB_ERR_INVALID, "group %d, op %d: jump to %d, outside the program [%d, %d]", g, pc, op.a, grp.first_op, end);
+        if (op.a <= pc) return fail(SWB_ERR_INVALID, "group %d, op %d: backward JUMP to %d (only TEST goes back)", g, pc, op.a);
+      } else if (op.kind == SWB_OP_TEST) {
+        if (op.a < 0 || op.a >= sp->n_preds) return fail(SWB_ERR_INVALID, "group %d, op %d: bad predicate index", g, pc);
+        if (op.c < grp.first_op || op.c > pc) return fail(SWB_ERR_INVALID, "group %d, op %d: TEST retries at %d, outside [%d, %d]", g, pc, op.c, grp.first_op, pc);
+      } else {
+        return fail(SWB_ERR_INVALID, "group %d, op %d: bad op kind", g, pc);
+      }
+    }
+    if (!draws_x || !draws_y) return fail(SWB_ERR_INVALID, "group %d: x and y must be float32 Continuous factors", g);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1063,7 +1241,7 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
   if (!h || !spec || !pool_base_host || !pool_len_host) return fail(SWB_ERR_INVALID, "null argument");
   bump_list_epoch(h);
   HIP_TRY(hipSetDevice(h->device));
-  const int P = n_entries, S = h->p.S, T = h->p.n_tasks, N = h->p.N;
+  const int P = n_entries, S = h->p.S, N = h->p.N;
   if (P < 1) return fail(SWB_ERR_INVALID, "pool is empty");
   if (h->keyed) return fail(SWB_ERR_INVALID, "a task of this handle keys on position: its labels depend on where a sprite is drawn -- sample such "
                             "generators on the host (swb_set_pool with swb_pool::cell_label)");
@@ -1138,40 +1316,13 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
   for (int i = 0; i < N; ++i)
     if (pool_len_host[i] < 1 || pool_base_host[i] < 0 || pool_base_host[i] + pool_len_host[i] > P)
       return fail(SWB_ERR_INVALID, "env %d: pool range [%d, +%d) outside the pool of %d", i, pool_base_host[i], pool_len_host[i], P);
-  const size_t PS = (size_t)P * S;
-  int rc = 0;
-  h->rollout_stale = true;                        // (swb_rollout_frames: as in swb_set_pool)
-  if (h->pool_entries != P || !h->d_p_angle || !h->d_p_color) {
-    rc |= h->d_p_n.fill(nullptr, P);
-    rc |= h->d_p_x.fill(nullptr, PS); rc |= h->d_p_y.fill(nullptr, PS);
-    rc |= h->d_p_xv.fill(nullptr, PS); rc |= h->d_p_yv.fill(nullptr, PS);
-    rc |= h->d_p_scale.fill(nullptr, PS); rc |= h->d_p_ca.fill(nullptr, PS);
-    rc |= h->d_p_sa.fill(nullptr, PS);
-    rc |= h->d_p_shape.fill(nullptr, PS); rc |= h->d_p_rgb.fill(nullptr, PS);
-    rc |= h->d_p_label.fill(nullptr, (size_t)P * T * S);
-    rc |= h->d_p_attr.fill(nullptr, PS);
-    rc |= h->d_p_angle.fill(nullptr, PS); rc |= h->d_p_color.fill(nullptr, PS * 3);
-  }
-  rc |= h->d_pool_base.fill(pool_base_host, N);
-  rc |= h->d_pool_len.fill(pool_len_host, N);
-  rc |= h->d_sampler.fill(spec, 1);
-  if (rc) return SWB_ERR_HIP;
-  h->pool_entries = P;
-  bind_pool(h, true, true);
+  if (alloc_sampled_pool(h, P, pool_base_host, pool_len_host) || h->d_sampler.fill(spec, 1)) return SWB_ERR_HIP;
   const swb_sampler_args a = sampler_args(h, seed, first_entry, false);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((P + 255) / 256), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(h->d_reset_next, 1, N, st));      // environment.py:70
-  HIP_TRY(hipMemsetAsync(h->d_episode, 0, sizeof(int32_t) * N, st));
-  HIP_TRY(hipMemsetAsync(h->d_step_count, 0, sizeof(int32_t) * N, st));
-  h->have_pool = true;
-  if (int rc2 = restore_run_list_reservation(h)) return rc2;
-  h->pool_sampled = true;
-  h->pool_uniform = true;
-  for (int i = 0; i < N; ++i)
-    if (pool_len_host[i] != pool_len_host[0] || pool_base_host[i] != i * pool_len_host[0]) h->pool_uniform = false;
-  return SWB_OK;
+  h->pool_tree = false;
+  return finish_sampled_pool(h, pool_base_host, pool_len_host, st);
 }
 
 int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* stream) {
@@ -1182,9 +1333,83 @@ int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* s
     return fail(SWB_ERR_STATE, "swb_resample_pool needs the env-major layout pool_base[n] = n * pool_len, equal pool_len");
   HIP_TRY(hipSetDevice(h->device));
   h->rollout_stale = true;      // (swb_rollout_frames: only entries the LIVE environments play are kept, a candidate's may be redrawn)
+  if (h->pool_tree) return launch_tree_sampler(h, seed, first_entry, true, (hipStream_t)stream);
   const swb_sampler_args a = sampler_args(h, seed, first_entry, true);
   hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((h->pool_entries + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
+  return SWB_OK;
+}
+
+int swb_sample_pool_tree(swb_handle h, const swb_tree_sampler* spec, int32_t n_entries, const int32_t* pool_base_host,
+                         const int32_t* pool_len_host, uint64_t seed, uint64_t first_entry, void* stream) {
+  if (!h || !spec || !pool_base_host || !pool_len_host) return fail(SWB_ERR_INVALID, "null argument");
+  bump_list_epoch(h);
+  HIP_TRY(hipSetDevice(h->device));
+  const int P = n_entries, S = h->p.S, N = h->p.N;
+  if (P < 1) return fail(SWB_ERR_INVALID, "pool is empty");
+  if (!h->cfg.pos_is_f32) return fail(SWB_ERR_INVALID, "the device sampler draws float32 positions (swb_config::pos_is_f32)");
+  if (int rc = check_tree_sampler(h, spec)) return rc;
+  auto over_lists = [&](auto per_group) {          // the most of a per-group figure an episode can add up to
+    int most = 0;
+    if (spec->n_alternatives > 0) {
+      for (int i = 0; i < spec->n_alternatives; ++i) {
+        int tot = 0;
+        for (int g = 0; g < spec->alternatives[i].n; ++g) tot += per_group(spec->groups[spec->alternatives[i].group[g]]);
+        most = std::max(most, tot);
+      }
+    } else {
+      for (int g = 0; g < spec->n_groups; ++g) most += per_group(spec->groups[g]);
+    }
+    return most;
+  };
+  const int max_total = over_lists([](const swb_tree_group& grp) { return grp.count_max; });
+  if (max_total > S) return fail(SWB_ERR_INVALID, "sampler can emit %d sprites (max_sprites %d)", max_total, S);
+  if (h->have_shapes) {       // the most polygon vertices an episode of this sampler can have (LDS sizing)
+    auto verts_of = [&](double shape) { return (int)shape < (int)h->shape_nverts.size() ? h->shape_nverts[(int)shape] : 0; };
+    const int most = over_lists([&](const swb_tree_group& grp) {
+      int mv = 0;
+      bool drawn = false;
+      for (int pc = grp.first_op; pc < grp.first_op + grp.n_ops; ++pc) {
+        if (spec->ops[pc].kind != SWB_OP_DRAW || spec->leaves[spec->ops[pc].a].factor != SWB_F_SHAPE) continue;
+        const swb_tree_leaf& lf = spec->leaves[spec->ops[pc].a];
+        for (int i = 0; i < lf.n; ++i) mv = std::max(mv, verts_of(lf.cand[i]));
+        drawn = true;
+      }
+      if (!drawn) mv = verts_of(grp.defaults[SWB_F_SHAPE]);
+      return mv * grp.count_max;
+    });
+    if (int rc = lf_check_vertices(h, (std::max(most, 1) + 3) & ~3, "swb_sample_pool_tree")) return rc;
+    h->p.max_edges = (std::max(most, 1) + 3) & ~3;
+  }
+  for (int i = 0; i < N; ++i)
+    if (pool_len_host[i] < 1 || pool_base_host[i] < 0 || pool_base_host[i] + pool_len_host[i] > P)
+      return fail(SWB_ERR_INVALID, "env %d: pool range [%d, +%d) outside the pool of %d", i, pool_base_host[i], pool_len_host[i], P);
+  auto dev = std::make_unique<swb_tree_dev>();
+  memset(dev.get(), 0, sizeof(swb_tree_dev));
+  dev->spec = *spec;
+  for (int t = 0; t < h->p.n_tasks; ++t) {
+    const swb_task& tk = h->cfg.tasks[t];
+    dev->n_xcuts[t] = tk.n_xcuts; dev->n_ycuts[t] = tk.n_ycuts;
+    for (int k = 0; k < SWB_MAX_CUTS; ++k) { dev->xcuts[t][k] = tk.xcuts[k]; dev->ycuts[t][k] = tk.ycuts[k]; }
+  }
+  if (alloc_sampled_pool(h, P, pool_base_host, pool_len_host) || h->d_tree.fill(dev.get(), 1) ||
+      (!h->d_exhausted && h->d_exhausted.fill(nullptr, 1)))
+    return SWB_ERR_HIP;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch_tree_sampler(h, seed, first_entry, false, st)) return rc;
+  h->pool_tree = true;
+  return finish_sampled_pool(h, pool_base_host, pool_len_host, st);
+}
+
+int swb_sampler_exhausted(swb_handle h, int64_t* sprites, void* stream) {
+  if (!h || !sprites) return fail(SWB_ERR_INVALID, "null argument");
+  *sprites = 0;
+  if (!h->d_exhausted) return SWB_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpy(&n, h->d_exhausted, sizeof(n), hipMemcpyDeviceToHost));
+  *sprites = (int64_t)n;
   return SWB_OK;
 }
 
@@ -1204,6 +1429,7 @@ int swb_get_pool(swb_handle h, const swb_pool* pool) {
   SWB_D2H(pool->scale, h->d_p_scale, PS); SWB_D2H(pool->cos_a, h->d_p_ca, PS); SWB_D2H(pool->sin_a, h->d_p_sa, PS);
   SWB_D2H(pool->shape, h->d_p_shape, PS);
   SWB_D2H(pool->label, h->d_p_label, (size_t)P * T * S);
+  if (h->keyed) SWB_D2H(pool->cell_label, h->d_p_cell_label, (size_t)P * T * S * SWB_MAX_CELLS);
   SWB_D2H(pool->attr_f32, h->d_p_attr, PS);
   SWB_D2H(pool->pool_base, h->d_pool_base, (size_t)N); SWB_D2H(pool->pool_len, h->d_pool_len, (size_t)N);
   if (h->p.p_angle) SWB_D2H(pool->angle, h->d_p_angle, PS);

@@ -229,6 +229,242 @@ __global__ void __launch_bounds__(256) swb_sample_pool_kernel(const swb_sampler_
 }
 
 // --------------------------------------------------------------------------------------------
+// The general sampler (swb_sample_pool_tree, include/swb.h): any tree of factor distributions, as a bytecode program per sprite
+// group, with `contains()` as postfix predicates over leaf tests -- so rejection loops close on the device, labels are evaluated
+// per sprite from the values drawn, and per cell of the position grid for tasks that key on position.
+// The launch shape, the Philox streams, the live-entry skip and steps 0 - 2 of the draw order are swb_sample_pool_kernel's
+// (with `alternatives_weighted`, step 0 is one uniform() against alternative_cdf).  Then per sprite, in generation order, the
+// group's program from its first op until it runs off its end (tests/_sampler_tree_model.py restates it, bit for bit):
+//   DRAW    UNIFORM_*: two u32, as draw_factor.  DISCRETE: u32 % n, or weighted: u = uniform(), index = #{i : cdf[i] <= u}.
+//   CHOOSE  u = uniform(), go to target[#{i : cdf[i] <= u}].
+//   JUMP    forward.
+//   TEST    predicate == accept_if: go on; else one more of the sprite's max_tries is spent and the program goes back to
+//           retry_pc -- when none is left the draw is kept, every later TEST passes and the sprite is counted as exhausted.
+// Every jump was checked on the host: backward only from TEST, so a sprite takes at most (max_tries + 1) * n_ops ops.
+// --------------------------------------------------------------------------------------------
+struct swb_tree_dev {            // what the kernel reads: the caller's spec and the position grids of the handle's tasks
+  swb_tree_sampler spec;
+  int32_t n_xcuts[SWB_MAX_TASKS], n_ycuts[SWB_MAX_TASKS];
+  double xcuts[SWB_MAX_TASKS][SWB_MAX_CUTS], ycuts[SWB_MAX_TASKS][SWB_MAX_CUTS];
+};
+
+struct swb_tree_args {
+  swb_sampler_args pool;         // (spec unused)
+  const swb_tree_dev* tree;
+  int8_t* p_cell_label;          // [P][T][S][SWB_MAX_CELLS], or null: no task of the handle keys on position
+  unsigned long long* exhausted; // sprites whose retry budget ran out
+};
+
+// The factors of the sprite being drawn, each with the type the reference would hold (factor_value::py; `shape`: its table index).
+struct tree_values {
+  double v[SWB_TREE_N_FACTORS];
+  int py[SWB_TREE_N_FACTORS];
+};
+
+// numpy's choice(p=...): cdf.searchsorted(u, side='right')
+__device__ inline int tree_cdf_index(const double* cdf, int n, double u) {
+  int i = 0;
+  for (int k = 0; k < n; ++k) i += (cdf[k] <= u) ? 1 : 0;
+  return i < n ? i : n - 1;
+}
+
+// Continuous.contains / Discrete.contains of one leaf (factor_distributions.py:105-112,146-148) under NEP 50: an np.float32
+// value meets the bound rounded to float32, every other value is compared in float64.
+__device__ inline bool tree_leaf_test(const swb_tree_leaf& lf, const tree_values& tv) {
+  const double v = tv.v[lf.factor];
+  if (lf.factor == SWB_F_SHAPE) return ((lf.shape_mask >> ((uint32_t)(int)v & 31u)) & 1u) != 0u;
+  const bool f32 = tv.py[lf.factor] == 0;
+  if (lf.kind != SWB_FACTOR_DISCRETE) return f32 ? (v >= lf.lo32 && v < lf.hi32) : (v >= lf.lo && v < lf.hi);
+  bool in = false;
+  for (int i = 0; i < lf.n; ++i) in = in || (v == (f32 ? lf.cand32[i] : lf.cand[i]));
+  return in;
+}
+
+// A predicate: postfix over leaf tests, the stack is the bits of one word (at most SWB_TREE_MAX_STACK deep: checked on the host).
+__device__ inline bool tree_pred(const swb_tree_sampler& sp, int pi, const tree_values& tv) {
+  const swb_tree_pred pr = sp.preds[pi];
+  uint32_t st = 0u;
+  for (int k = pr.first; k < pr.first + pr.n; ++k) {
+    const swb_pred_node nd = sp.pred_nodes[k];
+    if (nd.op == SWB_PRED_LEAF) {
+      st = (st << 1) | (tree_leaf_test(sp.leaves[nd.leaf], tv) ? 1u : 0u);
+    } else if (nd.op == SWB_PRED_TRUE) {
+      st = (st << 1) | 1u;
+    } else {
+      const uint32_t b = st & 1u, a = (st >> 1) & 1u;
+      const uint32_t r = nd.op == SWB_PRED_AND ? (a & b) : (nd.op == SWB_PRED_OR ? (a | b) : (a & (b ^ 1u)));
+      st = ((st >> 2) << 1) | r;
+    }
+  }
+  return (st & 1u) != 0u;
+}
+
+// tasks.py:134-137 (FindGoalPosition filter), :196-205 (first cluster that contains the sprite, else -1)
+__device__ inline int tree_label(const swb_tree_sampler& sp, const swb_tree_task& tk, const tree_values& tv) {
+  if (tk.kind == SWB_TASK_FIND_GOAL) return tk.n_preds == 0 ? 1 : (tree_pred(sp, tk.pred[0], tv) ? 1 : 0);
+  if (tk.kind == SWB_TASK_CLUSTERING) {
+    for (int k = 0; k < tk.n_preds; ++k)
+      if (tree_pred(sp, tk.pred[k], tv)) return k;
+    return -1;
+  }
+  return 0;
+}
+
+__global__ void __launch_bounds__(256) swb_sample_tree_kernel(const swb_tree_args ta) {
+  const swb_sampler_args& a = ta.pool;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.P) return;
+  if (a.live_entry) {
+    // pools are laid out env-major with a fixed length (pool_base[n] = n * pool_len[0])
+    const int k = a.env_pool_len[0];
+    const int env = e / k;
+    if (env < a.N && a.env_pool_base[env] == env * k && a.live_entry[env] == e) return;
+  }
+  const swb_tree_dev* __restrict__ td = ta.tree;
+  const swb_tree_sampler& sp = td->spec;
+  philox_stream rng;
+  rng.key0 = (uint32_t)a.seed; rng.key1 = (uint32_t)(a.seed >> 32); rng.block = 0u; rng.have = 0;
+  const uint64_t ge = a.first_entry + (uint64_t)e;
+  rng.entry = (uint32_t)ge; rng.entry_hi = (uint32_t)(ge >> 32);
+  const int S = a.S, T = a.T;
+
+  // sample_generator: which list of groups this episode generates
+  int list[SWB_MAX_GROUPS];
+  int G = sp.n_groups;
+  if (sp.n_alternatives > 0) {
+    int ai = 0;
+    if (sp.alternatives_weighted) ai = tree_cdf_index(sp.alternative_cdf, sp.n_alternatives, rng.uniform());
+    else if (sp.n_alternatives > 1) ai = (int)(rng.u32() % (uint32_t)sp.n_alternatives);
+    const swb_alternative& alt = sp.alternatives[ai];
+    G = alt.n;
+    for (int g = 0; g < SWB_MAX_GROUPS; ++g) list[g] = alt.group[g < G ? g : 0];
+  } else {
+    for (int g = 0; g < SWB_MAX_GROUPS; ++g) list[g] = g;
+  }
+  int counts[SWB_MAX_GROUPS];
+  int n = 0;
+  for (int g = 0; g < G; ++g) {
+    const swb_tree_group& grp = sp.groups[list[g]];
+    int c = grp.count_min + (int)(rng.u32() % (uint32_t)(grp.count_max - grp.count_min + 1));
+    if (n + c > S) c = S - n;
+    counts[g] = c;
+    n += c;
+  }
+  // z-order: slot[k] = where the k-th generated sprite lands (sprite_generators.shuffle:124-126)
+  uint8_t slot[SWB_MAX_SPRITES];
+  for (int k = 0; k < SWB_MAX_SPRITES; ++k) slot[k] = (uint8_t)k;
+  int n_shuffled = 0;
+  for (int g = 0; g < G && g < sp.shuffle; ++g) n_shuffled += counts[g];
+  if (n_shuffled > 1)
+    for (int i = n_shuffled - 1; i >= 1; --i) {
+      const int j = (int)(rng.u32() % (uint32_t)(i + 1));
+      const uint8_t t = slot[i]; slot[i] = slot[j]; slot[j] = t;
+    }
+  a.p_n[e] = n;
+  unsigned long long n_spent = 0ull;
+  int k = 0;
+  for (int g = 0; g < G; ++g) {
+    const swb_tree_group& grp = sp.groups[list[g]];
+    for (int c = 0; c < counts[g]; ++c, ++k) {
+      const size_t o = (size_t)e * S + slot[k];
+      tree_values tv;
+      for (int i = 0; i < SWB_TREE_N_FACTORS; ++i) { tv.v[i] = grp.defaults[i]; tv.py[i] = 1; }
+      double ca = grp.default_cos, sa = grp.default_sin;
+      int tries = 0;
+      bool spent = false;
+      const int end = grp.first_op + grp.n_ops;
+      for (int pc = grp.first_op; pc < end;) {
+        const swb_tree_op op = sp.ops[pc];
+        if (op.kind == SWB_OP_DRAW) {
+          const swb_tree_leaf& lf = sp.leaves[op.a];
+          if (lf.kind == SWB_FACTOR_DISCRETE) {
+            const int i = lf.weighted ? tree_cdf_index(lf.cdf, lf.n, rng.uniform()) : (int)(rng.u32() % (uint32_t)lf.n);
+            tv.v[lf.factor] = lf.cand[i]; tv.py[lf.factor] = 1;
+            if (lf.factor == SWB_F_ANGLE) { ca = lf.cos_a[i]; sa = lf.sin_a[i]; }
+          } else {
+            const double val = __dadd_rn(lf.lo, __dmul_rn(__dsub_rn(lf.hi, lf.lo), rng.uniform()));  // np.random.uniform
+            if (lf.kind == SWB_FACTOR_UNIFORM_INT) {                                                 // .astype(int)
+              tv.v[lf.factor] = trunc(val); tv.py[lf.factor] = 2;
+              if (lf.factor == SWB_F_ANGLE) {   // integer degrees in [0, 360]
+                const int d = ((int)tv.v[lf.factor]) % 360;
+                ca = sp.deg_cos[d]; sa = sp.deg_sin[d];
+              }
+            } else {                                                                                 // .astype(float32)
+              tv.v[lf.factor] = (double)(float)val; tv.py[lf.factor] = 0;
+            }
+          }
+          ++pc;
+        } else if (op.kind == SWB_OP_CHOOSE) {
+          const swb_tree_choice& ch = sp.choices[op.a];
+          pc = ch.target[tree_cdf_index(ch.cdf, ch.n, rng.uniform())];
+        } else if (op.kind == SWB_OP_JUMP) {
+          pc = op.a;
+        } else {  // SWB_OP_TEST
+          if (spent || tree_pred(sp, op.a, tv) == (op.b != 0)) {
+            ++pc;
+          } else if (++tries >= sp.max_tries) {
+            spent = true;
+            ++pc;
+          } else {
+            pc = op.c;
+          }
+        }
+      }
+      if (spent) n_spent += 1ull;
+      const factor_value x{tv.v[SWB_F_X], tv.py[SWB_F_X]}, y{tv.v[SWB_F_Y], tv.py[SWB_F_Y]};
+      const factor_value scale{tv.v[SWB_F_SCALE], tv.py[SWB_F_SCALE]}, angle{tv.v[SWB_F_ANGLE], tv.py[SWB_F_ANGLE]};
+      const factor_value c0{tv.v[SWB_F_C0], tv.py[SWB_F_C0]}, c1{tv.v[SWB_F_C1], tv.py[SWB_F_C1]}, c2{tv.v[SWB_F_C2], tv.py[SWB_F_C2]};
+      a.p_x[o] = x.v; a.p_y[o] = y.v; a.p_xv[o] = tv.v[SWB_F_XVEL]; a.p_yv[o] = tv.v[SWB_F_YVEL];
+      a.p_shape[o] = (int32_t)tv.v[SWB_F_SHAPE];
+      a.p_scale[o] = scale.v;
+      a.p_angle[o] = angle.v;
+      a.p_ca[o] = ca; a.p_sa[o] = sa;
+      a.p_color[3 * o] = c0.v; a.p_color[3 * o + 1] = c1.v; a.p_color[3 * o + 2] = c2.v;
+      uint32_t rgb;
+      if (sp.color_map == 1) rgb = swb_hsv_to_rgb(c0, c1, c2);
+      else rgb = ((uint32_t)(int)c0.v & 255u) | (((uint32_t)(int)c1.v & 255u) << 8) | (((uint32_t)(int)c2.v & 255u) << 16);
+      a.p_rgb[o] = rgb;
+      a.p_attr[o] = (uint8_t)((angle.py == 0 ? 1 : 0) | (scale.py == 0 ? 2 : 0));
+      for (int t = 0; t < T; ++t) {
+        const size_t lo = ((size_t)e * T + t) * S + slot[k];
+        a.p_label[lo] = (int8_t)tree_label(sp, sp.tasks[t], tv);
+        if (!ta.p_cell_label) continue;
+        // lowering.cell_labels_of: the label with x / y at the representative of every cell of the task's grid
+        int8_t* cells = ta.p_cell_label + lo * SWB_MAX_CELLS;
+        const int nx = td->n_xcuts[t], ny = td->n_ycuts[t];
+        int q = 0;
+        if (nx + ny > 0) {
+          tv.py[SWB_F_X] = 0; tv.py[SWB_F_Y] = 0;
+          for (int cy = 0; cy <= ny; ++cy)
+            for (int cx = 0; cx <= nx; ++cx, ++q) {
+              tv.v[SWB_F_X] = cx == 0 ? -__builtin_huge_val() : td->xcuts[t][cx - 1];
+              tv.v[SWB_F_Y] = cy == 0 ? -__builtin_huge_val() : td->ycuts[t][cy - 1];
+              cells[q] = (int8_t)tree_label(sp, sp.tasks[t], tv);
+            }
+          tv.v[SWB_F_X] = x.v; tv.py[SWB_F_X] = x.py; tv.v[SWB_F_Y] = y.v; tv.py[SWB_F_Y] = y.py;
+        }
+        for (; q < SWB_MAX_CELLS; ++q) cells[q] = 0;
+      }
+    }
+  }
+  if (n_spent) atomicAdd(ta.exhausted, n_spent);
+  // unused slots: neutral values (never read: every loop is bounded by n_sprites)
+  for (int q = n; q < S; ++q) {
+    const size_t o = (size_t)e * S + q;
+    a.p_x[o] = 0.0; a.p_y[o] = 0.0; a.p_xv[o] = 0.0; a.p_yv[o] = 0.0; a.p_shape[o] = 0; a.p_scale[o] = 1.0;
+    a.p_angle[o] = 0.0; a.p_ca[o] = 1.0; a.p_sa[o] = 0.0; a.p_rgb[o] = 0u;
+    a.p_color[3 * o] = 0.0; a.p_color[3 * o + 1] = 0.0; a.p_color[3 * o + 2] = 0.0;
+    a.p_attr[o] = 0;
+    for (int t = 0; t < T; ++t) {
+      const size_t lo = ((size_t)e * T + t) * S + q;
+      a.p_label[lo] = 0;
+      if (ta.p_cell_label)
+        for (int c = 0; c < SWB_MAX_CELLS; ++c) ta.p_cell_label[lo * SWB_MAX_CELLS + c] = 0;
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------
 // Random-agent actions (swb_sample_actions, include/swb.h): one wave per environment draws the environment's next action
 // -- uniform, or a click inside a randomly chosen sprite (environment.py:110-126, sprite.py:117-126) -- from the sprites as
 // they are now.  The handle is only read, and everything read was written by earlier launches (as_const: scalar loads).

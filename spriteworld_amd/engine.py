@@ -117,6 +117,25 @@ class Engine(object):
     self._pool_entries = int(n_entries)
     self._rendered = 0
 
+  def sample_pool_tree(self, spec, n_entries, pool_base, pool_len, seed, first_entry=0):
+    """`sample_pool` for an _abi.SwbTreeSampler (swb_sample_pool_tree): any tree of factor distributions, labels per sprite,
+    tasks that key on position included."""
+    base = np.ascontiguousarray(pool_base, dtype=np.int32)
+    length = np.ascontiguousarray(pool_len, dtype=np.int32)
+    assert base.shape == (self.N,) and length.shape == (self.N,)
+    self._check(self.lib.swb_sample_pool_tree(self._h, C.byref(spec), int(n_entries), _ptr(base), _ptr(length),
+                                              C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(first_entry)),
+                                              self._stream()))
+    self.pool = None
+    self._pool_entries = int(n_entries)
+    self._rendered = 0
+
+  def sampler_exhausted(self):
+    """Sprites of the last tree (re)sampling whose retry budget ran out (swb_sampler_exhausted; blocking)."""
+    n = C.c_int64(0)
+    self._check(self.lib.swb_sampler_exhausted(self._h, C.byref(n), self._stream()))
+    return n.value
+
   def resample_pool(self, seed, first_entry=0):
     """Fresh episodes in every pool entry no environment is playing; nothing is reset (swb_resample_pool)."""
     self._check(self.lib.swb_resample_pool(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
@@ -129,6 +148,8 @@ class Engine(object):
     pool = lowering.Pool(n, self.S, self.cfg.n_tasks)
     pool.pool_base = np.zeros(self.N, np.int32)
     pool.pool_len = np.zeros(self.N, np.int32)
+    if any(t.n_xcuts + t.n_ycuts for t in self.cfg.tasks[:self.cfg.n_tasks]):     # a task keys on position
+      pool.cell_label = np.zeros((n, self.cfg.n_tasks, self.S, _abi.SWB_MAX_CELLS), np.int8)
     cpool = pool.as_struct()
     self._check(self.lib.swb_get_pool(self._h, C.byref(cpool)))
     return pool

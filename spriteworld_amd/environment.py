@@ -21,6 +21,10 @@ ignores its action and returns FIRST (:90-91).  Where new episodes come from:
     (device_sampler, Philox streams keyed by `seed`) and the idle pool entries
     are redrawn every `refresh_every` steps, so an environment never meets an
     episode twice -- the reference's "fresh init_sprites() at every reset";
+  * `device_reset='tree'`: the same, and generators or tasks that path refuses
+    (Mixture / Intersection / Selection, any SetMinus, weighted choices, tasks
+    that select by a drawn value or key on position) are drawn on the device
+    too, by device_sampler.TreeSampler; LoweringError if neither lowers;
   * otherwise (opaque `init_sprites` callables) the pool holds
     `episodes_per_env` host draws per environment and each environment CYCLES
     through them: a long run replays these episodes until `refill_pool()` is
@@ -120,11 +124,20 @@ class BatchedEnvironment(object):
     # 'auto' -- when it was built with sprite_generators.* from Product/SetMinus/Continuous/Discrete
     # distributions (the generator's closures are read, device_sampler.from_generator); 'auto' falls
     # back to calling init_sprites() on the host when that is not possible.
-    self._sampler = init_sprites if isinstance(init_sprites, device_sampler.DeviceSampler) else None
+    # device_reset='tree': generators the DeviceSampler takes draw the episodes they draw today; every other tree of factor
+    # distributions, and tasks that select by a sampled value or key on position, go through device_sampler.TreeSampler
+    # (swb_sample_pool_tree); LoweringError if neither lowers.
+    self._sampler = init_sprites if isinstance(init_sprites, (device_sampler.DeviceSampler, device_sampler.TreeSampler)) else None
     if self._sampler is None and device_reset:
       try:
-        sampler = device_sampler.from_generator(init_sprites, seed=0)
-        sampler.lower(task, renderers)
+        try:
+          sampler = device_sampler.from_generator(init_sprites, seed=0)
+          sampler.lower(task, renderers)
+        except lowering.LoweringError:
+          if device_reset != 'tree':
+            raise
+          sampler = device_sampler.from_generator(init_sprites, seed=0, tree=True)
+          sampler.lower(task, renderers)
         # `seed` keys the Philox episode streams; None draws it from numpy's global stream, so np.random.seed()
         # makes runs reproducible and different seeds give different episodes.  Drawn only once the generator is
         # known to lower: a generator that falls back to the host path sees numpy's stream untouched.
@@ -180,9 +193,9 @@ class BatchedEnvironment(object):
     if self._sampler is not None:
       k = self._episodes_per_env
       base = np.arange(self._num_envs, dtype=np.int32) * k
-      self._engine.sample_pool(self._sampler_spec, self._num_envs * k, base,
-                               np.full(self._num_envs, k, np.int32), self._sampler.next_seed(),
-                               first_entry=self._global_env_offset * k)
+      sample = self._engine.sample_pool_tree if self._tree_sampled else self._engine.sample_pool
+      sample(self._sampler_spec, self._num_envs * k, base, np.full(self._num_envs, k, np.int32), self._sampler.next_seed(),
+             first_entry=self._global_env_offset * k)
       return
     episodes = self._draw_episodes()
     pool = lowering.lower_episodes(episodes, self._task, self._renderers,
@@ -190,8 +203,12 @@ class BatchedEnvironment(object):
     pool.assign_round_robin(self._num_envs, self._episodes_per_env)
     self._engine.set_pool(pool)
 
+  @property
+  def _tree_sampled(self):
+    return isinstance(self._sampler, device_sampler.TreeSampler)
+
   def refresh_pool(self):
-    """DeviceSampler only: redraws every pool entry that no environment is playing right now, without
+    """DeviceSampler / TreeSampler only: redraws every pool entry that no environment is playing right now, without
     resetting anything.  Called every few episodes, environments never meet an episode twice."""
     if self._sampler is None:
       raise lowering.LoweringError('refresh_pool() needs init_sprites to be a device_sampler.DeviceSampler')
@@ -255,6 +272,11 @@ class BatchedEnvironment(object):
   def check(self):
     """Raises what the reference would have raised if any environment flagged an error."""
     self._steps_since_check = 0
+    if self._tree_sampled:
+      spent = self._engine.sampler_exhausted()
+      if spent:      # (the reference: ValueError after _MAX_TRIES rejections, factor_distributions.py)
+        raise EnvironmentError_('%d sprites of the last pool kept a draw their distribution rejects: max_tries = %d rejections '
+                                'were used up (TreeSampler(max_tries=...))' % (spent, self._sampler.max_tries))
     err = int(self._engine.error.max().item())
     if err:
       self._engine.error.zero_()          # the flags are sticky on the device (include/swb.h): consumed here

@@ -2,7 +2,8 @@
 
 Small mirrors of the reference's distribution algebra (reference:
 spriteworld/factor_distributions.py:81-120 Continuous, :123-158 Discrete,
-:161-209 Mixture, :212-265 Intersection, :268-310 Product, :313-358 SetMinus):
+:161-209 Mixture, :212-265 Intersection, :268-310 Product, :313-358 SetMinus,
+:361-401 Selection):
 `sample(rng=None)` returns {factor: value}, `contains(spec)` tests membership,
 `keys` is the set of factor names.  They run on the host when an episode pool is
 drawn; tasks use `contains` for the per-sprite filter / cluster labels that
@@ -123,3 +124,23 @@ class SetMinus(object):
 
   def contains(self, spec):
     return self.hold_in.contains(spec) and not self.hold_out.contains(spec)
+
+
+class Selection(object):
+  """Samples of `base` that `filtering` contains (rejection sampling): SetMinus with the test inverted."""
+
+  def __init__(self, base, filtering):
+    if not filtering.keys <= base.keys:
+      raise ValueError('keys of filtering must be a subset of those of base')
+    self.base, self.filtering = base, filtering
+    self.keys = set(base.keys)
+
+  def sample(self, rng=None):
+    for _ in range(_MAX_TRIES):
+      s = self.base.sample(rng=rng)
+      if self.filtering.contains(s):
+        return s
+    raise ValueError('max_tries exceeded when sampling from a Selection')
+
+  def contains(self, spec):
+    return self.base.contains(spec) and self.filtering.contains(spec)
