@@ -81,8 +81,18 @@ enum swb_env_error {
   SWB_ENV_ERR_DB_ZERO = 1,       /* Davies-Bouldin score exactly 0.0, by sklearn's early-outs or its regular path => reference raises
                                     ZeroDivisionError (tasks.py:215); reward NaN, success 0 */
   SWB_ENV_ERR_DB_LABELS = 2,     /* sklearn check_number_of_labels => reference raises ValueError            */
-  SWB_ENV_ERR_SPAN_OVERFLOW = 4  /* internal raster span list overflow (never expected)                      */
+  SWB_ENV_ERR_SPAN_OVERFLOW = 4  /* internal raster span list overflow (never expected); ALSO: a sprite of the frame has a vertex whose
+                                    canvas coordinate (int)(canvas size * vertex, pil_renderer.py:81-83) lies outside
+                                    +-SWB_TUNED_COORD_LIMIT (tuned paths) / +-SWB_LF_COORD_LIMIT (large-frame and many-sprite paths,
+                                    swb_variant_info::large_frames), or is not finite (a NaN / inf position: a diverged policy,
+                                    keep_in_frame = 0).  The test is made on the double, before the conversion.  The state, rewards
+                                    and step types of the step are the reference's; the FRAME of a flagged environment is
+                                    unspecified (its bytes stay inside the environment's own frame) */
 };
+/* The canvas coordinates a render path takes.  Tuned paths: the cover kernel's edge records hold int16.  Large frames / many
+ * sprites: int32 vertices whose differences must fit an int and be exact in float32. */
+#define SWB_TUNED_COORD_LIMIT 32000.0
+#define SWB_LF_COORD_LIMIT 16777216.0
 
 /* One (sub-)task.  Field names follow the reference attributes they lower
  * (tasks.py:118-124 FindGoalPosition, tasks.py:189-194 Clustering). */
@@ -412,7 +422,9 @@ int swb_reset_all(swb_handle h, void* stream);
  * SelectMove/DragAndDrop, or i32[N,2] for Embodied. */
 int swb_step(swb_handle h, const void* actions_dev, const swb_outputs* out, void* stream);
 
-/* observation() only (no state change): obs_dev u8[N,H,W,3]. */
+/* observation() only (no state change): obs_dev u8[N,H,W,3].  Reports no swb_env_error flags: a sprite beyond the render path's
+ * coordinate limit (SWB_ENV_ERR_SPAN_OVERFLOW) leaves its environment's frame unspecified without a sign; the next swb_step
+ * that renders raises the flag. */
 int swb_render(swb_handle h, uint8_t* obs_dev, void* stream);
 
 /* Environment.success() (/root/reference/spriteworld/environment.py:80-81: `task.success(self._sprites)` of the sprites AS

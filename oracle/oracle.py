@@ -49,6 +49,8 @@ def lib():
     _lib.swo_create.argtypes = [C.c_void_p, C.c_void_p]
     _lib.swo_destroy.argtypes = [C.c_void_p]
     _lib.swo_reset_all.argtypes = [C.c_void_p]
+    _lib.swo_set_coord_limit.argtypes = [C.c_void_p, C.c_double]
+    _lib.swo_set_coord_limit.restype = None
     _lib.swo_step_range.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
     _lib.swo_render_range.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib.swo_evaluate_range.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -165,6 +167,12 @@ class Engine(object):
 
   def reset_all(self):
     lib().swo_reset_all(self._h)
+
+  def set_coord_limit(self, limit):
+    """The canvas coordinate limit of the render path the engine under test takes (include/swb.h: SWB_TUNED_COORD_LIMIT, the
+    default, or SWB_LF_COORD_LIMIT): a step that renders a sprite with a vertex beyond it, or at a non-finite position, reports
+    SWB_ENV_ERR_SPAN_OVERFLOW in `error` and leaves the sprite out of the frame."""
+    lib().swo_set_coord_limit(self._h, float(limit))
 
   def step(self, actions, render=True, env_range=None):
     cfg = self.cfg

@@ -398,9 +398,13 @@ int swo_resample(const uint8_t* src, int Wc, int Hc, uint8_t* dst, int W, int H)
  * cfg->image_w = image_size[1]; for the (square) shipped configs the
  * distinction vanishes.  We follow the reference's actual behaviour:
  * PIL width Wp = AA*image_h, PIL height Hp = AA*image_w. */
-static void render_env(const swb_config* cfg, int n, const double* x, const double* y,
-                       const int32_t* shape, const double* scale, const double* ca,
-                       const double* sa, const uint8_t* rgb, uint8_t* obs, const double* paths) {
+/* Returns 0, or SWB_ENV_ERR_SPAN_OVERFLOW when a vertex's canvas coordinate is not finite or truncates to an integer outside
+ * +-coord_limit (include/swb.h: the limit of the render path the engine under test takes; the caller says which).  The test is
+ * made on the double -- converting a NaN or a double outside int is undefined in C -- and a sprite that fails it is not drawn:
+ * the frame of a flagged environment is unspecified. */
+static int render_env(const swb_config* cfg, int n, const double* x, const double* y,
+                      const int32_t* shape, const double* scale, const double* ca,
+                      const double* sa, const uint8_t* rgb, uint8_t* obs, const double* paths, double coord_limit) {
   const int AA = cfg->anti_aliasing;
   const int Wo = cfg->image_h, Ho = cfg->image_w;     /* PIL (width, height) of the output */
   const int Wc = AA * Wo, Hc = AA * Ho;
@@ -410,8 +414,9 @@ static void render_env(const swb_config* cfg, int n, const double* x, const doub
   }
   double cx[SWB_MAX_SHAPE_VERTS], cy[SWB_MAX_SHAPE_VERTS];
   int ixy[2 * SWB_MAX_SHAPE_VERTS];
+  int err = 0;
   for (int s = 0; s < n; ++s) {                         /* back to front :80-83 */
-    int nv;
+    int nv, fits = 1;
     if (paths) {                                        /* centred paths as the attribute setters left them (sprite.py:152-175) */
       nv = g_off[shape[s] + 1] - g_off[shape[s]];
       for (int i = 0; i < nv; ++i) {
@@ -424,9 +429,12 @@ static void render_env(const swb_config* cfg, int n, const double* x, const doub
     for (int i = 0; i < nv; ++i) {
       const double vx = 1.0 * cx[i] + 0.0 * cy[i] + x[s]; /* sprite.py:131-133 */
       const double vy = 0.0 * cx[i] + 1.0 * cy[i] + y[s];
-      ixy[2 * i] = (int)((double)Wc * vx);              /* canvas_size * vertices; C truncation in _imaging */
-      ixy[2 * i + 1] = (int)((double)Hc * vy);
+      const double fx = (double)Wc * vx, fy = (double)Hc * vy;
+      if (!(fabs(fx) < coord_limit + 1.0 && fabs(fy) < coord_limit + 1.0)) { fits = 0; break; }   /* |trunc(v)| <= limit; NaN fails */
+      ixy[2 * i] = (int)fx;                             /* canvas_size * vertices; C truncation in _imaging */
+      ixy[2 * i + 1] = (int)fy;
     }
+    if (!fits) { err = SWB_ENV_ERR_SPAN_OVERFLOW; continue; }
     draw_polygon(canvas, Wc, Hc, nv, ixy, rgb + 4 * s);
   }
   uint8_t* img = canvas;
@@ -438,6 +446,7 @@ static void render_env(const swb_config* cfg, int n, const double* x, const doub
   }
   for (int r = 0; r < Ho; ++r)                          /* np.flipud :90 */
     memcpy(obs + (size_t)r * Wo * 3, img + (size_t)(Ho - 1 - r) * Wo * 3, (size_t)Wo * 3);
+  return err;
 }
 
 /* ------------------------------------------------------------------------- */
@@ -737,6 +746,7 @@ typedef struct {
   double *ov_scale, *ov_angle, *ov_cpath;   /* [N][S], [N][S], [N][S][SWB_MAX_SHAPE_VERTS][2] */
   int8_t* ov_label;   /* [N][T][S] */
   int8_t* ov_cell_label;   /* [N][T][S][SWB_MAX_CELLS] (allocated by the first swo_set_sprite_cell_labels) */
+  double coord_limit;      /* SWB_TUNED_COORD_LIMIT, or what swo_set_coord_limit said */
 } swo_engine;
 
 /* The centred path of sprite s of environment i: as the setters left it, else fresh from the pool. */
@@ -760,6 +770,7 @@ static void* dup_mem(const void* p, size_t bytes) {
 swo_engine* swo_create(const swb_config* cfg, const swb_pool* pool) {
   swo_engine* e = (swo_engine*)calloc(1, sizeof(swo_engine));
   e->cfg = *cfg;
+  e->coord_limit = SWB_TUNED_COORD_LIMIT;
   const int N = cfg->n_envs, S = cfg->max_sprites, P = pool->n_entries, T = cfg->n_tasks;
   e->P = P;
   e->p_n = dup_mem(pool->n_sprites, sizeof(int32_t) * P);
@@ -802,6 +813,10 @@ void swo_destroy(swo_engine* e) {
   free(e->p_angle); free(e->ov_flag); free(e->ov_shape); free(e->ov_scale); free(e->ov_angle); free(e->ov_cpath); free(e->ov_label);
   free(e);
 }
+
+/* The canvas coordinate limit of the render path the engine under test takes (SWB_TUNED_COORD_LIMIT, the default, or
+ * SWB_LF_COORD_LIMIT): a step that renders a sprite beyond it reports SWB_ENV_ERR_SPAN_OVERFLOW. */
+void swo_set_coord_limit(swo_engine* e, double limit) { e->coord_limit = limit; }
 
 void swo_reset_all(swo_engine* e) { memset(e->reset_next, 1, e->cfg.n_envs); }
 
@@ -846,15 +861,15 @@ static void observe(swo_engine* e, int i, uint8_t* obs, uint8_t* succ_out, uint8
     }
     label = eff;
   }
-  const int err = eval_task(c, n, e->x + i * S, e->y + i * S, label, &r, &ok);
+  int err = eval_task(c, n, e->x + i * S, e->y + i * S, label, &r, &ok);
   if (task_reward) *task_reward = r;
   if (succ_out) *succ_out = (uint8_t)ok;
-  if (err_out) *err_out = (uint8_t)err;
   if (obs)
-    render_env(c, n, e->x + i * S, e->y + i * S, ov ? e->ov_shape + i * S : e->p_shape + en * S, e->p_scale + en * S,
+    err |= render_env(c, n, e->x + i * S, e->y + i * S, ov ? e->ov_shape + i * S : e->p_shape + en * S, e->p_scale + en * S,
                e->p_ca + en * S, e->p_sa + en * S, e->p_rgb + (size_t)en * S * 4,
                obs + (size_t)i * c->image_h * c->image_w * 3,
-               ov ? e->ov_cpath + (size_t)i * S * SWB_MAX_SHAPE_VERTS * 2 : NULL);
+               ov ? e->ov_cpath + (size_t)i * S * SWB_MAX_SHAPE_VERTS * 2 : NULL, e->coord_limit);
+  if (err_out) *err_out = (uint8_t)err;
 }
 
 /* environment.py:88-108 Environment.step for env range [i0, i1).
@@ -1125,6 +1140,6 @@ int swo_get_sprite(swo_engine* e, int env, int sprite, int32_t* shape, double* a
 int swo_render_sprites(const swb_config* cfg, int n, const double* x, const double* y,
                        const int32_t* shape, const double* scale, const double* ca, const double* sa,
                        const uint8_t* rgb, uint8_t* obs) {
-  render_env(cfg, n, x, y, shape, scale, ca, sa, rgb, obs, NULL);
+  render_env(cfg, n, x, y, shape, scale, ca, sa, rgb, obs, NULL, SWB_LF_COORD_LIMIT);
   return 0;
 }

@@ -983,8 +983,13 @@ __device__ __forceinline__ void build_all_edges(const swb_params& p, wave_lds<NW
       // sprite.py:131-133 translate: (1*x + 0*y) + px
       const double vx = __dadd_rn(__dadd_rn(__dmul_rn(1.0, cx), __dmul_rn(0.0, cy)), sx);
       const double vy = __dadd_rn(__dadd_rn(__dmul_rn(0.0, cx), __dmul_rn(1.0, cy)), sy);
-      const int X = (int)__dmul_rn((double)p.Wc, vx), Y = (int)__dmul_rn((double)p.Hc, vy);
-      if (max(abs(X), abs(Y)) > 32000) err |= SWB_ENV_ERR_SPAN_OVERFLOW;
+      // The range is decided on the doubles: converting one that is NaN or outside int is undefined (x86 gives INT_MIN, gfx950
+      // saturates and turns NaN into 0), and |trunc(v)| <= 32000 is |v| < 32001.  NaN fails the comparison; a vertex that
+      // fails is flagged and stored as 0, so that every later phase sees coordinates that fit the records.
+      const double fx = __dmul_rn((double)p.Wc, vx), fy = __dmul_rn((double)p.Hc, vy);
+      const bool fits = fabs(fx) < SWB_TUNED_COORD_LIMIT + 1.0 && fabs(fy) < SWB_TUNED_COORD_LIMIT + 1.0;
+      if (!fits) err |= SWB_ENV_ERR_SPAN_OVERFLOW;
+      const int X = fits ? (int)fx : 0, Y = fits ? (int)fy : 0;
       edge_rec e;
       e.x0 = (int16_t)X; e.y0 = (int16_t)Y; e.y1 = 0; e.xtop = SWB_NO_REPL; e.dx = 0.0f; e.xbot = SWB_NO_REPL;
       e.pad = (int16_t)(sid | ((k - vb) << 8));
@@ -2741,6 +2746,7 @@ swb_lf_raster_kernel(const swb_params p, const swb_lf_args a) {
   __syncthreads();
   const int ns = B->n, vtotal = B->vtotal;
   // vertices -> canvas ints: sprite.py:131-133 translate, then (int)(canvas size * v) (C truncation)
+  bool all_fit = true;
   for (int k = t; k < vtotal; k += blockDim.x) {
     int sid = 0;
     for (int s = 1; s < ns; ++s) if (k >= B->voff[s]) sid = s;
@@ -2754,8 +2760,14 @@ swb_lf_raster_kernel(const swb_params p, const swb_lf_args a) {
     }
     const double vx = __dadd_rn(__dadd_rn(__dmul_rn(1.0, cx), __dmul_rn(0.0, cy)), B->px[sid]);
     const double vy = __dadd_rn(__dadd_rn(__dmul_rn(0.0, cx), __dmul_rn(1.0, cy)), B->py[sid]);
-    verts[k] = swb_lf_xy{(int)__dmul_rn((double)Wc, vx), (int)__dmul_rn((double)Hc, vy)};
+    // (decided on the doubles, as in the cover kernel's P1b: within +-2^24 the difference of two coordinates fits an int and
+    // is exact as a float; a vertex beyond that, or not finite, is flagged and stored as 0)
+    const double fx = __dmul_rn((double)Wc, vx), fy = __dmul_rn((double)Hc, vy);
+    const bool fits = fabs(fx) < SWB_LF_COORD_LIMIT + 1.0 && fabs(fy) < SWB_LF_COORD_LIMIT + 1.0;
+    all_fit = all_fit && fits;
+    verts[k] = swb_lf_xy{fits ? (int)fx : 0, fits ? (int)fy : 0};
   }
+  if (!all_fit) B->err = SWB_ENV_ERR_SPAN_OVERFLOW;      // (every writer stores the same value)
   __syncthreads();
   // Draw.c add_edge: edge i joins vertex i and i + 1; the closing edge only if the last vertex differs from the first
   for (int k = t; k < vtotal; k += blockDim.x) {

@@ -11,11 +11,13 @@ def bits(a):
   return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what='', errors=None):
+def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what='', errors=None, nan_positions=False, frame_envs=None):
   """One step's outputs (`want`: the oracle's, `got`: the engine's, on the host) and the state after it; returns the
   engine's state.  reward_ulp: a bound in units of the last place in place of bit-equal rewards; `what`: the caller's case, put
   in front of the step in every message; `errors`: the error buffer expected in place of an empty one (the engine's flags are sticky:
-  the OR of the oracle's per-step flags so far)."""
+  the OR of the oracle's per-step flags so far).  nan_positions: a position the oracle holds as NaN must be NaN in the engine
+  (sign and payload differ between x86 and the GPU) -- every other position stays bit-equal; off, NaN positions are compared bit
+  for bit like the rest.  frame_envs: bool[N], the environments whose frames are compared (None: all)."""
   at = '%st=%d' % (what and what + ', ', t)
   st_o, st_g = ora.state(), eng.state()
   if errors is None:
@@ -23,8 +25,13 @@ def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what='', errors=N
   else:
     np.testing.assert_array_equal(got['error'], errors, err_msg='error flags ' + at)
   np.testing.assert_array_equal(got['step_type'], want['step_type'], err_msg='step_type ' + at)
-  np.testing.assert_array_equal(bits(st_g['x']), bits(st_o['x']), err_msg='x ' + at)
-  np.testing.assert_array_equal(bits(st_g['y']), bits(st_o['y']), err_msg='y ' + at)
+  for k in ('x', 'y'):
+    pg, po = st_g[k], st_o[k]
+    if nan_positions:
+      nan = np.isnan(po)
+      np.testing.assert_array_equal(np.isnan(pg), nan, err_msg=k + ' NaN pattern ' + at)
+      pg, po = np.where(nan, 0.0, pg), np.where(nan, 0.0, po)
+    np.testing.assert_array_equal(bits(pg), bits(po), err_msg=k + ' ' + at)
   for k in ('step_count', 'reset_next', 'episode', 'pool_entry', 'n_sprites'):
     np.testing.assert_array_equal(st_g[k], st_o[k], err_msg=k + ' ' + at)
   np.testing.assert_array_equal(got['success'], want['success'], err_msg='success ' + at)
@@ -32,6 +39,8 @@ def compare(t, ora, eng, want, got, frames=True, reward_ulp=0, what='', errors=N
   assert_rewards_equal(got['reward'], want['reward'], at, reward_ulp)
   if frames:
     diff = np.abs(got['obs'].astype(np.int16) - want['obs'].astype(np.int16))
+    if frame_envs is not None:      # (the frames left out compare as equal)
+      diff[~np.asarray(frame_envs, dtype=bool)] = 0
     assert diff.max() == 0, ('frame diff', int(diff.max()), int((diff > 0).sum()), at, np.argwhere(diff > 0)[:5].tolist())
   return st_g
 

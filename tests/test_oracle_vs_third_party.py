@@ -38,6 +38,50 @@ def test_polygon_fill_equals_pillow_on_sprite_polygons():
     assert np.array_equal(np.array(im), mine)
 
 
+def _far_sprite_polygon(rng, W, H):
+  """A sprite polygon that is huge (scales log-uniform up to 15000 / max(W, H)) and / or far off the canvas (40 % of the positions in
+  [-0.5, 1.5], the others uniform within +-15000 / max(W, H)); None when a vertex leaves +-32000 pixels, the widest range an
+  engine path is asked to draw."""
+  verts, offs = shapes.packed_table()
+  si = rng.integers(12)
+  v = verts[offs[si]:offs[si + 1]]
+  reach = 15000.0 / max(W, H)
+  sc = math.exp(rng.uniform(math.log(0.05), math.log(reach)))
+  th = math.radians(rng.uniform(0, 360) if rng.random() < 0.5 else float(rng.integers(0, 360)))
+  a, b = math.cos(th), math.sin(th)
+  px, py = rng.uniform(-0.5, 1.5, 2) if rng.random() < 0.4 else rng.uniform(-reach, reach, 2)
+  P = np.stack([a * sc * v[:, 0] - b * sc * v[:, 1] + px, b * sc * v[:, 0] + a * sc * v[:, 1] + py], 1) * np.array([W, H])
+  return P if np.abs(np.trunc(P)).max() <= 32000 else None
+
+
+def test_polygon_fill_equals_pillow_on_far_and_huge_sprite_polygons():
+  """Edges tens of thousands of pixels long, of which the canvas sees a few rows: the float32 slopes and the clipping of the
+  oracle's fill against Pillow's.  The draws must reach the regime: at least one polygon in twenty covers the canvas partly,
+  and one in twenty fully."""
+  rng = np.random.default_rng(5)
+  drawn = partly = fully = 0
+  farthest = 0.0
+  while drawn < 3000:
+    W = int(rng.choice([32, 64, 96, 160, 320, 640]))
+    H = W if rng.random() < 0.7 else int(rng.choice([32, 64, 320]))
+    P = _far_sprite_polygon(rng, W, H)
+    if P is None:
+      continue
+    drawn += 1
+    im = Image.new('RGB', (W, H))
+    ImageDraw.Draw(im).polygon([tuple(q) for q in P], fill=(255, 0, 0))
+    ref = np.array(im)
+    mine = oracle.fill_polygon(W, H, np.trunc(P).astype(np.int32), (255, 0, 0))
+    assert np.array_equal(ref, mine), (W, H, np.trunc(P).tolist())
+    covered = ref[..., 0] != 0
+    partly += int(covered.any() and not covered.all())
+    fully += int(covered.all())
+    if covered.any():
+      farthest = max(farthest, float(np.abs(P).max()))
+  assert 20 * partly >= drawn and 20 * fully >= drawn, (drawn, partly, fully)
+  assert farthest >= 15000, farthest        # (visible polygons reach far beyond anything the in-frame tests draw)
+
+
 def test_polygon_fill_equals_pillow_on_random_integer_polygons():
   # self-intersecting, degenerate, partly off-canvas: exercises duplicates and the corner rule
   rng = np.random.default_rng(1)
