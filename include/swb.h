@@ -621,6 +621,22 @@ int swb_trim_run_lists(swb_handle h, int32_t* run_cap_out, void* stream);
  * large-frame handles have no lists and count nothing. */
 int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream);
 
+/* Frame cache.  A frame is a pure function of the run lists, their header's colour words, the background and the resampling
+ * tables.  A handle whose frames come from the resample kernel (anti_aliasing > 1, not the large-frame or many-sprite path, not
+ * SWB_NO_KEEP_LISTS) owns one frame per environment of device memory (swb_variant_info::frame_cache_bytes: 12 KB per environment
+ * at 64x64, 49 KB at 128x128).  The first launch that keeps an environment's lists leaves its frame there as well; every
+ * further launch that keeps them copies the caller's frame from it instead of resampling the lists again.  The caller's buffer
+ * is written in full at every rendering launch either way and is never read back across launches: it may be another buffer at
+ * every step, and the caller may do with it what it likes.  Whatever makes the lists stale (see above) makes the cache stale.
+ * A handle that cannot get the memory runs without a cache.  Switch of the environment, read at swb_create:
+ *   SWB_NO_FRAME_CACHE  no cache: every wave resamples (tests, A/B runs); results are identical either way
+ * swb_frame_stats: the tasks of the resample kernel -- one per (environment, column group[, band]) and launch -- since
+ * swb_create that copied from the cache / resampled and filled it / only resampled.  Blocking; needs SWB_LIST_STATS like
+ * swb_list_stats.  swb_frame_cycles (measurement): out3 = wave cycles of the copying tasks, of all others, and the list bytes
+ * the others walked. */
+int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream);
+int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream);
+
 /* SpriteFactors observation (renderers/handcrafted.py:29-82): factors_dev f64[N,S,10] in
  * sprite.FACTOR_NAMES order (x, y, shape, angle, scale, c0, c1, c2, x_vel, y_vel), `shape` as its
  * constants.ShapeType value (1-based); rows >= n_sprites[env] are zero. */
@@ -710,6 +726,8 @@ typedef struct swb_variant_info {
                                * the large-frame kernels (large_frames is 1 too); no run lists */
   int32_t reserved_;
   int64_t run_list_bytes;     /* device memory of the hand-off lists: fixed parts + arena (0 until the first launch) */
+  int64_t frame_cache_bytes;  /* device memory of the frame cache (swb_frame_stats): one frame per environment, 0 on a handle
+                               * without one */
 } swb_variant_info;
 int swb_variant(swb_handle h, swb_variant_info* out);
 const char* swb_build_id(void);

@@ -133,6 +133,12 @@ struct swb_engine {
   uint32_t list_epoch = 1;
   bool no_keep_lists = false;
   dev_buf<unsigned long long> d_list_stats;   // SWB_LIST_STATS: cover waves that kept / built their lists (swb_list_stats)
+  // frame cache (swb_params::frame_cache): the engine's own copy of every environment's last frame, from which the resample
+  // waves of an environment whose lists were kept write the caller's frame.  Only on handles whose frames come from
+  // swb_resample_kernel under a live list epoch; SWB_NO_FRAME_CACHE (tests, A/B runs) and a failed allocation leave it out
+  dev_buf<uint8_t> d_frame_cache;
+  int copy_cost = 0;                 // what a task that copies a column group's whole frame is filed under (SWB_COPY_COST)
+  dev_buf<unsigned long long> d_frame_stats;  // SWB_LIST_STATS: what the resample tasks did (swb_frame_stats)
   dev_buf<int32_t> d_band_y0, d_band_first, d_band_lo, d_cg_lo, d_cg_hi;
   dev_buf<uint32_t> d_v_break;
   // live sprite overrides (swb_set_sprite_attr), allocated at the first call
@@ -503,6 +509,10 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   // handle's epoch and keeps those that carry it.  A launch on a state view leaves another state's lists behind: epoch 0, it
   // keeps nothing and stamps them invalid.  A step without a frame moves sprites and lists nothing: the epoch moves on.
   p.list_epoch = (view || !p.obs || paint || !p.rhdr || h->no_keep_lists) ? 0u : h->list_epoch;
+  // (the frame cache's mover takes 16 bytes per lane where the caller's buffer and every row segment of it start on 16)
+  p.obs_aligned16 = (p.obs && (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0 && (p.Wo & 15) == 0) ? 1 : 0;
+  // (a band task copies its band's rows only: measured, 465 units for a whole frame, 67 for one band of eight)
+  p.copy_cost = h->copy_cost / (p.band_tasks ? std::max(p.nbands, 1) : 1);
   if (!p.obs && render_only == 0 && !view) bump_list_epoch(h);
   step_timer timer(h, stream);
   if (int rc = timer.begin()) return rc;
@@ -532,11 +542,19 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   };
   launch_cover(0, p.N);
   HIP_TRY(hipGetLastError());
+  // From here on the cover kernel may have run: its waves have told the resample waves of this launch to fill the frame cache,
+  // or that it is filled (SWB_RHDR_FRAME).  If those never run, the words are wrong -- every error return below moves the epoch,
+  // the next launch builds every list and resets every word.
+  struct epoch_guard {
+    swb_engine* h; bool armed = true;
+    ~epoch_guard() { if (armed) bump_list_epoch(h); }
+  } guard{h};
   if (int rc = timer.mid()) return rc;            // (a painting cover kernel is the whole step: nothing follows before end())
   if (p.obs && !p.paint_in_cover) launch_resample(0, p.N, stream);
   HIP_TRY(hipGetLastError());
   if (!p.obs && p.cost_cnt && render_only != 2)   // no second kernel to clear the next launch's bucket counters (kind 0; the cover kernel keeps kind 1)
     HIP_TRY(hipMemsetAsync(h->d_cost_cnt + (size_t)(p.parity ^ 1) * SWB_COST_SET, 0, SWB_COST_SET * sizeof(uint32_t), stream));
+  guard.armed = false;
   // swb_evaluate files nothing and lists nothing: the dispatch state (parity, phase, what the previous launch filed) stays as
   // the last step left it -- an evaluation between two steps does not cost the next one its cost order (round-5 advice) --, and
   // it is not a timed launch
@@ -1017,8 +1035,24 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
       h->d_step_count.fill(nullptr, p.N) || h->d_episode.fill(nullptr, p.N) || h->d_reset_next.fill(nullptr, p.N))
     return SWB_ERR_HIP;
   if (getenv("SWB_LIST_STATS")) {
-    if (h->d_list_stats.fill(nullptr, 2)) return SWB_ERR_HIP;
+    if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 6)) return SWB_ERR_HIP;
     p.list_stats = h->d_list_stats;
+    p.frame_stats = h->d_frame_stats;
+  }
+  // The frame cache: N frames, for the handles whose frames the resample kernel computes from lists that can be kept -- not the
+  // fill kernel and the painting builds (anti_aliasing = 1), not the large-frame and many-sprite paths, not SWB_NO_KEEP_LISTS.
+  // A handle that cannot have the memory runs without it (every wave resamples, as before): no error, and none left behind.
+  h->copy_cost = SWB_COPY_COST;
+  if (const char* x = getenv("SWB_COPY_COST")) h->copy_cost = std::max(0, atoi(x));      // A/B runs
+  if (p.AA != 1 && !h->large_frames && !h->no_keep_lists && !getenv("SWB_NO_FRAME_CACHE")) {
+    const size_t bytes = (size_t)p.N * p.Wo * p.Ho * 3;
+    if (hipMalloc(reinterpret_cast<void**>(&h->d_frame_cache.ptr), bytes) == hipSuccess) {
+      h->d_frame_cache.count = bytes;
+      p.frame_cache = h->d_frame_cache;
+    } else {
+      h->d_frame_cache.ptr = nullptr;
+      (void)hipGetLastError();
+    }
   }
   p.max_spans = SWB_MIN_SPANS;
   if (const char* ms = getenv("SWB_MAX_SPANS")) p.max_spans = atoi(ms) < SWB_MIN_SPANS ? SWB_MIN_SPANS : atoi(ms);
@@ -1787,6 +1821,28 @@ int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream) {
   return SWB_OK;
 }
 
+int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream) {
+  if (!h || !copied || !filled || !resampled) return fail(SWB_ERR_INVALID, "null argument");
+  if (!h->d_frame_stats) return fail(SWB_ERR_STATE, "swb_frame_stats: SWB_LIST_STATS was not set when the handle was created");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long w[3] = {0ull, 0ull, 0ull};
+  HIP_TRY(hipMemcpy(w, h->d_frame_stats, sizeof(w), hipMemcpyDeviceToHost));
+  *copied = (int64_t)w[0]; *filled = (int64_t)w[1]; *resampled = (int64_t)w[2];
+  return SWB_OK;
+}
+
+int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream) {
+  if (!h || !out3) return fail(SWB_ERR_INVALID, "null argument");
+  if (!h->d_frame_stats) return fail(SWB_ERR_STATE, "swb_frame_cycles: SWB_LIST_STATS was not set when the handle was created");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long w[3] = {0ull, 0ull, 0ull};
+  HIP_TRY(hipMemcpy(w, h->d_frame_stats + 3, sizeof(w), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+  return SWB_OK;
+}
+
 int swb_factors(swb_handle h, double* factors_dev, void* stream) {
   if (!h || !factors_dev) return fail(SWB_ERR_INVALID, "null argument");
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
@@ -2101,6 +2157,7 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
       out->waves_per_simd = 0;
     }
     out->run_list_bytes = 0;
+    out->frame_cache_bytes = 0;
     return SWB_OK;
   }
   const variant* v = pick_variant(h->p.Wc);
@@ -2120,6 +2177,7 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
   out->many_sprites = 0;
   out->reserved_ = 0;
   out->run_list_bytes = h->d_runs ? ((int64_t)h->p.arena_base + h->p.arena_units + 4) * 8 : 0;
+  out->frame_cache_bytes = (int64_t)h->d_frame_cache.count;
   return SWB_OK;
 }
 

@@ -207,6 +207,16 @@ struct swb_params {
   uint32_t list_epoch;         // 0: keep nothing and stamp the lists invalid (launches on a state view, SWB_NO_KEEP_LISTS)
   uint32_t list_pad_;
   unsigned long long* list_stats;   // [2] cover waves that kept / built their lists (SWB_LIST_STATS; else NULL)
+  // ---- frame cache (swb_resample_kernel; DESIGN.md section 24).  A frame is a pure function of the run lists, the header's
+  // colour words, the background and the resampling tables: where a cover wave KEPT its lists, the frame the resample waves
+  // would compute is the one they computed at the previous launch.  The engine keeps its own copy of every environment's last
+  // frame, laid out like `obs`; the header word SWB_RHDR_FRAME says what the resample waves of an environment do with it.
+  // The caller's buffer is written in full at every launch all the same -- from the copy instead of from the lists.
+  uint8_t* frame_cache;        // [N][Ho][Wo][3], NULL: the handle has none (every wave resamples)
+  unsigned long long* frame_stats;  // [6] resample tasks that copied / filled / resampled, then the wave cycles of the copying
+                                    // tasks, of the others, and the list bytes of the others (SWB_LIST_STATS; else NULL)
+  int32_t obs_aligned16;       // `obs` and every row segment of a column group start on 16 bytes: the copy moves 16 bytes per lane
+  int32_t copy_cost;           // the cost a task that copies is filed under (SWB_COPY_COST, over the bands of a band task)
 };
 
 // --------------------------------------------------------------------------------------------
@@ -1702,6 +1712,17 @@ __device__ __forceinline__ int dealt_block(const swb_params& p, int j, int block
 #define SWB_RHDR_COST (SWB_RHDR_GROUPS + SWB_MAX_CG * SWB_RHDR_GSTRIDE)
 #define SWB_RHDR_STAMP (SWB_RHDR_COST + SWB_MAX_CG)
 #define SWB_RHDR_CYCLES (SWB_RHDR_STAMP + 1)
+// ... and the state of the environment's frame in the engine's cache (swb_params::frame_cache), written by the cover wave alone:
+// 0 the cache does not hold it (the wave BUILT its lists, or the handle has no cache), 1 the resample waves of this launch
+// leave it there (the first launch that kept the lists), 2 it is there: they copy it.  A wave that keeps writes min(old + 1, 2).
+#define SWB_RHDR_FRAME (SWB_RHDR_CYCLES + 1)
+// What a task that copies a column group's whole frame is filed under for the order of the resample launch (a band task: that
+// over the number of bands, swb.hip).  Measured on the headline workload with the wave clocks of swb_frame_cycles
+// (profiles/r18_frame_cache.md section 4): a copying wave lives 307 743 cycles beside its seven neighbours, a resampling wave
+// 441 692 for a list of 1 336 bytes = 668 units of cost, that is 661 cycles per unit: 307 743 / 661 = 465.  (1 024 environments
+// in 8 bands, every band a task: 194 248 cycles against 2 908 per unit = 67, an eighth of it.)  Swept from 64 to 1 500: the
+// kernel is flat from 64 to 700 and 7 % longer from 1 000 on, where copies stand in front of the tasks that resample.
+#define SWB_COPY_COST 460
 #define SWB_RHDR_DWORDS (SWB_RHDR_STAMP + 4)
 #define SWB_BST_STRIDE (SWB_MAX_BANDS + 1)   // band starts of a list + its end, in LDS (swb_params::band_tasks: see emit_runs)
 __device__ __forceinline__ int run_units(int spans) { return spans <= 1 ? 1 : 2 + (spans > 3 ? (spans - 2) >> 1 : 0); }
@@ -2029,11 +2050,12 @@ swb_cover_kernel(const swb_params p) {
   uint32_t err = 0;
   const double shdmin_tab_l = (l < SWB_MAX_SHAPES) ? p.shape_dmin[l] : 0.0;
   // (... and what keeping the lists takes, swb_params::list_epoch: lane g < SWB_MAX_CG the cost the list of column group g was
-  // filed under, lane SWB_MAX_CG the header's stamp, the lane behind it the cycles of the wave that built the lists.  It depends on nothing but `env`; a plain load, not as_const: this wave
+  // filed under, lane SWB_MAX_CG the header's stamp, the lane behind it the cycles of the wave that built the lists, the next
+  // one the state of the frame cache (SWB_RHDR_FRAME).  It depends on nothing but `env`; a plain load, not as_const: this wave
   // writes the words again at its end.)
   // The words wait in LDS (wave_lds::outrow is idle until P1b), not in a register across the state phase.
   if constexpr (!PAINT) {
-    if (p.list_epoch != 0u && l <= SWB_MAX_CG + 1) L->outrow[l] = p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_COST + l];
+    if (p.list_epoch != 0u && l <= SWB_MAX_CG + 2) L->outrow[l] = p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_COST + l];
   }
   env_state es = load_env_state<OV>(p, env, tscratch);
   const int n = es.n, nv_l = es.nv_l;
@@ -2107,8 +2129,8 @@ swb_cover_kernel(const swb_params p) {
   // their copy in LDS (`bst`; reading the header back takes an agent-scope fence, which writes the XCD's L2 back: measured, the
   // cover kernel of 4096 environments 0.052 -> 0.133 ms).
   // cost_l: lane g, the cost of the list of column group g; built_cycles: 0, or (kept lists) the cycles of the wave that built
-  // them, in place of this wave's own.  Then the overflow slot goes back and the error flags out.
-  [[maybe_unused]] auto file_lists = [&](int cost_l, const uint32_t* bst, uint32_t built_cycles) __attribute__((always_inline)) {
+  // them, in place of this wave's own; copies: the second kernel copies this environment's frame (swb_params::frame_cache).  Then the overflow slot goes back and the error flags out.
+  [[maybe_unused]] auto file_lists = [&](int cost_l, const uint32_t* bst, uint32_t built_cycles, bool copies) __attribute__((always_inline)) {
     const bool bt = bst != nullptr;
     const int ntask = bt ? p.ncg * p.nbands : p.ncg;
     const bool file0 = p.cost_cnt != nullptr && l < ntask, file1 = p.ccost_list != nullptr && l == 0;
@@ -2122,6 +2144,9 @@ swb_cover_kernel(const swb_params p) {
       task_cost = 4 * max((u1 - u0) + (p.AA == 1 ? 0 : (((u2 - u1) * 5) >> 4)), 0);
       task_bits = (g2 << 24) | (b2 << 26);
     }
+    // (the tasks of an environment whose frame is copied from the cache, SWB_RHDR_FRAME = 2: a twentieth of a resampling task's
+    // work whatever the list -- filed under the stored cost they would stand between the tasks that resample)
+    if (copies) task_cost = p.copy_cost;
     const int key0 = cost_key(task_cost, (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 0), (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 1));
     int key1 = 0;
     uint32_t cycles = built_cycles;
@@ -2132,8 +2157,13 @@ swb_cover_kernel(const swb_params p) {
       if (l == 0 && (cycles >> width) >= (uint32_t)SWB_COST_BUCKETS) atomicMax(&p.cost_cnt[SWB_COST_WORD_COVER_MAX(ph, sh)], cycles);
     }
     uint32_t pos0 = 0u, pos1 = 0u;
-    if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);
+    // (copying tasks all carry one cost, so all of a wave's tasks -- and most of the launch's -- meet in one bucket: lane 0 takes
+    // the wave's ntask places with one atomic.  Measured without this, 1024 environments in 8 band tasks each: the cover kernel
+    // +15 %, eight returning atomics per wave queueing on one word per shard.)
+    if (copies) { if (file0 && l == 0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], (uint32_t)ntask); }
+    else if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);
     if (file1) pos1 = atomicAdd(&p.cost_cnt[cost_row1(ph, sh) + key1], 1u);
+    if (copies) pos0 = (uint32_t)__builtin_amdgcn_readlane((int)pos0, 0) + (uint32_t)l;
     if (file0) p.cost_list[((size_t)(p.parity * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key0) * p.cost_cap + pos0] = env | task_bits;
     if (file1) p.ccost_list[((size_t)(ph * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key1) * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) + pos1] = env;
     if (l == 0) ovf_slot_release(p, ovf);
@@ -2156,7 +2186,7 @@ swb_cover_kernel(const swb_params p) {
     bool keep = false;
     uint32_t keep_words_l = 0u;
     if (p.list_epoch != 0u) {
-      if (l <= SWB_MAX_CG + 1) keep_words_l = L->outrow[l];
+      if (l <= SWB_MAX_CG + 2) keep_words_l = L->outrow[l];
       keep = (uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG) == p.list_epoch && __ballot(es.first) == 0ull && !sc.changed;
     }
     if (p.list_stats != nullptr && l == 0) atomicAdd(&p.list_stats[keep ? 0 : 1], 1ull);
@@ -2168,7 +2198,12 @@ swb_cover_kernel(const swb_params p) {
         const int g = l / SWB_BST_STRIDE, b = l - g * SWB_BST_STRIDE;
         if (g < p.ncg && b <= p.nbands) bst[l] = hg[g * SWB_RHDR_GSTRIDE + (b < p.nbands ? 1 + b : 0)];
       }
-      file_lists((int)keep_words_l, bst, max((uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 1), 1u));
+      // the frame (SWB_RHDR_FRAME): kept once, the resample waves of this launch fill the cache; kept again, they copy from it
+      // (written only where it changes: a wave that keeps on through a still period writes nothing at all, as before)
+      const uint32_t frame_word_was = (uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 2);
+      const uint32_t frame_word = p.frame_cache ? min(frame_word_was + 1u, 2u) : 0u;
+      if (l == 0 && frame_word != frame_word_was) p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_FRAME] = frame_word;
+      file_lists((int)keep_words_l, bst, max((uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 1), 1u), frame_word == 2u);
       return;
     }
   }
@@ -2322,8 +2357,9 @@ swb_cover_kernel(const swb_params p) {
     const bool flawed_l = (err & ~SWB_INT_NEED_SLOT) != 0u || (l < p.ncg && ((uint32_t)band_l >> 4) != 0u);
     const bool stamped = p.list_epoch != 0u && __ballot(flawed_l) == 0ull;
     if (l <= SWB_MAX_CG) hdr[SWB_RHDR_COST + l] = l < SWB_MAX_CG ? (uint32_t)cost_l : (stamped ? p.list_epoch : 0u);
+    if (l == SWB_MAX_CG + 2) hdr[SWB_RHDR_FRAME] = 0u;       // (new lists: the cache does not hold their frame)
   }
-  const uint32_t own_cycles = file_lists(cost_l, bst, 0u);
+  const uint32_t own_cycles = file_lists(cost_l, bst, 0u, false);
   if (l == 0 && p.list_epoch != 0u) hdr[SWB_RHDR_CYCLES] = own_cycles;
   }   // !PAINT
 }
@@ -2353,6 +2389,36 @@ swb_cover_kernel(const swb_params p) {
 // continuation run -- the rows below a forced run end that have the spans of the run before it -- is one unit: the loop skips
 // from the two table loads straight to the vertical pass with the h[0..2] it holds (clipped, live across iterations); the
 // list position moves by one unit, so the "untouched slot" test above works as before.
+// The frame cache's mover (swb_params::frame_cache): `rows` row segments of `seg_bytes` bytes, `row_bytes` apart, from src to dst
+// at the same offsets -- a wave's rectangle of the frame, which lies alike in the caller's buffer and in the cache.  Lanes take
+// consecutive chunks of T (16 bytes where both sides are aligned, else a dword: the same bytes either way), BATCH of
+// them loaded before the first is stored -- a copying wave does nothing else, so the loads in flight are its whole latency hiding.
+template <typename T, int BATCH>
+__device__ __forceinline__ void copy_frame_rect_as(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows) {
+  const int l = lane_id();
+  const int cpr = (int)(seg_bytes / (uint32_t)sizeof(T)), total = rows * cpr;      // chunks per row segment (uniform), in all
+  const int step_rows = 64 / cpr, step_cols = 64 - step_rows * cpr;               // what 64 chunks further means
+  int row = l / cpr, col = l - row * cpr;
+  for (int base = 0; base < total; base += 64 * BATCH) {
+    T v[BATCH];
+    uint32_t off[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      off[j] = (uint32_t)row * row_bytes + (uint32_t)col * (uint32_t)sizeof(T);
+      if (base + 64 * j + l < total) v[j] = *reinterpret_cast<const T*>(src + off[j]);
+      row += step_rows; col += step_cols;
+      if (col >= cpr) { col -= cpr; ++row; }
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j)
+      if (base + 64 * j + l < total) *reinterpret_cast<T*>(dst + off[j]) = v[j];
+  }
+}
+typedef uint32_t swb_c16 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void copy_frame_rect(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows, bool aligned16) {
+  if (aligned16) copy_frame_rect_as<swb_c16, 6>(src, dst, row_bytes, seg_bytes, rows);
+  else copy_frame_rect_as<uint32_t, 8>(src, dst, row_bytes, seg_bytes, rows);
+}
 typedef uint32_t swb_u4 __attribute__((ext_vector_type(4), aligned(8)));      // a run record starts on an 8-byte unit
 typedef int32_t swb_i8 __attribute__((ext_vector_type(8), aligned(32)));
 template <int VS>
@@ -2382,6 +2448,19 @@ swb_resample_kernel(const swb_params p) {
   const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];
   if (o_lo >= o_hi) return;
   cptr<uint32_t> hdr = as_const(p.rhdr) + (size_t)env * SWB_RHDR_DWORDS;
+  // The frame cache (swb_params::frame_cache), decided once and wave-uniform from the word the cover wave left (SWB_RHDR_FRAME):
+  // 0 resample, as ever; 1 resample, then leave the wave's rectangle -- output rows [o_lo, o_hi) of column group g -- in the
+  // cache; 2 copy the rectangle from the cache to the frame and return: no list, no prefix table, no lane constants.
+  const uint32_t frame_mode = p.frame_cache ? hdr[SWB_RHDR_FRAME] : 0u;
+  const uint32_t rect_row_bytes = 3u * (uint32_t)p.Wo, rect_seg_bytes = 3u * (uint32_t)min(64, p.Wo - 64 * g);
+  const size_t frame_off = (size_t)env * p.Wo * p.Ho * 3 + (size_t)(p.Ho - o_hi) * rect_row_bytes + 192u * (uint32_t)g;
+  const uint32_t cycles0 = p.frame_stats ? (uint32_t)__builtin_amdgcn_s_memtime() : 0u;
+  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[frame_mode == 2u ? 0 : (frame_mode == 1u ? 1 : 2)], 1ull);
+  if (frame_mode == 2u) {
+    copy_frame_rect(p.frame_cache + frame_off, p.obs + frame_off, rect_row_bytes, rect_seg_bytes, o_hi - o_lo, p.obs_aligned16 != 0);
+    if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[3], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));
+    return;
+  }
   const uint32_t dpk_reg = (l < SWB_TUNED_SPRITES) ? p.rhdr[(size_t)env * SWB_RHDR_DWORDS + l] : 0u;   // lane s: sprite s
   uint32_t uo = 8u * hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + 1 + band];                           // byte offset of the next run
   // Wave priority by the list left to walk.  A SIMD issues from its oldest wave first, so the waves of a launch finish one after
@@ -2391,6 +2470,7 @@ swb_resample_kernel(const swb_params p) {
   const uint32_t u_end = 8u * hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + (band + 1 < p.nbands ? 2 + band : 0)];
   const uint32_t prio_shift = p.cost_cnt ? as_const(p.cost_cnt)[SWB_COST_WORD_PRIO_SHIFT(p.parity)] : 0u;
   int prio = prio_shift ? (int)min((u_end - uo) >> prio_shift, 3u) : 0;
+  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[5], (unsigned long long)(u_end - uo));
   if (prio == 3) __builtin_amdgcn_s_setprio(3);
   else if (prio == 2) __builtin_amdgcn_s_setprio(2);
   else if (prio == 1) __builtin_amdgcn_s_setprio(1);
@@ -2523,6 +2603,16 @@ swb_resample_kernel(const swb_params p) {
       if (r_first >= o_hi) { more = false; break; }
     }
   }
+  // Fill (SWB_RHDR_FRAME = 1): the rectangle this wave has just written goes into the cache as well.  A tail, not a second store in
+  // the finished-row block: the loop above is the parent's, instruction for instruction, for the waves that only resample.  The
+  // dwords a lane copies were stored by other lanes of this wave: a workgroup-scope release / acquire pair lies between.
+  if (frame_mode == 1u) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    copy_frame_rect(p.obs + frame_off, p.frame_cache + frame_off, rect_row_bytes, rect_seg_bytes, o_hi - o_lo, p.obs_aligned16 != 0);
+  }
+  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[4], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));
 }
 
 #ifndef SWB_WIDE_TU

@@ -365,6 +365,20 @@ class Engine(object):
     self._check(self.lib.swb_list_stats(self._h, C.byref(kept), C.byref(built), self._stream()))
     return kept.value, built.value
 
+  def frame_stats(self):
+    """(copied, filled, resampled): the tasks of the resample kernel -- one per environment, column group and band task of a
+    rendering launch -- that copied their part of the frame from the engine's frame cache / resampled it and left it in the
+    cache / only resampled it, since the engine was created (swb_frame_stats; blocking).  Needs SWB_LIST_STATS like list_stats."""
+    w = [C.c_int64(0) for _ in range(3)]
+    self._check(self.lib.swb_frame_stats(self._h, C.byref(w[0]), C.byref(w[1]), C.byref(w[2]), self._stream()))
+    return tuple(x.value for x in w)
+
+  def frame_cycles(self):
+    """(cycles of the copying tasks, cycles of all other tasks, list bytes those walked): measurement (swb_frame_cycles)."""
+    w = (C.c_int64 * 3)()
+    self._check(self.lib.swb_frame_cycles(self._h, w, self._stream()))
+    return tuple(w)
+
   def render(self):
     self._check(self.lib.swb_render(self._h, C.c_void_p(self.obs.data_ptr()), self._stream()))
     return self.obs

@@ -7,8 +7,11 @@ def apply(files, arg, replace_once):
   k = 'swb_kernels.hip.inc'
   replace_once(files, k, '    const int key0 = cost_key(task_cost, (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 0), (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 1));\n',
                '    const int key0 = 0;\n')
-  replace_once(files, k, '    if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);\n',
+  # (both forms of the filing atomic: one per task, and one per wave for the tasks that copy from the frame cache)
+  replace_once(files, k, '    if (copies) { if (file0 && l == 0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], (uint32_t)ntask); }\n'
+               '    else if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);\n',
                '    if (file0) {\n'
                '      pos0 = (uint32_t)(env >> 3) * (uint32_t)p.ncg + (uint32_t)l;\n'
                '      if ((env >> 3) == 0 && l == 0) p.cost_cnt[cost_row0(p.parity, sh)] = (uint32_t)(p.ncg * ((p.N - sh + 7) >> 3));\n'
                '    }\n')
+  replace_once(files, k, '    if (copies) pos0 = (uint32_t)__builtin_amdgcn_readlane((int)pos0, 0) + (uint32_t)l;\n', '')

@@ -33,8 +33,10 @@ def apply(files, arg, replace_once):
   # resample kernel: the end of its row loop is the end of the kernel
   replace_once(files, k, '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];\n  if (o_lo >= o_hi) return;\n',
                begin + '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];\n  if (o_lo >= o_hi) return;\n')
-  replace_once(files, k, '      if (r_first >= o_hi) { more = false; break; }\n    }\n  }\n}\n',
-               '      if (r_first >= o_hi) { more = false; break; }\n    }\n  }\n' +
+  # (behind the tail that fills the frame cache; a wave that copies from the cache returns early and leaves no end stamp)
+  kernel_end = '  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[4], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));\n'
+  replace_once(files, k, kernel_end + '}\n',
+               kernel_end +
                end('(size_t)p.N * p.nbands + (size_t)env * p.nbands + band') +
                '  if (p.exp_trace && l == 0) {   // where the task ran: block, wave of the block; and what it cost: units of its list\n'
                '    unsigned long long* t = p.exp_trace + ((size_t)p.N * p.nbands + (size_t)env * p.nbands + band) * 12;\n'
