@@ -653,6 +653,64 @@ int swb_get_sprite_types(swb_handle h, int32_t env, int32_t sprite, int32_t* fla
 int swb_get_state(swb_handle h, const swb_state* host_state, void* stream);
 int swb_set_positions(swb_handle h, const double* x_host, const double* y_host, void* stream);
 
+/* Snapshots: the state of environments saved to, and loaded from, DEVICE memory of the caller's -- nine small arrays of C slots,
+ * everything of an environment that a step changes plus the pool range it resets through.  What a closed-loop planner puts a
+ * batch back with, what seeds a larger batch from a smaller one (swb_copy_pool below), what adopts the end state of a rollout
+ * candidate without replaying it, and, copied to the host, a checkpoint.  Everything static (shapes, colours, labels, velocities)
+ * stays in the pool and is found through pool_entry: a snapshot means something only beside the pool it was saved under.
+ * Not in a snapshot: sprite overrides (swb_set_sprite_attr) -- all three calls below return SWB_ERR_STATE on a handle whose
+ * override buffers exist, as the rollouts do --, the caller's output and error buffers, and anything the host keeps (random
+ * generators, seeds).
+ *
+ * swb_pool_id: every call that installs or redraws a pool (swb_set_pool, swb_sample_pool, swb_sample_pool_tree,
+ * swb_resample_pool) gives the handle a fresh id, unique in the process and never 0; swb_copy_pool hands on the source's.
+ * *id is 0 on a handle without a pool.
+ *
+ * swb_save_state: slot c of `snap` takes the state of environment index_dev[c] (i32[C], device); index_dev == NULL: slot c takes
+ * environment c, and C must be N.  source = SWB_STATE_ROLLOUT_END: the states the handle's last rollout ended in -- index
+ * n * M + m is candidate m of environment n, NULL all N * M of them in that order (C must be N * M) --, refused with
+ * SWB_ERR_STATE where swb_rollout_frames is (no rollout has run, the pool has changed since).  A slot whose index is outside the
+ * source is left untouched.  One kernel, asynchronous on `stream`; the handle is only read.  pool_base / pool_len travel with
+ * the state: an environment that is loaded with it auto-resets through the entries its source would have played.
+ *
+ * swb_load_state: environment n takes slot slot_dev[n] (i32[N], device); -1 leaves the environment exactly as it is; any other
+ * value outside [0, C) leaves it alone too and adds one to *rejected_dev (a device word, may be NULL; the call never reads it).
+ * slot_dev == NULL: environment n takes slot n, and C must be N.  pool_id: the id the snapshot was saved under, checked against
+ * the handle's (SWB_ERR_STATE when they differ); 0 skips the check -- the caller vouches that the handle's pool holds, entry for
+ * entry, what the snapshot's did (a run resumed from swb_get_pool + swb_set_pool after a restart).  One kernel, asynchronous on
+ * `stream`, no synchronisation, no allocation.  From the next launch on a loaded environment behaves bit for bit as its source
+ * would have.  The kept run lists and the cached frame of the loaded environments are dropped (per environment: the others keep
+ * theirs); the caller's sticky error buffer, the outputs of the last step and a held rollout are not touched.  The pool ranges
+ * of the environments may have moved: swb_resample_pool, which relies on pool_base[n] = n * pool_len, is refused afterwards
+ * until a pool call lays the ranges out again.
+ *
+ * SWB_ERR_INVALID, with the function's name in the message: a null handle, a null snapshot or a null pointer in it, C < 1,
+ * C * max_sprites beyond an int, an unknown source, NULL index / slot with C different from the source's size.  SWB_ERR_STATE:
+ * no pool, override buffers, and the cases named above. */
+typedef struct swb_snapshot {      /* DEVICE memory, caller-owned, C slots; every pointer required */
+  double *x, *y;                   /* f64[C, S]  S = cfg.max_sprites of the handle that saves / loads */
+  int32_t *n_sprites, *pool_entry, *step_count, *episode, *pool_base, *pool_len;   /* i32[C] */
+  uint8_t *reset_next;             /* u8[C] */
+} swb_snapshot;
+enum swb_state_source { SWB_STATE_LIVE = 0, SWB_STATE_ROLLOUT_END = 1 };
+int swb_pool_id(swb_handle h, uint64_t* id);
+int swb_save_state(swb_handle h, int32_t source, const int32_t* index_dev, int32_t C, const swb_snapshot* snap, void* stream);
+int swb_load_state(swb_handle h, const swb_snapshot* snap, int32_t C, const int32_t* slot_dev, uint64_t pool_id,
+                   int32_t* rejected_dev, void* stream);
+
+/* The device pool of `src` copied into `dst`, device to device on `stream`: every array swb_set_pool uploads, cell_label on
+ * handles with a task that keys on position, and the angle / colour columns of the SpriteFactors observation.  dst takes
+ * pool_base_host / pool_len_host (i32[N of dst], ranges inside src's pool) as its environments' ranges, takes over src's pool
+ * id -- snapshots of src load into dst --, and is marked "reset on next step" like after swb_set_pool (swb_load_state then puts
+ * states in); its run lists get their full reservation back and a rollout it holds becomes stale.  The copies are made into
+ * fresh allocations that replace dst's only when all of them succeeded: a failure leaves dst's pool as it was.  Blocking
+ * (synchronises the device before the old arrays are freed).
+ * SWB_ERR_INVALID: a null argument, dst == src, handles that differ in device, max_sprites, n_tasks, position dtype or in whether
+ * a task keys on position, a range outside the pool, a pool whose scenes the large-frame raster kernel of dst cannot hold.
+ * SWB_ERR_STATE: src has no pool; override buffers exist on either handle.  dst cannot redraw the pool (the sampler's
+ * specification stays with src): swb_resample_pool on it is refused until it is given a pool of its own. */
+int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host, const int32_t* pool_len_host, void* stream);
+
 /* Sprite attribute setters on a LIVE sprite (sprite.py:152-175; pinned by the reference's
  * tests/sprite_test.py:138-174), for sprite `sprite` of environment `env` in its current episode:
  *   SWB_ATTR_SHAPE  value = index into the uploaded shape table: _shape = s; _reset_centered_path()

@@ -158,6 +158,24 @@ class SwbState(C.Structure):
   ]
 
 
+class SwbSnapshot(C.Structure):
+  _fields_ = [
+      ('x', C.c_void_p),
+      ('y', C.c_void_p),
+      ('n_sprites', C.c_void_p),
+      ('pool_entry', C.c_void_p),
+      ('step_count', C.c_void_p),
+      ('episode', C.c_void_p),
+      ('pool_base', C.c_void_p),
+      ('pool_len', C.c_void_p),
+      ('reset_next', C.c_void_p),
+  ]
+
+
+# enum swb_state_source
+STATE_LIVE, STATE_ROLLOUT_END = 0, 1
+
+
 class SwbVariantInfo(C.Structure):
   _fields_ = [('nw', C.c_int32), ('ncol', C.c_int32), ('vs', C.c_int32), ('lds_bytes_per_wave', C.c_int32),
               ('waves_per_simd', C.c_int32), ('resample_waves_per_simd', C.c_int32), ('n_bands', C.c_int32),
@@ -374,6 +392,10 @@ PROTOTYPES = {
     'swb_get_sprite_types': (None, [_h, _i32, _i32, _P(_i32), _h]),
     'swb_get_state': (None, [_h, _P(SwbState), _h]),
     'swb_set_positions': (None, [_h, _p, _p, _h]),
+    'swb_pool_id': (None, [_h, _P(_u64)]),
+    'swb_save_state': (None, [_h, _i32, _p, _i32, _P(SwbSnapshot), _h]),
+    'swb_load_state': (None, [_h, _P(SwbSnapshot), _i32, _p, _u64, _p, _h]),
+    'swb_copy_pool': (None, [_h, _h, _p, _p, _h]),
     'swb_set_sprite_attr': (None, [_h, _i32, _i32, _i32, _f64, _p, _p, _h]),
     'swb_set_sprite_cell_labels': (None, [_h, _i32, _i32, _p, _h]),
     'swb_get_sprite': (None, [_h, _i32, _i32, _p, _p, _p, _p, _p, _h]),

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -69,7 +70,21 @@ struct dev_buf {
     else HIP_TRY(hipMemset(ptr, 0, n * sizeof(T)));
     return 0;
   }
+  // a new allocation holding the n elements of the device array src, copied device to device on `st`
+  int clone(const T* src, size_t n, hipStream_t st) {
+    release();
+    if (n == 0) n = 1;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
+    count = n;
+    HIP_TRY(hipMemcpyAsync(ptr, src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    return 0;
+  }
+  void swap(dev_buf& o) { std::swap(ptr, o.ptr); std::swap(count, o.count); }
 };
+
+// Pool ids (swb_pool_id): one counter for the process, never 0.
+std::atomic<uint64_t> g_pool_ids{0};
+uint64_t next_pool_id() { return g_pool_ids.fetch_add(1) + 1; }
 
 }  // namespace
 
@@ -103,6 +118,7 @@ struct swb_engine {
   dev_buf<double> d_p_angle, d_p_color;
   dev_buf<swb_sampler> d_sampler;
   int pool_entries = 0;
+  uint64_t pool_id = 0;              // swb_pool_id: renewed by every call that installs or redraws the pool (0: no pool yet)
   bool pool_sampled = false, pool_uniform = false;   // pool came from swb_sample_pool / env-major fixed-length layout
   // swb_sample_pool_tree: the spec with the handle's position grids, the sprites that ran out of tries, and whether the tree
   // kernel filled the pool last (swb_resample_pool redraws with it)
@@ -722,6 +738,7 @@ int alloc_sampled_pool(swb_engine* h, int P, const int32_t* pool_base_host, cons
   const size_t PS = (size_t)P * S;
   int rc = 0;
   h->rollout_stale = true;                        // (swb_rollout_frames: as in swb_set_pool)
+  h->pool_id = next_pool_id();
   if (h->pool_entries != P || !h->d_p_angle || !h->d_p_color || (h->keyed && !h->d_p_cell_label)) {
     rc |= h->d_p_n.fill(nullptr, P);
     rc |= h->d_p_x.fill(nullptr, PS); rc |= h->d_p_y.fill(nullptr, PS);
@@ -1241,6 +1258,7 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
     if (pool->shape[i] < 0 || (h->have_shapes && pool->shape[i] >= SWB_MAX_SHAPES)) return fail(SWB_ERR_INVALID, "bad shape index in pool");
   int rc = 0;
   h->rollout_stale = true;                        // (swb_rollout_frames: a candidate may sit in an entry that is replaced here)
+  h->pool_id = next_pool_id();
   rc |= h->d_p_n.fill(pool->n_sprites, P);
   rc |= h->d_p_x.fill(pool->x, PS); rc |= h->d_p_y.fill(pool->y, PS);
   rc |= h->d_p_xv.fill(pool->x_vel, PS); rc |= h->d_p_yv.fill(pool->y_vel, PS);
@@ -1367,6 +1385,7 @@ int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* s
     return fail(SWB_ERR_STATE, "swb_resample_pool needs the env-major layout pool_base[n] = n * pool_len, equal pool_len");
   HIP_TRY(hipSetDevice(h->device));
   h->rollout_stale = true;      // (swb_rollout_frames: only entries the LIVE environments play are kept, a candidate's may be redrawn)
+  h->pool_id = next_pool_id();  // (... and so may the entries a snapshot plays)
   if (h->pool_tree) return launch_tree_sampler(h, seed, first_entry, true, (hipStream_t)stream);
   const swb_sampler_args a = sampler_args(h, seed, first_entry, true);
   hipLaunchKernelGGL(swb_sample_pool_kernel, dim3((h->pool_entries + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
@@ -1907,6 +1926,162 @@ int swb_set_positions(swb_handle h, const double* x_host, const double* y_host, 
   HIP_TRY(hipMemcpy(h->d_x, x_host, NS * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_y, y_host, NS * 8, hipMemcpyHostToDevice));
   return SWB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Snapshots (include/swb.h): swb_state_save_kernel / swb_state_load_kernel between the handle's state arrays -- or the scratch of
+// its last rollout -- and a caller's block of C slots.  Neither is a launch(): no parity, phase or cost list moves.
+// ---------------------------------------------------------------------------------------------------
+static swb_state_view live_state_view(swb_engine* h) {
+  swb_state_view v;
+  v.x = h->d_x; v.y = h->d_y; v.nspr = h->d_nspr; v.entry = h->d_entry; v.step_count = h->d_step_count; v.episode = h->d_episode;
+  v.pool_base = h->d_pool_base; v.pool_len = h->d_pool_len; v.reset_next = h->d_reset_next;
+  return v;
+}
+
+// What swb_save_state and swb_load_state refuse alike (`name`: the caller's, for the messages); the snapshot as a state view.
+static int check_snapshot_call(swb_handle h, const char* name, const swb_snapshot* snap, int32_t C, swb_state_view* v) {
+  if (!h) return fail(SWB_ERR_INVALID, "%s: null handle", name);
+  if (!snap) return fail(SWB_ERR_INVALID, "%s: snapshot is NULL", name);
+  if (!snap->x || !snap->y || !snap->n_sprites || !snap->pool_entry || !snap->step_count || !snap->episode || !snap->pool_base ||
+      !snap->pool_len || !snap->reset_next)
+    return fail(SWB_ERR_INVALID, "%s: a pointer of the snapshot is NULL (every array is required)", name);
+  if (C < 1) return fail(SWB_ERR_INVALID, "%s: C must be positive (C = %d)", name, C);
+  if ((long long)C * h->p.S > 0x7fffffffll)
+    return fail(SWB_ERR_INVALID, "%s: C x max_sprites = %d x %d does not fit an int (the slots are indexed with one)", name, C, h->p.S);
+  v->x = snap->x; v->y = snap->y; v->nspr = snap->n_sprites; v->entry = snap->pool_entry; v->step_count = snap->step_count;
+  v->episode = snap->episode; v->pool_base = snap->pool_base; v->pool_len = snap->pool_len; v->reset_next = snap->reset_next;
+  return 0;
+}
+
+int swb_pool_id(swb_handle h, uint64_t* id) {
+  if (!h || !id) return fail(SWB_ERR_INVALID, "swb_pool_id: null argument");
+  *id = h->have_pool ? h->pool_id : 0;
+  return SWB_OK;
+}
+
+int swb_save_state(swb_handle h, int32_t source, const int32_t* index_dev, int32_t C, const swb_snapshot* snap, void* stream) {
+  swb_state_view dst;
+  if (int rc = check_snapshot_call(h, "swb_save_state", snap, C, &dst)) return rc;
+  if (source != SWB_STATE_LIVE && source != SWB_STATE_ROLLOUT_END) return fail(SWB_ERR_INVALID, "swb_save_state: unknown source %d", source);
+  if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_save_state: swb_set_pool has not been called");
+  if (h->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_save_state: sprite setters have been called on this handle; snapshots under live overrides are not supported");
+  long long n_src = h->p.N;
+  swb_state_view src = live_state_view(h);
+  if (source == SWB_STATE_ROLLOUT_END) {
+    if (!h->rollout_M) return fail(SWB_ERR_STATE, "swb_save_state: no rollout has run on this handle (swb_rollout first)");
+    if (h->rollout_stale)
+      return fail(SWB_ERR_STATE, "swb_save_state: the pool has changed since the last rollout (swb_set_pool, swb_sample_pool or "
+                  "swb_resample_pool): its candidates may sit in entries that have been redrawn; roll out again");
+    n_src = (long long)h->p.N * h->rollout_M;          // (the scratch is in candidate order already: v = n * M + m)
+    src = rollout_state_view(h->d_rollout.ptr, (size_t)n_src, (size_t)h->p.S);
+  }
+  if (!index_dev && C != n_src)
+    return fail(SWB_ERR_INVALID, "swb_save_state: index is NULL (slot c takes element c) but C = %d and the source has %lld", C, n_src);
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t threads = (size_t)C * h->p.S;
+  hipLaunchKernelGGL(swb_state_save_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                     index_dev, (int)C, (int)h->p.S, (int)n_src);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
+}
+
+int swb_load_state(swb_handle h, const swb_snapshot* snap, int32_t C, const int32_t* slot_dev, uint64_t pool_id,
+                   int32_t* rejected_dev, void* stream) {
+  swb_state_view src;
+  if (int rc = check_snapshot_call(h, "swb_load_state", snap, C, &src)) return rc;
+  if (!slot_dev && C != h->p.N)
+    return fail(SWB_ERR_INVALID, "swb_load_state: slot is NULL (environment n takes slot n) but C = %d and the handle has %d environments",
+                C, h->p.N);
+  if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_load_state: swb_set_pool has not been called");
+  if (h->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_load_state: sprite setters have been called on this handle; snapshots under live overrides are not supported");
+  if (pool_id != 0 && pool_id != h->pool_id)
+    return fail(SWB_ERR_STATE, "swb_load_state: the snapshot was saved under pool %llu, the handle holds pool %llu (a pool call since "
+                "may have redrawn the entries it plays; pool_id = 0 skips the check)", (unsigned long long)pool_id,
+                (unsigned long long)h->pool_id);
+  HIP_TRY(hipSetDevice(h->device));
+  // Invalidation, per environment: the kernel clears SWB_RHDR_STAMP of the environments it loads, so their next cover wave
+  // builds (and resets SWB_RHDR_FRAME); the epoch stays, the others keep lists and cached frames.  A handle without headers
+  // has nothing to clear: painting builds, large frames and many sprites have no lists and pass epoch 0 at every launch, and
+  // headers that are not allocated yet (no launch so far, or dropped by a trim or a pool call) come back zeroed -- no stamp.
+  uint32_t* const rhdr = h->d_rhdr ? h->d_rhdr.ptr : nullptr;
+  // (the ranges may have moved between environments: swb_resample_pool's skip of live entries needs the env-major layout)
+  h->pool_uniform = false;
+  const size_t threads = (size_t)h->p.N * h->p.S;
+  hipLaunchKernelGGL(swb_state_load_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
+                     live_state_view(h), slot_dev, (int)C, (int)h->p.N, (int)h->p.S, rhdr, rejected_dev);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
+}
+
+int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host, const int32_t* pool_len_host, void* stream) {
+  if (!dst || !src || !pool_base_host || !pool_len_host) return fail(SWB_ERR_INVALID, "swb_copy_pool: null argument");
+  if (dst == src) return fail(SWB_ERR_INVALID, "swb_copy_pool: dst and src are the same handle");
+  if (dst->device != src->device || dst->p.S != src->p.S || dst->p.n_tasks != src->p.n_tasks || dst->p.pos_is_f32 != src->p.pos_is_f32 ||
+      dst->keyed != src->keyed)
+    return fail(SWB_ERR_INVALID, "swb_copy_pool: the handles differ (device %d / %d, max_sprites %d / %d, n_tasks %d / %d, pos_is_f32 %d / %d, "
+                "a task keys on position %d / %d)", dst->device, src->device, dst->p.S, src->p.S, dst->p.n_tasks, src->p.n_tasks,
+                dst->p.pos_is_f32, src->p.pos_is_f32, (int)dst->keyed, (int)src->keyed);
+  if (!src->have_pool) return fail(SWB_ERR_STATE, "swb_copy_pool: src has no pool (swb_set_pool has not been called on it)");
+  if (dst->d_ov_flag || src->d_ov_flag)
+    return fail(SWB_ERR_STATE, "swb_copy_pool: sprite setters have been called on one of the handles; snapshots under live overrides are not supported");
+  const int P = src->pool_entries, N = dst->p.N;
+  for (int i = 0; i < N; ++i)
+    if (pool_len_host[i] < 1 || pool_base_host[i] < 0 || pool_base_host[i] + pool_len_host[i] > P)
+      return fail(SWB_ERR_INVALID, "swb_copy_pool: env %d: pool range [%d, +%d) outside the pool of %d", i, pool_base_host[i], pool_len_host[i], P);
+  const int verts = src->have_shapes ? src->p.max_edges : 0;       // (the pool's largest scene: sizes dst's LDS as it does src's)
+  if (verts > 0)
+    if (int rc = lf_check_vertices(dst, verts, "swb_copy_pool")) return rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  const hipStream_t st = (hipStream_t)stream;
+  // Into temporaries, swapped in once every copy is made (the advice on swb_set_pool): a failure half-way leaves dst's pool whole.
+  // SWB_COPY_POOL_FAIL_AT (tests): the allocation that fails.
+  dev_buf<int32_t> t_n, t_shape, t_base, t_len;
+  dev_buf<double> t_x, t_y, t_xv, t_yv, t_scale, t_ca, t_sa, t_angle, t_color;
+  dev_buf<uint32_t> t_rgb;
+  dev_buf<int8_t> t_label, t_cell_label;
+  dev_buf<uint8_t> t_attr;
+  const bool have_angle = src->p.p_angle != nullptr, have_color = src->p.p_color != nullptr;
+  int made = 0, fail_at = -1;
+  if (const char* x = getenv("SWB_COPY_POOL_FAIL_AT")) fail_at = atoi(x);
+#define SWB_CLONE(tmp, from)                                                                                               \
+  do {                                                                                                                     \
+    if (made++ == fail_at) return fail(SWB_ERR_HIP, "swb_copy_pool: allocation %d refused (SWB_COPY_POOL_FAIL_AT)", made - 1); \
+    if (tmp.clone(src->from.ptr, src->from.count, st)) return SWB_ERR_HIP;                                                 \
+  } while (0)
+  SWB_CLONE(t_n, d_p_n);
+  SWB_CLONE(t_x, d_p_x); SWB_CLONE(t_y, d_p_y); SWB_CLONE(t_xv, d_p_xv); SWB_CLONE(t_yv, d_p_yv);
+  SWB_CLONE(t_scale, d_p_scale); SWB_CLONE(t_ca, d_p_ca); SWB_CLONE(t_sa, d_p_sa);
+  SWB_CLONE(t_shape, d_p_shape); SWB_CLONE(t_rgb, d_p_rgb); SWB_CLONE(t_label, d_p_label); SWB_CLONE(t_attr, d_p_attr);
+  if (src->keyed) SWB_CLONE(t_cell_label, d_p_cell_label);
+  if (have_angle) SWB_CLONE(t_angle, d_p_angle);
+  if (have_color) SWB_CLONE(t_color, d_p_color);
+#undef SWB_CLONE
+  if (t_base.fill(pool_base_host, N) || t_len.fill(pool_len_host, N)) return SWB_ERR_HIP;
+  HIP_TRY(hipDeviceSynchronize());                 // (the copies are made; work in flight may still read dst's old arrays)
+  dst->d_p_n.swap(t_n); dst->d_p_x.swap(t_x); dst->d_p_y.swap(t_y); dst->d_p_xv.swap(t_xv); dst->d_p_yv.swap(t_yv);
+  dst->d_p_scale.swap(t_scale); dst->d_p_ca.swap(t_ca); dst->d_p_sa.swap(t_sa); dst->d_p_shape.swap(t_shape); dst->d_p_rgb.swap(t_rgb);
+  dst->d_p_label.swap(t_label); dst->d_p_attr.swap(t_attr);
+  if (src->keyed) dst->d_p_cell_label.swap(t_cell_label);
+  if (have_angle) dst->d_p_angle.swap(t_angle);
+  if (have_color) dst->d_p_color.swap(t_color);
+  dst->d_pool_base.swap(t_base); dst->d_pool_len.swap(t_len);
+  bump_list_epoch(dst);
+  dst->rollout_stale = true;
+  bind_pool(dst, have_angle, have_color);
+  dst->pool_entries = P;
+  dst->pool_id = src->pool_id;
+  dst->pool_sampled = false;                       // (the sampler's specification is not copied: dst cannot redraw)
+  dst->pool_tree = false;
+  dst->pool_uniform = false;
+  if (verts > 0) dst->p.max_edges = verts;
+  HIP_TRY(hipMemsetAsync(dst->d_reset_next, 1, N, st));
+  HIP_TRY(hipMemsetAsync(dst->d_episode, 0, sizeof(int32_t) * N, st));
+  HIP_TRY(hipMemsetAsync(dst->d_step_count, 0, sizeof(int32_t) * N, st));
+  dst->have_pool = true;
+  return restore_run_list_reservation(dst);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -3207,6 +3207,56 @@ swb_rollout_pick_kernel(const swb_state_view src, const swb_state_view dst, cons
   }
 }
 
+// Snapshots (swb_save_state, swb_load_state): the nine arrays of a state move between the handle and a caller's block of C slots.
+// Both kernels are the pick kernel's copy with the index the other way round or the same way, and without its clamp: plain
+// vector loads and stores, one thread per (slot, sprite) or (environment, sprite), the words of an environment by the thread of
+// sprite 0.  Source and destination are different allocations (the handle's, the caller's), so nothing a launch writes is read
+// in it (THE RULE); no cross-lane operation.
+//   swb_state_save_kernel   slot c takes element index[c] (NULL: c) of `src`, the live state or a rollout's scratch of n_src
+//                           elements; an index outside [0, n_src) leaves the slot as it is.
+__global__ void __launch_bounds__(256)
+swb_state_save_kernel(const swb_state_view src, const swb_state_view dst, const int32_t* index, int C, int S, int n_src) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);         // (C * S < 2^31: swb_save_state checks)
+  if (idx >= C * S) return;
+  const int c = idx / S, s = idx - c * S;
+  const int e = index ? index[c] : c;
+  if (e < 0 || e >= n_src) return;
+  dst.x[idx] = src.x[(size_t)e * S + s];
+  dst.y[idx] = src.y[(size_t)e * S + s];
+  if (s == 0) {
+    dst.nspr[c] = src.nspr[e]; dst.entry[c] = src.entry[e]; dst.step_count[c] = src.step_count[e]; dst.episode[c] = src.episode[e];
+    dst.reset_next[c] = src.reset_next[e];
+    dst.pool_base[c] = src.pool_base[e]; dst.pool_len[c] = src.pool_len[e];
+  }
+}
+
+//   swb_state_load_kernel   live environment n takes slot slot[n] (NULL: n) of the snapshot `src`; -1 leaves it exactly as it
+//                           is, any other value outside [0, C) too and is counted in *rejected (may be NULL).  The thread of
+//                           sprite 0 also clears the environment's SWB_RHDR_STAMP where the handle has run-list headers (rhdr;
+//                           NULL: none): its next cover wave then finds no stamp of any epoch, builds its lists and resets
+//                           SWB_RHDR_FRAME, whatever the sprites it was given do in that launch.  Environments that are not
+//                           loaded keep stamp, lists and cached frame.
+__global__ void __launch_bounds__(256)
+swb_state_load_kernel(const swb_state_view src, const swb_state_view dst, const int32_t* slot, int C, int N, int S, uint32_t* rhdr,
+                      int32_t* rejected) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);         // (N * S < 2^31, as in swb_factors_kernel)
+  if (idx >= N * S) return;
+  const int n = idx / S, s = idx - n * S;
+  const int c = slot ? slot[n] : n;
+  if (c < 0 || c >= C) {
+    if (s == 0 && c != -1 && rejected) atomicAdd(rejected, 1);
+    return;
+  }
+  dst.x[idx] = src.x[(size_t)c * S + s];
+  dst.y[idx] = src.y[(size_t)c * S + s];
+  if (s == 0) {
+    dst.nspr[n] = src.nspr[c]; dst.entry[n] = src.entry[c]; dst.step_count[n] = src.step_count[c]; dst.episode[n] = src.episode[c];
+    dst.reset_next[n] = src.reset_next[c];
+    dst.pool_base[n] = src.pool_base[c]; dst.pool_len[n] = src.pool_len[c];
+    if (rhdr) rhdr[(size_t)n * SWB_RHDR_DWORDS + SWB_RHDR_STAMP] = 0u;
+  }
+}
+
 // swb_rollout_trajectory: where swb_rollout_kernel<true> keeps the state every step leaves.  `traj` is laid out like the scratch
 // with [K][N * M] in front of every array -- slot k of virtual environment v is element k * N * M + v --, so that the view
 // advanced by k * N * M + c * N is a valid swb_state_view of N environments for a render launch.  pool_base / pool_len do not

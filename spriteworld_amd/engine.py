@@ -18,6 +18,56 @@ def _ptr(a):
   return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+class Snapshot(object):
+  """The state of C environments (swb_snapshot): the nine tensors x, y f64[C, S], n_sprites, pool_entry, step_count, episode,
+  pool_base, pool_len i32[C] and reset_next u8[C], the id of the pool they were saved under (`pool_id`) and S (`max_sprites`).
+  `len()` is C.  `.cpu()` / `.to(device)` return a copy elsewhere (a checkpoint and its way back); the tensors are plain torch
+  tensors and may be indexed, stacked or saved like any.  A snapshot means something only beside the pool it was saved under:
+  `Engine.get_pool()` is the other half of a checkpoint."""
+
+  FIELDS = ('x', 'y', 'n_sprites', 'pool_entry', 'step_count', 'episode', 'pool_base', 'pool_len', 'reset_next')
+  _DTYPES = dict(x=torch.float64, y=torch.float64, reset_next=torch.uint8)
+
+  def __init__(self, tensors, pool_id, max_sprites):
+    self.pool_id, self.max_sprites = int(pool_id), int(max_sprites)
+    for k in self.FIELDS:
+      setattr(self, k, tensors[k])
+
+  @classmethod
+  def empty(cls, C, S, device, pool_id=0):
+    """C slots that no state has been saved into yet: each an environment without sprites that resets through pool entry 0 at
+    its next step -- what a slot `save_state` leaves untouched (an index out of range) loads as."""
+    new = lambda k: torch.zeros((C, S) if k in ('x', 'y') else (C,), dtype=cls._DTYPES.get(k, torch.int32), device=device)
+    tensors = {k: new(k) for k in cls.FIELDS}
+    tensors['pool_len'].fill_(1)
+    tensors['reset_next'].fill_(1)
+    return cls(tensors, pool_id, S)
+
+  def __len__(self):
+    return int(self.n_sprites.shape[0])
+
+  @property
+  def device(self):
+    return self.x.device
+
+  def to(self, device):
+    return Snapshot({k: getattr(self, k).to(device, copy=True) for k in self.FIELDS}, self.pool_id, self.max_sprites)
+
+  def cpu(self):
+    return self.to(torch.device('cpu'))
+
+  def as_struct(self):
+    s = _abi.SwbSnapshot()
+    for k in self.FIELDS:
+      t = getattr(self, k)
+      want = (len(self), self.max_sprites) if k in ('x', 'y') else (len(self),)
+      if tuple(t.shape) != want or t.dtype != self._DTYPES.get(k, torch.int32) or not t.is_contiguous():
+        raise ValueError('Snapshot.%s must be a contiguous %s%s tensor, got %s %s' % (k, self._DTYPES.get(k, torch.int32), list(want),
+                                                                                   t.dtype, tuple(t.shape)))
+      setattr(s, k, t.data_ptr())
+    return s
+
+
 class Engine(object):
   """N batched environments on one MI355X (`cfg`: _abi.SwbConfig, `pool`: lowering.Pool)."""
 
@@ -426,6 +476,85 @@ class Engine(object):
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.float64)
     self._check(self.lib.swb_set_positions(self._h, _ptr(x), _ptr(y), self._stream()))
+
+  # ------------------------------------------------------------------ snapshots (swb_save_state / swb_load_state / swb_copy_pool)
+  def pool_id(self):
+    """The id of the pool the handle holds (swb_pool_id): renewed by every call that installs or redraws it, 0 without one."""
+    v = C.c_uint64(0)
+    self._check(self.lib.swb_pool_id(self._h, C.byref(v)))
+    return v.value
+
+  def _index_tensor(self, values, what):
+    """int32 device tensor of a 1-D integer index (tensor or array)."""
+    t = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(values))
+    if t.dim() != 1 or t.is_floating_point():
+      raise ValueError('%s must be a 1-D integer tensor or array, got %s %s' % (what, t.dtype, tuple(t.shape)))
+    return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+  def save_state(self, index=None, source='live'):
+    """A `Snapshot` of the environments `index` (int[C], tensor or array; None: all N, in order), as fresh device tensors
+    (swb_save_state: one kernel, asynchronous, the handle only read).  source='rollout': the states the candidates of the last
+    rollout ended in -- index n * M + m is candidate m of environment n, None all N * M; raises where `rollout_frames` would.
+    A slot whose index is out of range is left as `Snapshot.empty` made it."""
+    if source not in ('live', 'rollout'):
+      raise ValueError("save_state source is 'live' or 'rollout', got %r" % (source,))
+    idx = None if index is None else self._index_tensor(index, 'save_state index')
+    n_src = self.N * self._rollout_M if source == 'rollout' else self.N
+    count = int(idx.shape[0]) if idx is not None else max(n_src, 1)      # (no rollout: the library refuses)
+    with self._device_scope():
+      snap = Snapshot.empty(count, self.S, self.device, self.pool_id())
+    cs = snap.as_struct()
+    self._last_state_index = idx  # keep alive until the launch is consumed
+    self._check(self.lib.swb_save_state(self._h, _abi.STATE_ROLLOUT_END if source == 'rollout' else _abi.STATE_LIVE,
+                                        None if idx is None else C.c_void_p(idx.data_ptr()), count, C.byref(cs), self._stream()))
+    return snap
+
+  def load_state(self, snapshot, slots=None, check_pool=True):
+    """Environment n takes slot slots[n] of `snapshot` (int[N], tensor or array; -1: the environment stays exactly as it is;
+    None: slot n, and the snapshot must hold N) -- swb_load_state: one kernel, asynchronous; from the next launch on a loaded
+    environment behaves bit for bit as its source would have.  A slot value outside [-1, len(snapshot)) leaves the environment
+    alone and is counted (`load_rejected()`).  Raises when the snapshot was saved under another pool than the handle holds now,
+    unless check_pool=False: the caller vouches that the pool is the one the snapshot was saved under (a run resumed from
+    `get_pool()` + `set_pool()`).  A snapshot on another device is copied over first.  `self.obs`, the outputs of the last
+    step, the sticky error buffer and a held rollout are not touched; `resample_pool()` is refused afterwards (the pool ranges
+    may have moved between environments) until `set_pool` / `sample_pool`."""
+    if snapshot.max_sprites != self.S:
+      raise ValueError('the snapshot holds %d sprites per environment, the engine %d' % (snapshot.max_sprites, self.S))
+    if snapshot.device != self.device:
+      snapshot = snapshot.to(self.device)
+    sl = None if slots is None else self._index_tensor(slots, 'load_state slots')
+    if sl is not None and sl.shape[0] != self.N:
+      raise ValueError('load_state slots must be int[%d], got %s' % (self.N, tuple(sl.shape)))
+    if getattr(self, '_rejected', None) is None:
+      self._rejected = torch.zeros(1, dtype=torch.int32, device=self.device)
+    cs = snapshot.as_struct()
+    self._last_loaded = (snapshot, sl)  # keep alive until the launch is consumed
+    self._check(self.lib.swb_load_state(self._h, C.byref(cs), len(snapshot), None if sl is None else C.c_void_p(sl.data_ptr()),
+                                        C.c_uint64(snapshot.pool_id if check_pool else 0), C.c_void_p(self._rejected.data_ptr()),
+                                        self._stream()))
+
+  def load_rejected(self):
+    """Slot values outside [-1, C) that `load_state` calls have met since the last call of this; reads and clears the word
+    (blocking)."""
+    if getattr(self, '_rejected', None) is None:
+      return 0
+    n = int(self._rejected.item())
+    if n:
+      self._rejected.zero_()
+    return n
+
+  def copy_pool_from(self, other, pool_base, pool_len):
+    """The device pool of engine `other` copied into this one, device to device (swb_copy_pool); environment n of this engine
+    resets through entries [pool_base[n], pool_base[n] + pool_len[n]).  This engine takes over `other`'s pool id -- snapshots
+    of `other` load here -- and every environment is marked "reset on next step", as after `set_pool`."""
+    base = np.ascontiguousarray(pool_base, dtype=np.int32)
+    length = np.ascontiguousarray(pool_len, dtype=np.int32)
+    if base.shape != (self.N,) or length.shape != (self.N,):
+      raise ValueError('copy_pool_from: pool_base and pool_len must be int[%d]' % self.N)
+    self._check(self.lib.swb_copy_pool(self._h, other._h, _ptr(base), _ptr(length), self._stream()))
+    self.pool = None
+    self._pool_entries = other.pool.n_entries if other.pool is not None else other._pool_entries
+    self._rendered = 0        # (the lists' full reservation is back: trimmed again after TRIM_AFTER launches)
 
   def set_sprite_attr(self, env, sprite, attr, value, delta=None, label=None, cell_label=None):
     """sprite.py:152-175 setters on a live sprite (swb_set_sprite_attr; attr: _abi.ATTR_SHAPE / ATTR_ANGLE / ATTR_SCALE).

@@ -277,6 +277,9 @@ class BatchedEnvironment(object):
       if spent:      # (the reference: ValueError after _MAX_TRIES rejections, factor_distributions.py)
         raise EnvironmentError_('%d sprites of the last pool kept a draw their distribution rejects: max_tries = %d rejections '
                                 'were used up (TreeSampler(max_tries=...))' % (spent, self._sampler.max_tries))
+    rejected = self._engine.load_rejected() if getattr(self, '_state_loaded', False) else 0      # (one word, after a load_state only)
+    if rejected:
+      raise IndexError('load_state: %d slot values were outside [-1, len(snapshot)); those environments were left as they were' % rejected)
     err = int(self._engine.error.max().item())
     if err:
       self._engine.error.zero_()          # the flags are sticky on the device (include/swb.h): consumed here
@@ -387,6 +390,85 @@ class BatchedEnvironment(object):
     ValueError without `candidates`."""
     obs = self._engine.rollout_frames(candidates, step=step)['obs']
     return obs.permute(1, 0, 2, 3, 4) if isinstance(step, str) else obs
+
+  # ------------------------------------------------------------------ snapshots
+  # A snapshot is the DEVICE state of environments: positions, sprite counts, pool entries, step counts, episode numbers, reset
+  # flags and the pool range each resets through.  NOT part of it, and unchanged by load_state: the generator of the SelectMove
+  # noise (seed_noise), the seed and draw count of the device action stream (seed_actions), the reset sampler's seed sequence,
+  # and the record of attribute types assigned through sprite setters (_attr_assigned; engines with setter overrides refuse
+  # snapshots altogether).
+  def save_state(self, envs=None):
+    """An `engine.Snapshot` of the environments `envs` (int[C]; None: all, in order): device tensors, one kernel, no host
+    synchronisation.  `snapshot.cpu()` and `engine.get_pool()` together are a checkpoint."""
+    return self._engine.save_state(envs)
+
+  def load_state(self, snapshot, slots=None):
+    """Puts environment n into the state of slot slots[n] of `snapshot` (int[N]; -1: the environment stays as it is; None:
+    slot n): one kernel, no host synchronisation.  From the next `step()` on a loaded environment returns, bit for bit, what
+    its source would have -- auto-resets through the source's pool entries included.  Raises when the pool has been redrawn
+    since the snapshot was taken (refresh_pool / refill_pool: its entries may be gone).  Slot values outside
+    [-1, len(snapshot)) leave their environment alone and make the next `check()` raise IndexError.  With device-side reset
+    sampling the automatic pool refresh is switched off by a load: the pool ranges may have moved between environments, which
+    `refresh_pool()` cannot follow (`refill_pool()` starts afresh)."""
+    self._engine.load_state(snapshot, slots)
+    self._state_loaded = True
+    self._refresh_every = 0
+
+  def rollout_snapshot(self, candidates=None):
+    """The states the candidates of the last rollout ended in, as an `engine.Snapshot`: all N * M (slot n * M + m: candidate m
+    of environment n), or, with `candidates` (int[N]; values outside [0, M) are clamped, as in `rollout_frames`), slot n the
+    end state of candidate candidates[n] of environment n -- `env.load_state(env.rollout_snapshot(best))` advances every
+    environment by its chosen plan in one launch, without replaying the K steps."""
+    e = self._engine
+    if candidates is None:
+      return e.save_state(None, source='rollout')
+    cand = candidates if isinstance(candidates, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(candidates))
+    if cand.dim() != 1 or cand.shape[0] != self._num_envs or cand.is_floating_point():
+      raise ValueError('rollout_snapshot candidates must be int[%d], got %s %s' % (self._num_envs, cand.dtype, tuple(cand.shape)))
+    M = max(e._rollout_M, 1)  # pylint: disable=protected-access
+    cand = cand.to(device=e.device, dtype=torch.int64).clamp(0, M - 1)
+    index = torch.arange(self._num_envs, device=e.device, dtype=torch.int64) * M + cand
+    return e.save_state(index, source='rollout')
+
+  def _pool_ranges(self):
+    """(pool_base, pool_len) int32[N] as the pool was laid out when it was installed."""
+    if getattr(self, '_ranges', None) is not None:
+      return self._ranges
+    if self._engine.pool is not None:
+      return np.asarray(self._engine.pool.pool_base, np.int32), np.asarray(self._engine.pool.pool_len, np.int32)
+    k = self._episodes_per_env
+    return np.arange(self._num_envs, dtype=np.int32) * k, np.full(self._num_envs, k, np.int32)
+
+  def fork(self, num_copies):
+    """A new BatchedEnvironment of N * num_copies environments, environment n * num_copies + m in the state of environment n of
+    this one: the same task, action space, renderers and limits, the device pool copied device to device (swb_copy_pool), the
+    states put in by one save and one load.  No episode is drawn and nothing is uploaded on the way; this environment is left
+    as it is.  Every copy steps, renders and auto-resets as its source would from here on (copies that take the same actions
+    stay equal).  The copy has no sampler: its automatic pool refresh is off and `refresh_pool()` raises; `refill_pool()`
+    draws a fresh pool on the host.  Its noise generator, action stream and setter records start unset (they are not state)."""
+    M = int(num_copies)
+    if M < 1:
+      raise ValueError('fork: num_copies must be positive, got %d' % M)
+    child = object.__new__(BatchedEnvironment)
+    child.__dict__.update(self.__dict__)
+    N = self._num_envs
+    child._num_envs = N * M
+    child._cfg = type(self._cfg).from_buffer_copy(self._cfg)
+    child._cfg.n_envs = N * M
+    child._sampler = None
+    child._refresh_every = 0
+    child._steps_since_refresh = child._steps_since_check = 0
+    child._noise_gen = None
+    child._action_seed, child._action_draws = None, 0
+    child._attr_assigned = {}
+    child._rollout_steps = None
+    child._state_loaded = True
+    base, length = self._pool_ranges()
+    child._ranges = (np.repeat(base, M), np.repeat(length, M))
+    child._engine = _engine.Engine(child._cfg, None, device=self._engine.device.index or 0)
+    child._engine.copy_pool_from(self._engine, *child._ranges)
+    child._engine.load_state(self._engine.save_state(), torch.arange(N * M, device=self._engine.device) // M)
+    return child
 
   def observation(self):
     """environment.py:136-142: every renderer's view of the sprites AS THEY ARE NOW -- the frame is rendered now (swb_render)
