@@ -374,7 +374,18 @@ int swb_upload_shapes(swb_handle h, const double* verts, const int32_t* offsets,
 
 /* PIL ImagingResample 8bpc coefficient tables for one axis (host-computed, see
  * spriteworld_amd/lanczos.py): bounds i32[out,2] (xmin,len), coeffs i32[out,ksize].  A large-frame handle keeps the
- * tables as they are, with per-output prefix sums of the horizontal coefficients. */
+ * tables as they are, with per-output prefix sums of the horizontal coefficients.
+ * Accepted: the tables of any Pillow 8bpc filter (BOX, BILINEAR, HAMMING, BICUBIC, LANCZOS) and source box -- Pillow holds
+ * the box as float[4]: compute the tables from float32 box coordinates -- with windows inside the canvas, len <= ksize, and,
+ * on the tuned path, vertical windows of at least one pixel whose first and last rows never decrease from one output row to
+ * the next, at most 8 output rows in flight at any canvas row (rows whose window is open, counted from the oldest that is
+ * not complete; up to 6 run swb_resample_kernel<6>, 7 and 8 swb_resample_kernel<8>), and a horizontal prefix table -- len + 1
+ * running sums per DISTINCT vector of them -- under 32 KB.  Large-frame handles take any number of rows in flight.
+ * Everything else is refused with SWB_ERR_INVALID and a message (out_size other than the image's, axis, "bad horizontal /
+ * vertical bounds", "vertical windows are not monotone", "more than 8 output rows in flight", "horizontal prefix table too
+ * large"), and a refused upload leaves the handle's tables as they were.  An upload onto a live handle -- of the tables it
+ * already holds, too -- makes the kept run lists and the cached frames stale: the next launch lists and resamples every
+ * environment.  (tests/_resample_tables_cases.py uploads every such family.) */
 int swb_upload_resample(swb_handle h, int32_t axis /*0=horizontal,1=vertical*/, int32_t out_size,
                         int32_t ksize, const int32_t* bounds, const int32_t* coeffs);
 

@@ -21,11 +21,12 @@ from spriteworld_amd import renderers
 from spriteworld_amd import synthetic
 from spriteworld_amd import tasks
 from tests import _parity
+from tests import _resample_tables
 
 N_SPRITES = 5
 # per environment: build, fill, move, fill, move (a fill that no copy follows), fill, copy, copy, move, fill
 SCRIPT = (0, 0, 1, 0, 1, 0, 0, 0, 1, 0)
-BETWEEN = ('render', 'evaluate', 'step_without_frame', 'set_positions', 'sprite_setter', 'trim', 'rollout_frames')
+BETWEEN = ('render', 'evaluate', 'step_without_frame', 'set_positions', 'sprite_setter', 'trim', 'rollout_frames', 'upload_tables')
 GEOMETRIES = ('two_column_groups', 'bands_default', 'one_band', 'band_tasks_8', 'background')
 
 
@@ -62,9 +63,12 @@ def actions(state, hit, motion=(0.9, 0.3)):
 class Pair(object):
   """The engine and the oracle side by side, and the model of the header word: `word[e]` is what SWB_RHDR_FRAME of environment e
   holds.  A rendering launch in which e keeps its lists moves it to min(word + 1, 2) on a handle with a cache, any other to 0;
-  its tasks -- one per column group and band -- then count as copied (2), filled (1) or resampled (0)."""
+  its tasks -- one per column group and band -- then count as copied (2), filled (1) or resampled (0).
+  `tables` (the horizontal pair (bounds, coeffs), the vertical pair): resampling tables uploaded over the engine's own before the
+  first step -- the frames every step is held to are then tests/_resample_tables.py's two passes, with these tables, over the
+  canvases a second oracle paints; `canvases`: keep that second oracle in step for an `upload` later on."""
 
-  def __init__(self, make_engine, monkeypatch, cfg, pool, what, env=(), cache=True):
+  def __init__(self, make_engine, monkeypatch, cfg, pool, what, env=(), cache=True, tables=None, canvases=False):
     from oracle import oracle
     monkeypatch.setenv('SWB_LIST_STATS', '1')
     for k, v in env:
@@ -83,6 +87,26 @@ class Pair(object):
     self.copied = self.filled = self.resampled = 0
     self.scribble = False
     self.frames = []
+    self.tables = None
+    self.big = _resample_tables.canvases(cfg, pool) if (tables is not None or canvases) else None
+    if tables is not None:
+      self.upload(*tables)
+
+  def upload(self, tab_h, tab_v):
+    """swb_upload_resample of both axes on the live handle: from here on the frames are these tables'.  (The bands follow the
+    tables: the tasks per environment are read again after the next launch.)"""
+    assert self.big is not None
+    _resample_tables.upload(self.eng, tab_h, tab_v)
+    self.tables = (tab_h, tab_v)
+
+  def expected(self, want, canv):
+    """`want` with the frames the uploaded tables give (the oracle's own where none were uploaded)."""
+    if self.big is not None:
+      for k in ('step_type', 'success'):
+        np.testing.assert_array_equal(canv[k], want[k], err_msg='%s canvases %s t=%d' % (self.what, k, self.t))
+    if self.tables is not None and want['obs'] is not None:
+      want['obs'] = _resample_tables.expected_frames(canv['obs'], *self.tables)
+    return want
 
   def launch(self, keeps):
     """A rendering launch of the live state in which the waves of `keeps` kept their lists."""
@@ -91,6 +115,9 @@ class Pair(object):
       self.kept += int(keeps.sum())
       self.built += int((~keeps).sum())
     self.word = np.where(keeps & self.cache, np.minimum(self.word + 1, 2), 0)
+    if self.tables is not None:
+      v = self.eng.variant()
+      self.tasks = v['n_bands'] * v['n_column_groups']
     resample_kernel = self.cfg.anti_aliasing != 1       # (the fill kernel and the painting builds count nothing)
     if resample_kernel:
       self.copied += self.tasks * int((self.word == 2).sum())
@@ -107,6 +134,8 @@ class Pair(object):
     hit = np.broadcast_to(np.asarray(hit, dtype=bool), (self.N,))
     a = actions(self.ora.state(), hit)
     want = self.ora.step(a, render=render)
+    if self.big is not None:
+      want = self.expected(want, self.big.step(a, render=render and self.tables is not None))
     if self.scribble:
       self.eng.obs.fill_(0xA5)
     self.eng.step(a, render=render)
@@ -123,7 +152,10 @@ class Pair(object):
   def render(self, keeps):
     if self.scribble:
       self.eng.obs.fill_(0xA5)
-    np.testing.assert_array_equal(self.eng.render().cpu().numpy(), self.ora.render(), err_msg='%s render t=%d' % (self.what, self.t))
+    want = self.ora.render()
+    if self.tables is not None:
+      want = _resample_tables.expected_frames(self.big.render(), *self.tables)
+    np.testing.assert_array_equal(self.eng.render().cpu().numpy(), want, err_msg='%s render t=%d' % (self.what, self.t))
     self.launch(keeps)
 
   def close(self):
@@ -135,10 +167,10 @@ def scripted_hits(n_envs, t):
   return np.array([SCRIPT[(t + 3 * e) % len(SCRIPT)] for e in range(n_envs)], dtype=bool)
 
 
-def never_hit(make_engine, monkeypatch, n_envs, what='never_hit', env=(), steps=8, **scene):
-  """Every click a miss: step 1 (the reset) resamples, step 2 fills, steps 3 and later copy."""
+def never_hit(make_engine, monkeypatch, n_envs, what='never_hit', env=(), steps=8, tables=None, **scene):
+  """Every click a miss: step 1 (the reset) resamples, step 2 fills, steps 3 and later copy.  tables(cfg): see Pair."""
   cfg, pool = build(n_envs, **scene)
-  p = Pair(make_engine, monkeypatch, cfg, pool, what, env)
+  p = Pair(make_engine, monkeypatch, cfg, pool, what, env, tables=tables and tables(cfg))
   for _ in range(steps):
     p.step(False)
   T = p.tasks * n_envs
@@ -158,11 +190,11 @@ def hit_every_step(make_engine, monkeypatch, n_envs):
   p.close()
 
 
-def scripted(make_engine, monkeypatch, n_envs, what='scripted', env=(), cache=True, scribble=False, steps=16):
+def scripted(make_engine, monkeypatch, n_envs, what='scripted', env=(), cache=True, scribble=False, steps=16, tables=None):
   """SCRIPT, every environment at its own point of it.  `scribble`: the caller fills the whole frame buffer with 0xA5 before
-  every launch -- every byte of every frame must be written by the launch itself."""
+  every launch -- every byte of every frame must be written by the launch itself.  tables(cfg): see Pair."""
   cfg, pool = build(n_envs)
-  p = Pair(make_engine, monkeypatch, cfg, pool, what, env, cache=cache)
+  p = Pair(make_engine, monkeypatch, cfg, pool, what, env, cache=cache, tables=tables and tables(cfg))
   p.scribble = scribble
   for t in range(steps):
     p.step(scripted_hits(n_envs, t), keeps=None if cache or not any(k == 'SWB_NO_KEEP_LISTS' for k, _ in env) else False)
@@ -211,10 +243,11 @@ def alternating_buffers(make_engine, monkeypatch, n_envs):
 def call_between(make_engine, monkeypatch, n_envs, which):
   """reset, miss (fills), miss (copies) | the call | three misses that must neither copy a stale frame nor lose one."""
   cfg, pool = build(n_envs)
-  p = Pair(make_engine, monkeypatch, cfg, pool, 'between ' + which)
+  p = Pair(make_engine, monkeypatch, cfg, pool, 'between ' + which, canvases=(which == 'upload_tables'))
   for _ in range(3):
     p.step(False)
   rebuilt = True
+  fills = 2
   if which == 'render':            # a render of an unchanged state keeps, and copies: into the same buffer, scribbled first
     p.scribble = True
     p.render(True)
@@ -249,6 +282,21 @@ def call_between(make_engine, monkeypatch, n_envs, which):
     p.resampled += M * n_envs * p.tasks
     p.word[:] = 0
     p.check_counts()
+  elif which == 'upload_tables':   # another family of tables (BICUBIC, the whole canvas), then the same tables once more: an
+    # upload always makes lists and cached frames stale -- build and resample under the new tables, a fill, a copy, both times
+    aa = cfg.anti_aliasing
+    tabs = tuple(_resample_tables.tables(aa * n, n, 'bicubic') for n in (cfg.image_h, cfg.image_w))
+    old = p.frames[-1]
+    p.upload(*tabs)
+    p.scribble = True
+    p.step(False, keeps=False)
+    assert (p.frames[-1] != old).any()                                  # (the same scene: the tables are what changed)
+    p.step(False)
+    p.step(False)
+    assert p.word.tolist() == [2] * n_envs and p.filled == 2 * p.tasks * n_envs
+    assert p.frames[-1].tobytes() == p.frames[-3].tobytes()
+    p.upload(*tabs)
+    fills = 3
   else:
     raise ValueError(which)
   p.scribble = True
@@ -257,7 +305,7 @@ def call_between(make_engine, monkeypatch, n_envs, which):
   p.step(False)
   T = p.tasks * n_envs
   if rebuilt:      # the step after the call resampled everything; then a fill, then a copy
-    assert p.word.tolist() == [2] * n_envs and p.filled == 2 * T
+    assert p.word.tolist() == [2] * n_envs and p.filled == fills * T
   else:
     assert p.filled == T
   p.close()
