@@ -648,6 +648,22 @@ int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream);
 int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream);
 int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream);
 
+/* Split bands.  A batch that the band rule leaves at one band per frame, but whose resample launch is at most two rounds of
+ * resident waves, ends with its last resampling wave while most tasks only copy (frame cache).  Such a handle builds its lists
+ * and tables for swb_variant_info::split_bands bands and decides at every launch, on the device, which environments use them:
+ * one that copies files ONE whole task per column group; one that resamples or fills files its band tasks when the previous
+ * launch had at most SWB_SPLIT_WHEN frames that resampled or filled, else one whole task that walks the whole list.  Results
+ * never depend on it.  swb_variant_info::n_bands keeps reporting the nominal 1.  Switches of the environment, read at swb_create:
+ *   SWB_SPLIT_BANDS=n  0: never the mode; n >= 2: the mode with n bands at any batch size (tests, A/B runs)
+ *   SWB_SPLIT_WHEN=k   the threshold in frames (default: two per SIMD of the device); 0 never splits, a huge value always does
+ * Not by itself in the Embodied action space (the agent moves at nearly every step: nothing is kept, nothing copied; a proxy --
+ * a batch of another action space whose sprites all move at every step takes the mode, never splits, and pays for the band starts).
+ * Not under SWB_BANDS, SWB_NO_FRAME_CACHE, SWB_NO_KEEP_LISTS, SWB_NO_COST_ORDER, anti_aliasing = 1, the large-frame paths.
+ * swb_frame_stats keeps counting frames -- (environment, column group) pairs -- on such a handle, not waves.
+ * swb_split_stats: the tasks of the resample kernel since swb_create that were whole and resampled or filled / band tasks /
+ * whole and copied.  Blocking; needs SWB_LIST_STATS; SWB_ERR_STATE on a handle that is not in the mode. */
+int swb_split_stats(swb_handle h, int64_t* whole, int64_t* bands, int64_t* whole_copies, void* stream);
+
 /* SpriteFactors observation (renderers/handcrafted.py:29-82): factors_dev f64[N,S,10] in
  * sprite.FACTOR_NAMES order (x, y, shape, angle, scale, c0, c1, c2, x_vel, y_vel), `shape` as its
  * constants.ShapeType value (1-based); rows >= n_sprites[env] are zero. */
@@ -797,6 +813,9 @@ typedef struct swb_variant_info {
   int64_t run_list_bytes;     /* device memory of the hand-off lists: fixed parts + arena (0 until the first launch) */
   int64_t frame_cache_bytes;  /* device memory of the frame cache (swb_frame_stats): one frame per environment, 0 on a handle
                                * without one */
+  int32_t split_bands;        /* split-bands mode (swb_split_stats): the bands a frame that resamples is cut into when its launch
+                               * splits -- the count asked for until the first launch has placed them --, 0: the mode is off */
+  int32_t split_pad_;
 } swb_variant_info;
 int swb_variant(swb_handle h, swb_variant_info* out);
 const char* swb_build_id(void);

@@ -181,7 +181,8 @@ class SwbVariantInfo(C.Structure):
               ('waves_per_simd', C.c_int32), ('resample_waves_per_simd', C.c_int32), ('n_bands', C.c_int32),
               ('n_column_groups', C.c_int32), ('run_cap', C.c_int32), ('paint_in_cover', C.c_int32),
               ('arena_units', C.c_int32), ('large_frames', C.c_int32), ('many_sprites', C.c_int32), ('reserved_', C.c_int32),
-              ('run_list_bytes', C.c_int64), ('frame_cache_bytes', C.c_int64)]
+              ('run_list_bytes', C.c_int64), ('frame_cache_bytes', C.c_int64),
+              ('split_bands', C.c_int32), ('split_pad_', C.c_int32)]
 
 
 FACTOR_UNIFORM_F32, FACTOR_UNIFORM_INT, FACTOR_DISCRETE = 0, 1, 2
@@ -386,6 +387,7 @@ PROTOTYPES = {
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_list_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_frame_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
+    'swb_split_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_frame_cycles': (None, [_h, _P(C.c_int64), _h]),
     'swb_factors': (None, [_h, _p, _h]),
     'swb_get_env_state': (None, [_h, _i32, _p, _h]),

@@ -155,6 +155,9 @@ struct swb_engine {
   dev_buf<uint8_t> d_frame_cache;
   int copy_cost = 0;                 // what a task that copies a column group's whole frame is filed under (SWB_COPY_COST)
   dev_buf<unsigned long long> d_frame_stats;  // SWB_LIST_STATS: what the resample tasks did (swb_frame_stats)
+  // split bands (swb_params::split_bands): nbands is then the count the lists are built for, the nominal count is one
+  bool split_bands = false;
+  dev_buf<unsigned long long> d_split_stats;  // SWB_LIST_STATS: whole / band / whole-copy tasks (swb_split_stats)
   dev_buf<int32_t> d_band_y0, d_band_first, d_band_lo, d_cg_lo, d_cg_hi;
   dev_buf<uint32_t> d_v_break;
   // live sprite overrides (swb_set_sprite_attr), allocated at the first call
@@ -528,7 +531,9 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   // (the frame cache's mover takes 16 bytes per lane where the caller's buffer and every row segment of it start on 16)
   p.obs_aligned16 = (p.obs && (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0 && (p.Wo & 15) == 0) ? 1 : 0;
   // (a band task copies its band's rows only: measured, 465 units for a whole frame, 67 for one band of eight)
-  p.copy_cost = h->copy_cost / (p.band_tasks ? std::max(p.nbands, 1) : 1);
+  // (split bands: a copy is always the whole frame)
+  p.copy_cost = h->copy_cost / ((p.band_tasks && !p.split_bands) ? std::max(p.nbands, 1) : 1);
+  p.split_carry = view ? 1 : 0;
   if (!p.obs && render_only == 0 && !view) bump_list_epoch(h);
   step_timer timer(h, stream);
   if (int rc = timer.begin()) return rc;
@@ -570,6 +575,11 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   HIP_TRY(hipGetLastError());
   if (!p.obs && p.cost_cnt && render_only != 2)   // no second kernel to clear the next launch's bucket counters (kind 0; the cover kernel keeps kind 1)
     HIP_TRY(hipMemsetAsync(h->d_cost_cnt + (size_t)(p.parity ^ 1) * SWB_COST_SET, 0, SWB_COST_SET * sizeof(uint32_t), stream));
+  if (!p.obs && p.cost_cnt && p.split_bands && render_only != 2) {   // ... nor to hand the split-bands word and its cleared counters to the next launch
+    HIP_TRY(hipMemsetAsync(h->d_cost_cnt + SWB_COST_WORD_SPLIT_CNT(p.parity ^ 1, 0, 0), 0, SWB_COST_SET * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemcpyAsync(h->d_cost_cnt + SWB_COST_WORD_SPLIT(p.parity ^ 1), h->d_cost_cnt + SWB_COST_WORD_SPLIT(p.parity), sizeof(uint32_t),
+                           hipMemcpyDeviceToDevice, stream));
+  }
   guard.armed = false;
   // swb_evaluate files nothing and lists nothing: the dispatch state (parity, phase, what the previous launch filed) stays as
   // the last step left it -- an evaluation between two steps does not cost the next one its cost order (round-5 advice) --, and
@@ -995,8 +1005,32 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     while (nb < SWB_MAX_BANDS && tasks * nb < resident && (p.Ho / (2 * nb) >= 16 || (p.Ho / (2 * nb) >= 8 && tasks * nb * 2 <= resident))) nb *= 2;
     if (const char* x = getenv("SWB_BANDS")) nb = std::max(1, std::min(atoi(x), (int)SWB_MAX_BANDS));
     h->nbands = std::min(nb, p.Ho);
+    // Split bands (swb_params::split_bands): a batch whose rule gives ONE band but whose launch is at most two
+    // rounds of resident waves builds its lists and tables for SWB_SPLIT_BANDS_DEFAULT bands all the same, and every launch decides on
+    // the device which environments use them -- those that resample or fill, when few enough do that the launch ends with its
+    // last resampling wave.  Only handles that will own a frame cache (the copies stay whole) and dispatch by cost; not under
+    // SWB_BANDS, not in the Embodied action space.  SWB_SPLIT_BANDS=n (tests, A/B runs): 0 never, n >= 2 the mode with n bands at any batch size.
+    const bool cache_wanted = p.AA != 1 && !h->large_frames && !h->no_keep_lists && !getenv("SWB_NO_FRAME_CACHE");
+    const bool cost_ordered = !getenv("SWB_NO_COST_ORDER") && p.N < (1 << 24) && !h->large_frames;
+    // (not in the Embodied action space, where the agent's body moves at nearly every step: `embodied_s12` keeps 6 % of its lists,
+    // copies nothing and never splits, and the band starts in 7 700 lists a launch made its cover kernel 2 % longer.  A proxy for
+    // "almost nothing is kept", not a measure: a batch of another action space whose sprites all move at every step still takes the
+    // mode and pays that; an Embodied batch with long still periods gets it only through SWB_SPLIT_BANDS.)
+    int split = (nb == 1 && tasks <= 2 * resident && p.action_space != SWB_ACTION_EMBODIED) ? SWB_SPLIT_BANDS_DEFAULT : 0;
+    if (const char* x = getenv("SWB_SPLIT_BANDS")) split = atoi(x) >= 2 ? std::min(atoi(x), (int)SWB_MAX_BANDS) : 0;
+    if (getenv("SWB_BANDS") || !cache_wanted || !cost_ordered || std::min(split, p.Ho) < 2) split = 0;
+    if (split) {
+      h->split_bands = true;
+      h->nbands = std::min(split, p.Ho);
+      p.split_bands = 1;
+      // the threshold, in frames that resampled or filled in the previous launch: two per SIMD (swept: profiles/r20_split_bands.md)
+      p.split_when = 2 * cus * 4;
+      if (const char* x = getenv("SWB_SPLIT_WHEN")) p.split_when = (int32_t)std::max(0ll, std::min(atoll(x), 0x7fffffffll));
+    }
   }
-  const long long rs_waves = (long long)p.N * ncg * h->nbands;      // waves of the second kernel: one per (environment, column group, band)
+  // waves of the second kernel: one per (environment, column group, band) -- split bands: counted at the nominal one band, what
+  // decides priorities and dealing below is the launch the batch rule saw
+  const long long rs_waves = (long long)p.N * ncg * (h->split_bands ? 1 : h->nbands);
   // cost buckets of the second kernel's tasks: 32 of them over the cost of a run list (3 per run + 2 per 8-byte unit: a canvas row
   // costs 1 unit (one span), 2 (two or three) or more, and rows that repeat the row above nothing); the range they span is
   // fitted by every launch (cost_housekeeping), to begin with it is [0, 8 * canvas height)
@@ -1008,8 +1042,13 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     // profiles/r06_experiments/band_tasks_ab.txt).
     p.band_tasks = (h->nbands > 1 && rs_waves >= 4ll * cus * 4 && !getenv("SWB_NO_BAND_TASKS")) ? 1 : 0;
     if (const char* x = getenv("SWB_BAND_TASKS")) p.band_tasks = (h->nbands > 1 && atoi(x) != 0) ? 1 : 0;      // tests
+    // (split bands: the tasks are band tasks or whole ones; lists and grid hold the worst case, every environment in bands --
+    // any launch can meet a step in which all of them build)
+    if (h->split_bands) p.band_tasks = 1;
     p.cost_cap = ncg * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) * (p.band_tasks ? h->nbands : 1);
     std::vector<uint32_t> cnt0(5 * SWB_COST_SET + SWB_COST_WORDS, 0u);
+    // (split bands: the first launch decides as if every frame had resampled in the one before it)
+    for (int par = 0; par < 2; ++par) cnt0[SWB_COST_WORD_SPLIT(par)] = (h->split_bands && p.split_when > 0 && (long long)p.N * ncg <= p.split_when) ? 1u : 0u;
     for (int ph = 0; ph < 3; ++ph) cnt0[SWB_COST_WORD_COVER_SHIFT(ph)] = 12;   // bucket width of the cover kernel's cycle counts: 2^12 to begin with
     for (int par = 0; par < 2; ++par) {                                       // buckets of the second kernel's tasks: [0, cost_range0) to begin with
       cnt0[SWB_COST_WORD_KEY_LO(par)] = 0u;
@@ -1055,11 +1094,15 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
     if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 6)) return SWB_ERR_HIP;
     p.list_stats = h->d_list_stats;
     p.frame_stats = h->d_frame_stats;
+    if (h->split_bands) {
+      if (h->d_split_stats.fill(nullptr, 3)) return SWB_ERR_HIP;
+      p.split_stats = h->d_split_stats;
+    }
   }
   // The frame cache: N frames, for the handles whose frames the resample kernel computes from lists that can be kept -- not the
   // fill kernel and the painting builds (anti_aliasing = 1), not the large-frame and many-sprite paths, not SWB_NO_KEEP_LISTS.
   // A handle that cannot have the memory runs without it (every wave resamples, as before): no error, and none left behind.
-  h->copy_cost = SWB_COPY_COST;
+  h->copy_cost = h->split_bands ? SWB_SPLIT_COPY_COST : SWB_COPY_COST;
   if (const char* x = getenv("SWB_COPY_COST")) h->copy_cost = std::max(0, atoi(x));      // A/B runs
   if (p.AA != 1 && !h->large_frames && !h->no_keep_lists && !getenv("SWB_NO_FRAME_CACHE")) {
     const size_t bytes = (size_t)p.N * p.Wo * p.Ho * 3;
@@ -1851,6 +1894,18 @@ int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* res
   return SWB_OK;
 }
 
+int swb_split_stats(swb_handle h, int64_t* whole, int64_t* bands, int64_t* whole_copies, void* stream) {
+  if (!h || !whole || !bands || !whole_copies) return fail(SWB_ERR_INVALID, "null argument");
+  if (!h->d_split_stats)
+    return fail(SWB_ERR_STATE, "swb_split_stats: the handle is not in split-bands mode, or SWB_LIST_STATS was not set when it was created");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long w[3] = {0ull, 0ull, 0ull};
+  HIP_TRY(hipMemcpy(w, h->d_split_stats, sizeof(w), hipMemcpyDeviceToHost));
+  *whole = (int64_t)w[0]; *bands = (int64_t)w[1]; *whole_copies = (int64_t)w[2];
+  return SWB_OK;
+}
+
 int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream) {
   if (!h || !out3) return fail(SWB_ERR_INVALID, "null argument");
   if (!h->d_frame_stats) return fail(SWB_ERR_STATE, "swb_frame_cycles: SWB_LIST_STATS was not set when the handle was created");
@@ -2333,6 +2388,8 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
     }
     out->run_list_bytes = 0;
     out->frame_cache_bytes = 0;
+    out->split_bands = 0;
+    out->split_pad_ = 0;
     return SWB_OK;
   }
   const variant* v = pick_variant(h->p.Wc);
@@ -2343,7 +2400,10 @@ int swb_variant(swb_handle h, swb_variant_info* out) {
   out->lds_bytes_per_wave = (int32_t)lds_per_wave(h, v, nullptr);
   out->waves_per_simd = SWB_COVER_WAVES(v->nw);
   out->resample_waves_per_simd = SWB_RS_WAVES_PER_SIMD;
-  out->n_bands = h->p.nbands ? h->p.nbands : h->nbands;
+  // (split bands: the nominal count is one; the count the lists are cut into -- once the tables exist, the one placed -- is split_bands)
+  out->n_bands = h->split_bands ? 1 : (h->p.nbands ? h->p.nbands : h->nbands);
+  out->split_bands = h->split_bands ? (h->p.nbands ? h->p.nbands : h->nbands) : 0;
+  out->split_pad_ = 0;
   out->n_column_groups = h->p.ncg;
   out->run_cap = h->p.run_cap;
   out->paint_in_cover = paints_in_cover(h, v) ? 1 : 0;

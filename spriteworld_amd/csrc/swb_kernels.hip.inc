@@ -217,6 +217,16 @@ struct swb_params {
                                     // tasks, of the others, and the list bytes of the others (SWB_LIST_STATS; else NULL)
   int32_t obs_aligned16;       // `obs` and every row segment of a column group start on 16 bytes: the copy moves 16 bytes per lane
   int32_t copy_cost;           // the cost a task that copies is filed under (SWB_COPY_COST, over the bands of a band task)
+  // ---- split bands (DESIGN.md section 26): lists and tables are built for nbands bands and band_tasks is on, but an environment
+  // files its nbands band tasks only when it resamples or fills AND the launch's decision word (SWB_COST_WORD_SPLIT) says split;
+  // otherwise -- and always when its frame is copied -- it files ONE task per column group with SWB_TASK_WHOLE set, which takes
+  // the frame's whole rows and the whole list.  The word is written by the previous launch's cost_housekeeping: split when that
+  // launch had at most split_when frames that resampled or filled (counted by their cover waves, SWB_COST_WORD_SPLIT_CNT).
+  int32_t split_bands;         // 1: the mode is on
+  int32_t split_when;
+  int32_t split_carry;         // 1: this launch does not draw the live state (a state view): the next launch's word is this one's
+  int32_t split_pad_;
+  unsigned long long* split_stats;  // [3] resample tasks: whole ones that resampled / filled, band tasks, whole copies (SWB_LIST_STATS)
 };
 
 // --------------------------------------------------------------------------------------------
@@ -1573,7 +1583,16 @@ __device__ __forceinline__ int cost_row1(int ph, int sh) { return 2 * SWB_COST_S
 #define SWB_COST_WORD_KEY_LO(par) (5 * SWB_COST_SET + 9 + 3 * SWB_COST_SHARDS + (par))
 #define SWB_COST_WORD_KEY_RANGE(par) (5 * SWB_COST_SET + 11 + 3 * SWB_COST_SHARDS + (par))
 #define SWB_COST_WORD_KEY_SCALE(par) (5 * SWB_COST_SET + 13 + 3 * SWB_COST_SHARDS + (par))
-#define SWB_COST_WORDS (15 + 3 * SWB_COST_SHARDS)
+// Split bands (swb_params::split_bands): the decision word of the launch of parity `par` (1: an environment that resamples or
+// fills files its band tasks; 0: one whole task), written by the launch before it, and the frames that launch's cover waves
+// filed to resample or fill: a set of counters per parity, laid out and cleared like the kind-0 buckets, 32 per shard -- an
+// environment counts in word (environment / 8) % 32 of its shard.  (One word per shard was measured first: on `embodied_s12`,
+// where 94 % of the waves build, 7 700 atomics on eight words made the cover kernel 15 % longer.)
+#define SWB_COST_WORD_SPLIT(par) (5 * SWB_COST_SET + 15 + 3 * SWB_COST_SHARDS + (par))
+#define SWB_COST_WORD_SPLIT_CNT(par, sh, k) (5 * SWB_COST_SET + 17 + 3 * SWB_COST_SHARDS + ((par) * SWB_COST_SHARDS + (sh)) * SWB_COST_BUCKETS + (k))
+#define SWB_COST_WORDS (17 + 3 * SWB_COST_SHARDS + 2 * SWB_COST_SET)
+// A task word of the second kernel: environment | column group << 24 | band << 26 (swb_params::band_tasks) | SWB_TASK_WHOLE
+#define SWB_TASK_WHOLE (1 << 29)
 #define SWB_RUN_COST 3
 #define SWB_UNIT_COST 2
 #define SWB_KEY_BUCKETS_FITTED 30          // of the 32: one bucket of slack at either end
@@ -1583,7 +1602,7 @@ __device__ __forceinline__ int cost_key(int cost, uint32_t lo, uint32_t scale) {
   return (int)min(d >> 16, (unsigned long long)(SWB_COST_BUCKETS - 1));
 }
 // cnt: the 32 counts of a shard (bucket 0 first); list: its 32 lists of `cap` entries
-__device__ __forceinline__ int cost_ordered_entry(const uint32_t* cnt, cptr<int32_t> list, int cap, int i, int* bucket = nullptr) {
+__device__ __forceinline__ int cost_ordered_entry(const uint32_t* cnt, cptr<int32_t> list, int cap, int i, int* bucket = nullptr, int* filed = nullptr) {
   static_assert(SWB_COST_BUCKETS == 32, "lanes 0..31 = buckets");
   const int l = lane_id();
   const int c = (l < SWB_COST_BUCKETS) ? (int)cnt[SWB_COST_BUCKETS - 1 - l] : 0;
@@ -1594,6 +1613,7 @@ __device__ __forceinline__ int cost_ordered_entry(const uint32_t* cnt, cptr<int3
   incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);   // row_shr:8
   const int first_row = __builtin_amdgcn_readlane(incl, 15);
   incl += (l >= 16) ? first_row : 0;
+  if (filed) *filed = __builtin_amdgcn_readlane(incl, SWB_COST_BUCKETS - 1);     // entries of the shard in all
   const unsigned long long hit = __ballot(l < SWB_COST_BUCKETS && i < incl);
   if (hit == 0ull) return -1;
   const int f = __builtin_ctzll(hit);                                     // the first bucket whose running count exceeds i
@@ -1602,9 +1622,9 @@ __device__ __forceinline__ int cost_ordered_entry(const uint32_t* cnt, cptr<int3
   return list[(size_t)rfl(SWB_COST_BUCKETS - 1 - f) * cap + rfl(i - before)];
 }
 // ... of the resample / fill kernel's tasks
-__device__ __forceinline__ int cost_ordered_env(const swb_params& p, int par, int sh, int i) {
+__device__ __forceinline__ int cost_ordered_env(const swb_params& p, int par, int sh, int i, int* filed = nullptr) {
   return cost_ordered_entry(p.cost_cnt + cost_row0(par, sh), as_const(p.cost_list) + (size_t)(par * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS * p.cost_cap,
-                            p.cost_cap, i);
+                            p.cost_cap, i, nullptr, filed);
 }
 __device__ __forceinline__ uint32_t log2_level(uint32_t mean, int div) { return (uint32_t)max(31 - __clz((int)max(mean / (uint32_t)max(div, 1), 2u)), 4); }
 // The second kernel of a launch clears the kind-0 counters the NEXT launch files into (idle now) and derives, from the complete
@@ -1613,7 +1633,17 @@ __device__ __forceinline__ uint32_t log2_level(uint32_t mean, int div) { return 
 __device__ __forceinline__ void cost_housekeeping(const swb_params& p, int shard_block, int wave) {
   const int l = lane_id();
   if (shard_block < SWB_COST_SHARDS && wave == 0 && l < SWB_COST_BUCKETS) p.cost_cnt[cost_row0(p.parity ^ 1, shard_block) + l] = 0u;
+  if (p.split_bands && shard_block < SWB_COST_SHARDS && wave == 0 && l < SWB_COST_BUCKETS) p.cost_cnt[SWB_COST_WORD_SPLIT_CNT(p.parity ^ 1, shard_block, l)] = 0u;
   if (shard_block == 0 && wave == 1) {
+    // split bands: the next launch splits when this one's cover waves filed at most split_when frames to resample or fill (complete:
+    // a kernel boundary lies behind them); a launch on a state view hands on the word it was given
+    if (p.split_bands) {
+      int frames = 0;
+      if (l < SWB_COST_BUCKETS)
+        for (int sh = 0; sh < SWB_COST_SHARDS; ++sh) frames += (int)p.cost_cnt[SWB_COST_WORD_SPLIT_CNT(p.parity, sh, l)];
+      for (int o = 16; o > 0; o >>= 1) frames += __shfl_xor(frames, o, 64);
+      if (l == 0) p.cost_cnt[SWB_COST_WORD_SPLIT(p.parity ^ 1)] = p.split_carry ? p.cost_cnt[SWB_COST_WORD_SPLIT(p.parity)] : ((p.split_when > 0 && frames <= p.split_when) ? 1u : 0u);
+    }
     int c = 0;
     if (l < SWB_COST_BUCKETS)
       for (int sh = 0; sh < SWB_COST_SHARDS; ++sh) c += (int)p.cost_cnt[cost_row0(p.parity, sh) + l];
@@ -1723,6 +1753,10 @@ __device__ __forceinline__ int dealt_block(const swb_params& p, int j, int block
 // in 8 bands, every band a task: 194 248 cycles against 2 908 per unit = 67, an eighth of it.)  Swept from 64 to 1 500: the
 // kernel is flat from 64 to 700 and 7 % longer from 1 000 on, where copies stand in front of the tasks that resample.
 #define SWB_COPY_COST 460
+// Split bands (swb_params::split_bands): the bands a changed frame is cut into, and what a whole-frame copy is filed under there --
+// below the cost of a band of the mean list (about 220), so that no copy stands in front of a task that resamples.
+#define SWB_SPLIT_BANDS_DEFAULT 8
+#define SWB_SPLIT_COPY_COST 64
 #define SWB_RHDR_DWORDS (SWB_RHDR_STAMP + 4)
 #define SWB_BST_STRIDE (SWB_MAX_BANDS + 1)   // band starts of a list + its end, in LDS (swb_params::band_tasks: see emit_runs)
 __device__ __forceinline__ int run_units(int spans) { return spans <= 1 ? 1 : 2 + (spans > 3 ? (spans - 2) >> 1 : 0); }
@@ -1985,8 +2019,10 @@ swb_cover_kernel(const swb_params p) {
   // kernel's tasks, the bucket width of the cover cycles): loaded at the start of the wave, a round trip to memory that the end of the wave --
   // nothing behind it to hide a latency -- does not wait for.  (All three were written by an earlier launch.)
   uint32_t filing_words_l = 0u;
-  if (p.cost_cnt != nullptr && l < 3)
-    filing_words_l = p.cost_cnt[l == 0 ? SWB_COST_WORD_KEY_LO(p.parity) : (l == 1 ? SWB_COST_WORD_KEY_SCALE(p.parity) : SWB_COST_WORD_COVER_SHIFT(ph))];
+  // (lane 3, split bands: the launch's decision word, SWB_COST_WORD_SPLIT -- in the builds that hand lists on; the painting
+  // builds file no lists and keep three lanes)
+  if (p.cost_cnt != nullptr && l < ((!PAINT && p.split_bands) ? 4 : 3))
+    filing_words_l = p.cost_cnt[l == 0 ? SWB_COST_WORD_KEY_LO(p.parity) : (l == 1 ? SWB_COST_WORD_KEY_SCALE(p.parity) : ((PAINT || l == 2) ? SWB_COST_WORD_COVER_SHIFT(ph) : SWB_COST_WORD_SPLIT(p.parity)))];
   if (p.ccost_list) cover_cost_housekeeping(p, ph_prev, ph, ph_next);
   // (the run lists' arena: every launch -- whether it lists runs or not -- leaves the NEXT launch's counter at zero)
   if (p.arena_head != nullptr && blockIdx.x == 0 && l == 0) p.arena_head[p.parity ^ 1] = 0u;
@@ -2131,7 +2167,11 @@ swb_cover_kernel(const swb_params p) {
   // cost_l: lane g, the cost of the list of column group g; built_cycles: 0, or (kept lists) the cycles of the wave that built
   // them, in place of this wave's own; copies: the second kernel copies this environment's frame (swb_params::frame_cache).  Then the overflow slot goes back and the error flags out.
   [[maybe_unused]] auto file_lists = [&](int cost_l, const uint32_t* bst, uint32_t built_cycles, bool copies) __attribute__((always_inline)) {
-    const bool bt = bst != nullptr;
+    // Split bands (swb_params::split_bands): the band tasks only where the environment resamples or fills and the launch's word
+    // says split; else one WHOLE task per column group, under the whole list's cost -- a copy always.  Lane 0 of a wave that does
+    // not copy counts its frames for the next launch's word.
+    const bool whole = p.split_bands && (copies || __builtin_amdgcn_readlane((int)filing_words_l, 3) == 0);
+    const bool bt = bst != nullptr && !whole;
     const int ntask = bt ? p.ncg * p.nbands : p.ncg;
     const bool file0 = p.cost_cnt != nullptr && l < ntask, file1 = p.ccost_list != nullptr && l == 0;
     const int sh = env & (SWB_COST_SHARDS - 1);
@@ -2144,6 +2184,7 @@ swb_cover_kernel(const swb_params p) {
       task_cost = 4 * max((u1 - u0) + (p.AA == 1 ? 0 : (((u2 - u1) * 5) >> 4)), 0);
       task_bits = (g2 << 24) | (b2 << 26);
     }
+    if (whole) task_bits |= SWB_TASK_WHOLE;
     // (the tasks of an environment whose frame is copied from the cache, SWB_RHDR_FRAME = 2: a twentieth of a resampling task's
     // work whatever the list -- filed under the stored cost they would stand between the tasks that resample)
     if (copies) task_cost = p.copy_cost;
@@ -2163,6 +2204,7 @@ swb_cover_kernel(const swb_params p) {
     if (copies) { if (file0 && l == 0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], (uint32_t)ntask); }
     else if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);
     if (file1) pos1 = atomicAdd(&p.cost_cnt[cost_row1(ph, sh) + key1], 1u);
+    if (p.split_bands && !copies && p.cost_cnt != nullptr && l == 0) atomicAdd(&p.cost_cnt[SWB_COST_WORD_SPLIT_CNT(p.parity, sh, (env >> 3) & (SWB_COST_BUCKETS - 1))], (uint32_t)p.ncg);
     if (copies) pos0 = (uint32_t)__builtin_amdgcn_readlane((int)pos0, 0) + (uint32_t)l;
     if (file0) p.cost_list[((size_t)(p.parity * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key0) * p.cost_cap + pos0] = env | task_bits;
     if (file1) p.ccost_list[((size_t)(ph * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key1) * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) + pos1] = env;
@@ -2191,17 +2233,20 @@ swb_cover_kernel(const swb_params p) {
     }
     if (p.list_stats != nullptr && l == 0) atomicAdd(&p.list_stats[keep ? 0 : 1], 1ull);
     if (keep) {
+      // the frame (SWB_RHDR_FRAME): kept once, the resample waves of this launch fill the cache; kept again, they copy from it
+      // (written only where it changes: a wave that keeps on through a still period writes nothing at all, as before)
+      const uint32_t frame_word_was = (uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 2);
+      const uint32_t frame_word = p.frame_cache ? min(frame_word_was + 1u, 2u) : 0u;
       uint32_t* bst = nullptr;
-      if (p.band_tasks) {                                // the band starts (and, in slot nbands, the list's end) from the header
+      // the band starts (and, in slot nbands, the list's end) from the header -- split bands: not for a wave that files whole
+      // tasks (file_lists decides the same way), which is nearly every wave that keeps (a round trip to memory at the wave's end, with nothing behind it to hide it)
+      const bool files_whole = p.split_bands && (frame_word == 2u || __builtin_amdgcn_readlane((int)filing_words_l, 3) == 0);
+      if (p.band_tasks && !files_whole) {
         bst = L->outrow + 64;
         const uint32_t* hg = p.rhdr + (size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_GROUPS;
         const int g = l / SWB_BST_STRIDE, b = l - g * SWB_BST_STRIDE;
         if (g < p.ncg && b <= p.nbands) bst[l] = hg[g * SWB_RHDR_GSTRIDE + (b < p.nbands ? 1 + b : 0)];
       }
-      // the frame (SWB_RHDR_FRAME): kept once, the resample waves of this launch fill the cache; kept again, they copy from it
-      // (written only where it changes: a wave that keeps on through a still period writes nothing at all, as before)
-      const uint32_t frame_word_was = (uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 2);
-      const uint32_t frame_word = p.frame_cache ? min(frame_word_was + 1u, 2u) : 0u;
       if (l == 0 && frame_word != frame_word_was) p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_FRAME] = frame_word;
       file_lists((int)keep_words_l, bst, max((uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 1), 1u), frame_word == 2u);
       return;
@@ -2432,20 +2477,30 @@ swb_resample_kernel(const swb_params p) {
   // consecutive blocks of a shard take tasks (environment, column group[, band: swb_params::band_tasks]) of decreasing cost: the
   // eight waves of a SIMD get one of every octile.  (Without cost ordering: blockIdx.z is the column group.)
   int env = task < p.N ? task : -1, g = blockIdx.z;
+  bool whole = false;                                            // (split bands: the task is the frame's whole rows, SWB_TASK_WHOLE)
   if (p.cost_cnt) {
-    env = cost_ordered_env(p, p.parity, (int)(blockIdx.x & (SWB_COST_SHARDS - 1)),
-                           dealt_block(p, (int)(blockIdx.x >> 3), (int)(gridDim.x >> 3)) * SWB_RS_WAVES_PER_BLOCK + wave);
+    const int first = dealt_block(p, (int)(blockIdx.x >> 3), (int)(gridDim.x >> 3)) * SWB_RS_WAVES_PER_BLOCK;
+    int filed = 0;
+    // (the filed count and the whole bit are taken on every handle: one readlane and one bit test.  OPEN QUESTION: taking them only
+    // in the mode was built and measured once -- `cluster_s5:65536:5`, where the mode is off, had its resample kernel 4.5 % longer in
+    // four of six rounds, against +0.06 % for this form (profiles/r20_split_bands.md section 6).  The cause is not known: the rounds
+    // were bimodal, so it may be where the code lands rather than the six instructions.  Not a settled trade-off; measure again.)
+    env = cost_ordered_env(p, p.parity, (int)(blockIdx.x & (SWB_COST_SHARDS - 1)), first + wave, &filed);
     if (env >= 0) {
+      whole = (env & SWB_TASK_WHOLE) != 0;
       if (p.band_tasks) band = rfl((env >> 26) & 7);
       g = (env >> 24) & 3; env &= 0xffffff;
     }
     if (blockIdx.y == 0) cost_housekeeping(p, (int)blockIdx.x, wave);
+    // Split bands: the grid covers the worst case, every environment in bands -- most workgroups of a launch have no task at all.
+    // Tasks are dealt in index order, so a workgroup whose first wave has none is empty: it leaves before the table and the barrier.
+    if (p.split_bands && first >= filed) return;
   }
   int32_t* pfx = reinterpret_cast<int32_t*>(smem);               // block-shared prefix table of the horizontal pass
   for (int i = threadIdx.x; i < p.h_pfx_len; i += blockDim.x) pfx[i] = p.h_pfx[i];
   __syncthreads();
   if (env < 0) return;
-  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];
+  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[whole ? p.nbands : band + 1];
   if (o_lo >= o_hi) return;
   cptr<uint32_t> hdr = as_const(p.rhdr) + (size_t)env * SWB_RHDR_DWORDS;
   // The frame cache (swb_params::frame_cache), decided once and wave-uniform from the word the cover wave left (SWB_RHDR_FRAME):
@@ -2455,7 +2510,9 @@ swb_resample_kernel(const swb_params p) {
   const uint32_t rect_row_bytes = 3u * (uint32_t)p.Wo, rect_seg_bytes = 3u * (uint32_t)min(64, p.Wo - 64 * g);
   const size_t frame_off = (size_t)env * p.Wo * p.Ho * 3 + (size_t)(p.Ho - o_hi) * rect_row_bytes + 192u * (uint32_t)g;
   const uint32_t cycles0 = p.frame_stats ? (uint32_t)__builtin_amdgcn_s_memtime() : 0u;
-  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[frame_mode == 2u ? 0 : (frame_mode == 1u ? 1 : 2)], 1ull);
+  // (the counts are of FRAMES where an environment's tasks differ in number -- split bands: the whole task or band 0 counts)
+  if (p.frame_stats && l == 0 && (!p.split_bands || whole || band == 0)) atomicAdd(&p.frame_stats[frame_mode == 2u ? 0 : (frame_mode == 1u ? 1 : 2)], 1ull);
+  if (p.split_stats && l == 0) atomicAdd(&p.split_stats[!whole ? 1 : (frame_mode == 2u ? 2 : 0)], 1ull);
   if (frame_mode == 2u) {
     copy_frame_rect(p.frame_cache + frame_off, p.obs + frame_off, rect_row_bytes, rect_seg_bytes, o_hi - o_lo, p.obs_aligned16 != 0);
     if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[3], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));
@@ -2467,7 +2524,7 @@ swb_resample_kernel(const swb_params p) {
   // the other and the last one alone, far below the SIMD's rate; with the priority (0..3) following the remaining work --
   // "longest remaining time first" -- they finish together instead.  One level = 2^prio_shift bytes of list (about half a
   // mean list; from the previous launch's histogram, cost_housekeeping), re-evaluated at every finished output row.
-  const uint32_t u_end = 8u * hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + (band + 1 < p.nbands ? 2 + band : 0)];
+  const uint32_t u_end = 8u * hdr[SWB_RHDR_GROUPS + g * SWB_RHDR_GSTRIDE + ((!whole && band + 1 < p.nbands) ? 2 + band : 0)];
   const uint32_t prio_shift = p.cost_cnt ? as_const(p.cost_cnt)[SWB_COST_WORD_PRIO_SHIFT(p.parity)] : 0u;
   int prio = prio_shift ? (int)min((u_end - uo) >> prio_shift, 3u) : 0;
   if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[5], (unsigned long long)(u_end - uo));

@@ -423,6 +423,14 @@ class Engine(object):
     self._check(self.lib.swb_frame_stats(self._h, C.byref(w[0]), C.byref(w[1]), C.byref(w[2]), self._stream()))
     return tuple(x.value for x in w)
 
+  def split_stats(self):
+    """(whole, bands, whole_copies): the tasks of the resample kernel of a handle in split-bands mode (variant()['split_bands'])
+    that took a frame's whole rows and resampled or filled / one band of them / the whole rows and copied, since the engine was
+    created (swb_split_stats; blocking).  Needs SWB_LIST_STATS like list_stats."""
+    w = [C.c_int64(0) for _ in range(3)]
+    self._check(self.lib.swb_split_stats(self._h, C.byref(w[0]), C.byref(w[1]), C.byref(w[2]), self._stream()))
+    return tuple(x.value for x in w)
+
   def frame_cycles(self):
     """(cycles of the copying tasks, cycles of all other tasks, list bytes those walked): measurement (swb_frame_cycles)."""
     w = (C.c_int64 * 3)()

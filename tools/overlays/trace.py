@@ -31,8 +31,8 @@ def apply(files, arg, replace_once):
                '  if (p.exp_trace && l == 0) { p.exp_trace[(size_t)env * 12 + 8] = exp_cov; p.exp_trace[(size_t)env * 12 + 9] = exp_emit; p.exp_trace[(size_t)env * 12 + 10] = exp_nb; }\n'
                '    if (p.error) {\n      uint32_t e = err & ~SWB_INT_NEED_SLOT;')
   # resample kernel: the end of its row loop is the end of the kernel
-  replace_once(files, k, '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];\n  if (o_lo >= o_hi) return;\n',
-               begin + '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[band + 1];\n  if (o_lo >= o_hi) return;\n')
+  replace_once(files, k, '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[whole ? p.nbands : band + 1];\n  if (o_lo >= o_hi) return;\n',
+               begin + '  const int o_lo = as_const(p.band_lo)[band], o_hi = as_const(p.band_lo)[whole ? p.nbands : band + 1];\n  if (o_lo >= o_hi) return;\n')
   # (behind the tail that fills the frame cache; a wave that copies from the cache returns early and leaves no end stamp)
   kernel_end = '  if (p.frame_stats && l == 0) atomicAdd(&p.frame_stats[4], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));\n'
   replace_once(files, k, kernel_end + '}\n',
