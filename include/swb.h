@@ -433,6 +433,29 @@ int swb_reset_all(swb_handle h, void* stream);
  * SelectMove/DragAndDrop, or i32[N,2] for Embodied. */
 int swb_step(swb_handle h, const void* actions_dev, const swb_outputs* out, void* stream);
 
+/* swb_step for a subset of the batch: active_dev is u8[N] in device memory, NULL means every environment (swb_step is exactly
+ * that call).  An environment n with active_dev[n] == 0 takes no part in the step:
+ *   - none of its state changes (positions, sprite count, pool entry, step count, episode, setter overrides), a pending reset
+ *     STAYS pending -- it is not reset, and does not start an episode it was not asked to --, and no task is evaluated;
+ *   - row n of actions_dev is never read (it may hold NaN or integers out of range);
+ *   - entry n of out->reward, discount, step_type, success and error is not written: the caller's buffers keep what the
+ *     environment's last active step left there (a held reward must not be summed twice);
+ *   - out->obs[n] IS written, with the frame of the environment's state as it is -- byte for byte what swb_render gives.  On the
+ *     two-kernel path the environment's cover wave keeps its run lists and its frame is copied from the frame cache like that of
+ *     any environment whose sprites did not move (swb_list_stats counts it as kept, swb_frame_stats as filled, then copied);
+ *     painting builds, large frames and many-sprite handles draw the unchanged state again.
+ * One case is unspecified: the frame of an environment that has had no FIRST step since its pool was installed (swb_set_pool,
+ * swb_sample_pool, swb_copy_pool) and is inactive -- it has no sprites of its own yet.
+ * Everything else is swb_step's: the same kernels and launches, a counted step of swb_timing_enable, the same dispatch
+ * bookkeeping.  The mask is read by the launch: keep it alive and unchanged until the launch has run. */
+int swb_step_masked(swb_handle h, const void* actions_dev, const uint8_t* active_dev, const swb_outputs* out, void* stream);
+
+/* Environment.reset() for the environments n with mask_dev[n] != 0 (u8[N] in device memory; NULL is refused with
+ * SWB_ERR_INVALID): the next step in which such an environment is ACTIVE is a FIRST step from pool entry pool_base + episode %
+ * pool_len, exactly as after a LAST.  One small kernel (swb_reset_envs_kernel), asynchronous on `stream`; nothing else is
+ * touched.  Unlike swb_reset_all it leaves the kept run lists and cached frames of the other environments valid. */
+int swb_reset_envs(swb_handle h, const uint8_t* mask_dev, void* stream);
+
 /* observation() only (no state change): obs_dev u8[N,H,W,3].  Reports no swb_env_error flags: a sprite beyond the render path's
  * coordinate limit (SWB_ENV_ERR_SPAN_OVERFLOW) leaves its environment's frame unspecified without a sign; the next swb_step
  * that renders raises the flag. */

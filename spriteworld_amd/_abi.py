@@ -375,6 +375,8 @@ PROTOTYPES = {
     'swb_get_pool': (None, [_h, _P(SwbPool)]),
     'swb_reset_all': (None, [_h, _h]),
     'swb_step': (None, [_h, _p, _P(SwbOutputs), _h]),
+    'swb_step_masked': (None, [_h, _p, _p, _P(SwbOutputs), _h]),
+    'swb_reset_envs': (None, [_h, _p, _h]),
     'swb_render': (None, [_h, _p, _h]),
     'swb_evaluate': (None, [_h, _p, _h]),
     'swb_rollout': (None, [_h, _p, _i32, _i32, _P(SwbRolloutOutputs), _h]),

@@ -411,9 +411,11 @@ int check_ready(const swb_engine* h, const void* actions, int render_only) {
 }
 
 // The kernel argument of one launch: the handle's parameters with the caller's buffers bound.
-swb_params bind_step(const swb_engine* h, const void* actions, const swb_outputs* out, int render_only) {
+// `active`: the mask of swb_step_masked (swb_params::active), NULL for every other launch.
+swb_params bind_step(const swb_engine* h, const void* actions, const swb_outputs* out, int render_only, const uint8_t* active) {
   swb_params p = h->p;
   p.actions = actions;
+  p.active = active;
   p.obs = out ? out->obs : nullptr;
   p.reward = out ? out->reward : nullptr;
   p.discount = out ? out->discount : nullptr;
@@ -487,18 +489,18 @@ bool paints_in_cover(const swb_engine* h, const variant* v, bool honour_switch =
 }
 
 int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
-                 const swb_state_view* view);
+                 const swb_state_view* view, const uint8_t* active);
 
 int launch(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
-           const swb_state_view* view = nullptr) {
-  if (h->large_frames) return launch_large(h, actions, out, render_only, stream, view);
+           const swb_state_view* view = nullptr, const uint8_t* active = nullptr) {
+  if (h->large_frames) return launch_large(h, actions, out, render_only, stream, view, active);
   if (int rc = check_ready(h, actions, render_only)) return rc;
   const variant* v = pick_variant(h->p.Wc);
   if (!v) return fail(SWB_ERR_INVALID, "canvas %dx%d not supported", h->p.Wc, h->p.Hc);
   if (int rc = ensure_handoff_tables(h, !paints_in_cover(h, v))) return rc;
   int vs = 0;
   const kernel_fn fn2 = pick_resample(h->p.AA, h->vslots, &vs);
-  swb_params p = bind_step(h, actions, out, render_only);
+  swb_params p = bind_step(h, actions, out, render_only, active);
   bind_view(&p, view);
   if (p.v_tab && vs == 8) {                                           // slot tables of this VS
     p.v_tab += (size_t)p.Hc * SWB_VSLOTS;
@@ -655,9 +657,9 @@ int lf_render(swb_engine* h, const swb_params& p, hipStream_t stream) {
 }
 
 int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int render_only, hipStream_t stream,
-                 const swb_state_view* view) {
+                 const swb_state_view* view, const uint8_t* active) {
   if (int rc = check_ready(h, actions, render_only)) return rc;
-  swb_params p = bind_step(h, actions, out, render_only);
+  swb_params p = bind_step(h, actions, out, render_only, active);
   bind_view(&p, view);
   // the state phase: the cover kernel of the narrowest build with obs = NULL, or (many sprites) swb_ms_state_kernel, whose LDS
   // does not depend on the scene
@@ -1551,9 +1553,25 @@ int swb_reset_all(swb_handle h, void* stream) {
 }
 
 int swb_step(swb_handle h, const void* actions_dev, const swb_outputs* out, void* stream) {
+  return swb_step_masked(h, actions_dev, nullptr, out, stream);
+}
+
+int swb_step_masked(swb_handle h, const void* actions_dev, const uint8_t* active_dev, const swb_outputs* out, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  return launch(h, actions_dev, out, 0, (hipStream_t)stream);
+  return launch(h, actions_dev, out, 0, (hipStream_t)stream, nullptr, active_dev);
+}
+
+// (the list epoch stays: the environments marked build their lists at their FIRST step whatever the stamp says, the others go on
+// keeping theirs)
+int swb_reset_envs(swb_handle h, const uint8_t* mask_dev, void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "swb_reset_envs: null handle");
+  if (!mask_dev) return fail(SWB_ERR_INVALID, "swb_reset_envs: mask is NULL (u8[N] in device memory; swb_reset_all resets every environment)");
+  HIP_TRY(hipSetDevice(h->device));
+  hipLaunchKernelGGL(swb_reset_envs_kernel, dim3((unsigned)((h->p.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->d_reset_next.ptr,
+                     mask_dev, (int)h->p.N);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
 }
 
 int swb_render(swb_handle h, uint8_t* obs_dev, void* stream) {

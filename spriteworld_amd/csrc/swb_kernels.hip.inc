@@ -227,6 +227,11 @@ struct swb_params {
   int32_t split_carry;         // 1: this launch does not draw the live state (a state view): the next launch's word is this one's
   int32_t split_pad_;
   unsigned long long* split_stats;  // [3] resample tasks: whole ones that resampled / filled, band tasks, whole copies (SWB_LIST_STATS)
+  // ---- active mask (swb_step_masked; DESIGN.md section 27).  An environment whose byte is 0 takes no part in the step: the state
+  // phase leaves its state arrays and its entries of the outputs alone (a pending reset stays pending, its action row is not
+  // read, no task is evaluated), and its frame is drawn from the state as it is -- on the two-kernel path its wave keeps its
+  // lists like any wave whose sprites did not move.  Read once per wave, in load_env_state.  (Appended last, as above.)
+  const uint8_t* active;       // [N], NULL: every environment takes part (and everything but a step: renders, evaluations, rollouts)
 };
 
 // --------------------------------------------------------------------------------------------
@@ -661,6 +666,7 @@ __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double
 // --------------------------------------------------------------------------------------------
 struct env_state {            // what load_env_state hands on; per lane, lane s < n = sprite s
   bool first, ov;             // (uniform) this step resets the episode; the episode's sprites carry setter overrides
+  bool active;                // (uniform) the environment takes part in this step (swb_params::active); else nothing of it changes
   int en, n, sc_old;          // (uniform) pool entry, sprites, steps taken so far
   double px, py;              // position
   double scale_l, ca_l, sa_l, xv_l, yv_l;
@@ -669,19 +675,25 @@ struct env_state {            // what load_env_state hands on; per lane, lane s 
   int acti;                   // lanes 0..1: ... of the embodied action space
 };
 // what act_and_move hands to finish_step -- and `changed` (wave-uniform): some sprite's position differs BITWISE from the one the
-// step began with (false after a missed click, a zero motion, a move clipped back onto the same value -- and on a reset, which
-// moves nothing here: es.first says that)
+// step began with (false after a missed click, a zero motion, a move clipped back onto the same value, in an environment that
+// takes no part in the step -- and on a reset, which moves nothing here: es.first says that)
 struct step_cost { double cost; float cost_f32; bool cost_is_f32; int step_count; bool changed; };
 
 // Round 1 of loads (independent of each other): the environment's scalars, its live positions
 // and its action.  Round 2 (needs the pool entry): the episode's static sprite columns.
-template <bool OV, typename SC>
+// MASK = false: a caller whose parameter blocks never carry an active mask (the rollout kernels) compiles without the test.
+template <bool OV, bool MASK = true, typename SC>
 __device__ __forceinline__ env_state load_env_state(const swb_params& p, int env, SC* tscratch) {
   const int l = lane_id();
   const int S = p.S;
   double* gx = p.x + (size_t)env * S;
   double* gy = p.y + (size_t)env * S;
-  const int rn = p.render_only ? 0 : (int)p.reset_next[env];
+  // (the mask is the caller's input, written by no wave of the launch; one wave-uniform byte, made a scalar before anything
+  // branches on it -- gfx950 has no scalar byte load: the compiler loads the one address and takes the first lane)
+  bool active = true;
+  if constexpr (MASK) { if (p.active != nullptr) active = rfl((int)as_const(p.active)[env]) != 0; }
+  // (an environment that takes no part is not reset either: a pending reset stays pending)
+  const int rn = (p.render_only || !active) ? 0 : (int)p.reset_next[env];
   const int ep = p.episode[env], pbase = as_const(p.pool_base)[env], plen = as_const(p.pool_len)[env];
   const int en_old = p.entry[env], n_old = p.nspr[env], sc_old = p.step_count[env];
   double px = 0.0, py = 0.0;      // lane s < n holds sprite s's position
@@ -691,7 +703,7 @@ __device__ __forceinline__ env_state load_env_state(const swb_params& p, int env
   const int shoff_tab_l = (l <= SWB_MAX_SHAPES) ? p.shape_off[l] : 0;
   double act = 0.0;               // lanes 0..3: the action components
   int acti = 0;
-  if (!p.render_only) {
+  if (!p.render_only && active) {                       // (the action row of an environment that takes no part is never read)
     if (p.action_space == SWB_ACTION_EMBODIED) { if (l < 2) acti = reinterpret_cast<const int32_t*>(p.actions)[2 * (size_t)env + l]; }
     else if (l < 4) {
       act = p.action_is_f32 ? (double)reinterpret_cast<const float*>(p.actions)[4 * (size_t)env + l]
@@ -720,7 +732,7 @@ __device__ __forceinline__ env_state load_env_state(const swb_params& p, int env
       if (ov) { shape_l = p.ov_shape[(size_t)env * S + l]; scale_l = p.ov_scale[(size_t)env * S + l]; }
     }
   }
-  if (p.render_only != 1) {
+  if (p.render_only != 1 && active) {                   // (the task's labels: no task is evaluated without a step)
     const int8_t* lab_src = p.p_label + (size_t)en * p.n_tasks * S;
     if constexpr (OV) { if (ov) lab_src = p.ov_label + (size_t)env * p.n_tasks * S; }
     for (int i = l; i < p.n_tasks * S; i += SWB_WAVE) tscratch->labels[i] = lab_src[i];
@@ -733,7 +745,7 @@ __device__ __forceinline__ env_state load_env_state(const swb_params& p, int env
   const int so_any = __shfl(shoff_tab_l, sh_idx, 64), so_next = __shfl(shoff_tab_l, sh_idx + 1, 64);
   const int so_l = (l < n) ? so_any : 0;
   const int nv_l = (l < n) ? so_next - so_any : 0;
-  return env_state{first, ov, en, n, sc_old, px, py, scale_l, ca_l, sa_l, xv_l, yv_l, sh_idx, so_l, nv_l, act, acti};
+  return env_state{first, ov, active, en, n, sc_old, px, py, scale_l, ca_l, sa_l, xv_l, yv_l, sh_idx, so_l, nv_l, act, acti};
 }
 
 // Action decoding, the hit tests (hit(s2, tx, ty): sprite.py:113-115 contains_point of sprite s2 -- wave-uniform -- at the
@@ -749,7 +761,7 @@ __device__ __forceinline__ step_cost act_and_move(const swb_params& p, int env, 
   bool cost_is_f32 = false;
   int step_count = 0;
   bool changed = false;
-  if (!p.render_only && !es.first) {
+  if (!p.render_only && !es.first && es.active) {
     const double ox = px, oy = py;
     step_count = es.sc_old + 1;                         // :93
     int moved = -1;
@@ -2141,7 +2153,7 @@ swb_cover_kernel(const swb_params p) {
   const step_cost sc = act_and_move(p, env, es, hit);
   const double px = es.px, py = es.py;
   SWB_HOOK_PHASE_END(4)
-  if (p.render_only != 1) {
+  if (p.render_only != 1 && es.active) {                // (no part in the step: no task, no outputs -- skipped, not masked)
     err |= finish_step<OV>(p, env, es, sc, tscratch);
     wave_sync();                                        // (the scratch aliases the span lists)
   }
@@ -3167,7 +3179,7 @@ swb_ms_state_kernel(const swb_params p) {
     return contains_point_wave(cpath, nv, tx, ty);
   };
   const step_cost sc = act_and_move(p, env, es, hit);
-  if (p.render_only != 1) {
+  if (p.render_only != 1 && es.active) {
     const uint32_t err = finish_step<OV>(p, env, es, sc, tscratch);
     if (l == 0 && p.error && err) p.error[env] |= (uint8_t)err;         // sticky: the caller clears
   }
@@ -3219,7 +3231,7 @@ swb_rollout_fork_kernel(const swb_params p, const swb_rollout_args a) {
     swb_params q = p;
     q.x = a.x; q.y = a.y; q.nspr = a.nspr; q.entry = a.entry; q.step_count = a.step_count; q.episode = a.episode;
     q.reset_next = a.reset_next; q.pool_base = a.pool_base; q.pool_len = a.pool_len;
-    q.obs = nullptr; q.error = nullptr; q.render_only = 0;
+    q.obs = nullptr; q.error = nullptr; q.render_only = 0; q.active = nullptr;
     q.actions = reinterpret_cast<const unsigned char*>(a.actions) + o * action_bytes;
     q.reward = a.reward ? a.reward + o : nullptr;
     q.discount = a.discount ? a.discount + o : nullptr;
@@ -3236,6 +3248,13 @@ swb_rollout_fork_kernel(const swb_params p, const swb_rollout_args a) {
     a.reset_next[v] = p.reset_next[n];
     a.pool_base[v] = p.pool_base[n]; a.pool_len[v] = p.pool_len[n];
   }
+}
+
+// swb_reset_envs: environment n resets at its next active step where mask[n] != 0; nothing else is touched.
+__global__ void __launch_bounds__(256)
+swb_reset_envs_kernel(uint8_t* reset_next, const uint8_t* mask, int N) {
+  const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (n < N && mask[n] != 0) reset_next[n] = 1;
 }
 
 // The per-environment state arrays a launch reads and writes (swb_params "live state", and the pool range beside it): the live
@@ -3401,7 +3420,7 @@ swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep,
   if constexpr (SAMPLE) drawer.start(sa, v / a.M, v % a.M);
   for (int k = 0; k < a.K; ++k) {
     const swb_params& q = *(const swb_params*)as_const(a.steps + k);
-    env_state es = load_env_state<false>(q, v, tscratch);
+    env_state es = load_env_state<false, false>(q, v, tscratch);
     if constexpr (SAMPLE) drawer.draw(sa, q, k, es, cpath);
     // sprite.py:113-115 contains_point of sprite s2 (wave-uniform), as in swb_ms_state_kernel: its centred path into LDS,
     // lanes = vertices, then the even-odd test

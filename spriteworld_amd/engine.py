@@ -207,8 +207,32 @@ class Engine(object):
   def reset_all(self):
     self._check(self.lib.swb_reset_all(self._h, self._stream()))
 
-  def step(self, actions, render=True):
-    """actions: device tensor f64[N,4] (f32 if cfg.action_is_f32) or i32[N,2] (Embodied)."""
+  def _mask_tensor(self, mask, what):
+    """Contiguous uint8 device tensor of a bool or uint8 mask of shape [N] (tensor or array)."""
+    t = mask if isinstance(mask, torch.Tensor) else None
+    if t is None:
+      try:
+        t = torch.as_tensor(np.ascontiguousarray(mask))
+      except (TypeError, ValueError, RuntimeError):
+        raise ValueError('%s must be a bool or uint8 tensor or array of shape [%d], got %r' % (what, self.N, type(mask)))
+    if t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != (self.N,):
+      raise ValueError('%s must be a bool or uint8 tensor or array of shape [%d], got %s %s' % (what, self.N, t.dtype, tuple(t.shape)))
+    return t.to(device=self.device, dtype=torch.uint8).contiguous()
+
+  def reset_envs(self, mask):
+    """Environment.reset() for the environments of `mask` (bool or uint8 [N]; swb_reset_envs: one small kernel, asynchronous):
+    the next step in which such an environment is active is a FIRST step from its next pool entry.  The others are untouched and
+    go on keeping their run lists and cached frames."""
+    m = self._mask_tensor(mask, 'reset_envs mask')
+    self._last_reset_mask = m  # keep alive until the launch is consumed
+    self._check(self.lib.swb_reset_envs(self._h, C.c_void_p(m.data_ptr()), self._stream()))
+
+  def step(self, actions, render=True, active=None):
+    """actions: device tensor f64[N,4] (f32 if cfg.action_is_f32) or i32[N,2] (Embodied).
+    active: None, or a bool or uint8 mask of shape [N] (swb_step_masked).  An environment whose entry is 0 takes no part in the
+    step: its state does not change, a pending reset stays pending, its action row is never read (NaN is fine) and its entries
+    of reward, discount, step_type, success and error keep the values of its last active step; `obs` holds the frame of its
+    current state all the same."""
     if self.cfg.action_space == _abi.ACTION_EMBODIED:
       want = torch.int32
     else:
@@ -220,8 +244,14 @@ class Engine(object):
     assert actions.numel() == self.N * (2 if want == torch.int32 else 4), actions.shape
     self._last_actions = actions  # keep alive until the launch is consumed
     outs = self._outs if render else self._outs_norender
-    self._check(self.lib.swb_step(self._h, C.c_void_p(actions.data_ptr()), C.byref(outs),
-                                  self._stream()))
+    if active is None:
+      self._check(self.lib.swb_step(self._h, C.c_void_p(actions.data_ptr()), C.byref(outs),
+                                    self._stream()))
+    else:
+      m = self._mask_tensor(active, 'step active')
+      self._last_active = m  # keep alive until the launch is consumed
+      self._check(self.lib.swb_step_masked(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(m.data_ptr()), C.byref(outs),
+                                           self._stream()))
     if render:
       self._rendered += 1
       if self._rendered == self.TRIM_AFTER:

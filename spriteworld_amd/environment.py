@@ -73,6 +73,12 @@ class Rollout(collections.namedtuple('Rollout', ['step_type', 'reward', 'discoun
 RolloutSteps = collections.namedtuple('RolloutSteps', ['x', 'y', 'n_sprites'])
 
 
+# What `BatchedEnvironment.run_episodes` returns, device tensors [N]: episode_return f64 (the rewards of the environment's active
+# non-FIRST steps, summed in step order), length i64 (how many such steps), episodes i32 (LAST steps seen) and success bool (the
+# success flag of its most recent LAST step).
+EpisodeStats = collections.namedtuple('EpisodeStats', ['episode_return', 'length', 'episodes', 'success'])
+
+
 _ACTION_KEY_DOMAIN = 0xA5A5C3D2E1F00F1E      # folded into the seed of the device action stream (_next_action_seed)
 
 # What `BatchedEnvironment.sample_contained_positions` returns, device tensors: position f64[N, 2], sprite i32[N], tries i32[N].
@@ -289,10 +295,18 @@ class BatchedEnvironment(object):
         raise ValueError('Number of labels is invalid for davies_bouldin_score')
       raise EnvironmentError_('internal engine error bits 0x%x' % err)
 
-  def reset(self):
-    """Environment.reset() for every environment: returns the FIRST time steps."""
-    self._engine.reset_all()
-    return self.step(self.null_actions())
+  def reset(self, envs=None):
+    """Environment.reset() for every environment: returns the FIRST time steps.
+    With `envs` (a bool or uint8 mask of shape [N]; anything else raises ValueError) only those environments are reset
+    (swb_reset_envs), by one null-action step in which only they are active: they return FIRST, from their next pool entry, and
+    the others are untouched -- their entries of the returned time step are those of their last active step, as in
+    `step(active=...)`."""
+    if envs is None:
+      self._engine.reset_all()
+      return self.step(self.null_actions())
+    mask = self._engine._mask_tensor(envs, 'reset envs')  # pylint: disable=protected-access
+    self._engine.reset_envs(mask)
+    return self.step(self.null_actions(), active=mask)
 
   def null_actions(self):
     if self._cfg.action_space == _abi.ACTION_EMBODIED:
@@ -300,8 +314,16 @@ class BatchedEnvironment(object):
     dt = torch.float32 if self._cfg.action_is_f32 else torch.float64
     return torch.zeros((self._num_envs, 4), dtype=dt, device=self._engine.device)
 
-  def step(self, actions):
-    """actions: [N, 4] float (SelectMove / DragAndDrop) or [N, 2] int (Embodied)."""
+  def step(self, actions, active=None):
+    """actions: [N, 4] float (SelectMove / DragAndDrop) or [N, 2] int (Embodied).
+    active: None (every environment), or a bool or uint8 mask of shape [N] (anything else raises ValueError).  An environment
+    whose entry is 0 takes no part in the step: its state does not change, an auto-reset that is due stays due, and its action
+    row is never read (it may hold NaN).  The returned time step HOLDS, for such an environment, the step type, reward, discount
+    and success flag of its last active step -- a held reward must not be summed twice: weigh sums with the mask -- while the
+    image shows its current state.  SelectMove noise is drawn for the whole batch whatever the mask, so an environment's noise
+    does not depend on which others are active; the pool refresh and error check tick as for any step."""
+    if active is not None:
+      active = self._engine._mask_tensor(active, 'step active')  # pylint: disable=protected-access
     if self._noise_scale is not None:
       e = self._engine
       if not isinstance(actions, torch.Tensor):
@@ -309,13 +331,53 @@ class BatchedEnvironment(object):
       actions = actions.to(device=e.device)
       noise = torch.randn(actions.shape, dtype=torch.float64, device=e.device, generator=self._noise_gen)
       actions = actions.to(torch.float64) + noise * self._noise_scale.to(e.device)      # float64 from here on (see __init__)
-    self._engine.step(actions, render=self._render)
+    if active is None:      # (an engine stand-in with the older step(actions, render) surface still serves unmasked steps)
+      self._engine.step(actions, render=self._render)
+    else:
+      self._engine.step(actions, render=self._render, active=active)
     if self._refresh_every and self._sampler is not None:
       self._steps_since_refresh += 1
       if self._steps_since_refresh >= self._refresh_every:
         self._steps_since_refresh = 0
         self.refresh_pool()
     return self._timestep()
+
+  def run_episodes(self, policy, episodes_per_env=1, max_steps=None):
+    """Exactly `episodes_per_env` (E) episodes of every environment, then stop: the evaluation loop.  Starts with `reset()`, then
+    calls `policy(timestep, active) -> actions` before every step -- `timestep` the `BatchedTimeStep` of the step before
+    (entries of frozen environments held, see `step`), `active` the bool[N] device mask of the step about to be taken; the
+    action rows of inactive environments are never read -- and freezes an environment as soon as its E-th LAST step has been
+    seen.  A frozen environment is not stepped again: it does not start episode E + 1, draws nothing from the pool and is
+    rendered from the frame cache.  Returns `EpisodeStats` of device tensors [N], accumulated on the device: episode_return
+    (float64, the rewards of the environment's active non-FIRST steps added in step order), length (those steps), episodes and
+    success (of its last LAST step).  One `.any()` synchronisation per step decides when to stop; `max_steps` bounds the steps
+    taken after the reset (None: no bound) -- environments that have not finished by then report episodes < E.
+    Afterwards every finished environment has `state()['episode'] == E` and a reset pending: the next `step()` in which it is
+    active, or `reset()`, starts its next episode."""
+    E = int(episodes_per_env)
+    if E < 1:
+      raise ValueError('run_episodes: episodes_per_env must be positive, got %d' % E)
+    N, dev = self._num_envs, self._engine.device
+    ret = torch.zeros(N, dtype=torch.float64, device=dev)
+    length = torch.zeros(N, dtype=torch.int64, device=dev)
+    episodes = torch.zeros(N, dtype=torch.int32, device=dev)
+    success = torch.zeros(N, dtype=torch.bool, device=dev)
+    ts = self.reset()
+    active = torch.ones(N, dtype=torch.bool, device=dev)
+    steps = 0
+    while max_steps is None or steps < int(max_steps):
+      ts = self.step(policy(ts, active), active=active)
+      steps += 1
+      counted = active & (ts.step_type != _abi.STEP_FIRST)
+      ret = ret + torch.where(counted, ts.reward, torch.zeros_like(ts.reward))
+      length = length + counted.to(torch.int64)
+      ended = active & (ts.step_type == _abi.STEP_LAST)
+      episodes = episodes + ended.to(torch.int32)
+      success = torch.where(ended, self._engine.success.bool(), success)
+      active = active & (episodes < E)
+      if not bool(active.any()):
+        break
+    return EpisodeStats(ret, length, episodes, success)
 
   def rollout(self, actions, keep_steps=False):
     """Scores candidate action sequences from where every environment is now, without stepping: actions is [N, M, K, A]
@@ -624,10 +686,11 @@ class EnvironmentGroups(object):
     with torch.cuda.stream(self.streams[g]):
       return self.groups[g].reset()
 
-  def step(self, g, actions):
-    """Steps group `g` on its stream; the returned tensors are valid on `self.streams[g]`."""
+  def step(self, g, actions, active=None):
+    """Steps group `g` on its stream; the returned tensors are valid on `self.streams[g]`.  `active`: the group's mask, as in
+    `BatchedEnvironment.step`."""
     with torch.cuda.stream(self.streams[g]):
-      return self.groups[g].step(actions)
+      return self.groups[g].step(actions, active=active)
 
   def sample_actions(self, g, where='host', click='uniform'):
     """`BatchedEnvironment.sample_actions` of group `g`; the device forms run on its stream.  The groups' global_env_offset
