@@ -671,6 +671,23 @@ int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream);
 int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream);
 int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream);
 
+/* Task cache.  The task's reward, success and error bits are a pure function of the sprites' positions, the episode's labels,
+ * the sprite count and the task configuration.  The handle owns one 16-byte record per environment
+ * (swb_variant_info::task_cache_bytes), on every path (tuned, painting, large frames, many sprites; with or without an
+ * observation buffer).  A step that is no reset of the environment and moves none of its sprites, bit for bit -- a missed
+ * click, a zero motion, a move clipped back onto the same value -- takes the three from the record instead of evaluating the
+ * task again; every other step evaluates and leaves the record.  The error bits come back at every such step as a fresh
+ * evaluation would raise them (the caller may have cleared `error`).  Every call other than a step that may change what the
+ * task reads makes all records stale (the pool calls, swb_copy_pool, swb_set_positions, the sprite setters, swb_load_state,
+ * swb_upload_shapes); swb_reset_all / swb_reset_envs need not: a reset step evaluates.  swb_evaluate, swb_render, rollouts and
+ * their frames neither read nor write a record.  A handle that cannot get the memory runs without a cache.  Switch of the
+ * environment, read at swb_create:
+ *   SWB_NO_TASK_CACHE  no cache: every step evaluates the task (tests, A/B runs); results are identical either way
+ * swb_task_stats: the environment-steps since swb_create -- environments that took part in a swb_step / swb_step_masked -- that
+ * reused the record / evaluated the task.  Blocking (synchronises `stream`); needs SWB_LIST_STATS at swb_create like
+ * swb_list_stats (SWB_ERR_STATE otherwise); one atomic per stepping wave. */
+int swb_task_stats(swb_handle h, int64_t* reused, int64_t* evaluated, void* stream);
+
 /* Split bands.  A batch that the band rule leaves at one band per frame, but whose resample launch is at most two rounds of
  * resident waves, ends with its last resampling wave while most tasks only copy (frame cache).  Such a handle builds its lists
  * and tables for swb_variant_info::split_bands bands and decides at every launch, on the device, which environments use them:
@@ -839,6 +856,8 @@ typedef struct swb_variant_info {
   int32_t split_bands;        /* split-bands mode (swb_split_stats): the bands a frame that resamples is cut into when its launch
                                * splits -- the count asked for until the first launch has placed them --, 0: the mode is off */
   int32_t split_pad_;
+  int64_t task_cache_bytes;   /* device memory of the task cache (swb_task_stats): 16 bytes per environment, 0 on a handle
+                               * without one */
 } swb_variant_info;
 int swb_variant(swb_handle h, swb_variant_info* out);
 const char* swb_build_id(void);

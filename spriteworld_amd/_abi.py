@@ -182,7 +182,7 @@ class SwbVariantInfo(C.Structure):
               ('n_column_groups', C.c_int32), ('run_cap', C.c_int32), ('paint_in_cover', C.c_int32),
               ('arena_units', C.c_int32), ('large_frames', C.c_int32), ('many_sprites', C.c_int32), ('reserved_', C.c_int32),
               ('run_list_bytes', C.c_int64), ('frame_cache_bytes', C.c_int64),
-              ('split_bands', C.c_int32), ('split_pad_', C.c_int32)]
+              ('split_bands', C.c_int32), ('split_pad_', C.c_int32), ('task_cache_bytes', C.c_int64)]
 
 
 FACTOR_UNIFORM_F32, FACTOR_UNIFORM_INT, FACTOR_DISCRETE = 0, 1, 2
@@ -388,6 +388,7 @@ PROTOTYPES = {
                                    _P(SwbRolloutSampledOutputs), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_list_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _h]),
+    'swb_task_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_frame_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_split_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_frame_cycles': (None, [_h, _P(C.c_int64), _h]),

@@ -155,6 +155,12 @@ struct swb_engine {
   dev_buf<uint8_t> d_frame_cache;
   int copy_cost = 0;                 // what a task that copies a column group's whole frame is filed under (SWB_COPY_COST)
   dev_buf<unsigned long long> d_frame_stats;  // SWB_LIST_STATS: what the resample tasks did (swb_frame_stats)
+  // task cache (swb_params::task_cache): one record per environment of its last task evaluation, stamped with task_epoch -- never
+  // 0, a counter of its own beside list_epoch: a step without a frame moves the list epoch and must not empty this cache.
+  // SWB_NO_TASK_CACHE (tests, A/B runs) and a failed allocation leave it out: every wave evaluates
+  dev_buf<swb_task_record> d_task_cache;
+  uint32_t task_epoch = 1;
+  dev_buf<unsigned long long> d_task_stats;   // SWB_LIST_STATS: stepping waves that reused / evaluated the task (swb_task_stats)
   // split bands (swb_params::split_bands): nbands is then the count the lists are built for, the nominal count is one
   bool split_bands = false;
   dev_buf<unsigned long long> d_split_stats;  // SWB_LIST_STATS: whole / band / whole-copy tasks (swb_split_stats)
@@ -248,6 +254,15 @@ void bump_list_epoch(swb_engine* h) {
   if (++h->list_epoch == 0u) h->list_epoch = 1u;
 }
 
+// What a task evaluation depends on -- positions, labels, sprite counts, the pool rows in use, overrides -- may have changed
+// outside a step: no record stamped before this is reused (swb_params::task_epoch), and no list is kept either.  Every call
+// site of the two says which it is: BOTH (this one), or LISTS ONLY (bump_list_epoch: the call moves or rebuilds lists and
+// leaves the state the task reads alone).  swb_reset_all and swb_reset_envs need neither for the task: a reset step evaluates.
+void bump_state_epochs(swb_engine* h) {
+  bump_list_epoch(h);
+  if (++h->task_epoch == 0u) h->task_epoch = 1u;
+}
+
 // Overflow slots for the span lists of the cover kernel: one per wave that can be resident at once (occupancy of
 // the kernel that will be launched with its LDS footprint x CUs, capped by the batch), never one per environment.
 // (fn_alt: the other build of the same family -- the one that paints the frame itself / the one that does not --, which a
@@ -277,7 +292,7 @@ int ensure_overflow_slots(swb_engine* h, kernel_fn fn, kernel_fn fn_alt, size_t 
 // never hands anything to a second kernel and reserves no lists.
 int ensure_handoff_tables(swb_engine* h, bool need_lists = true) {
   if (!h->tables_dirty && (h->d_runs || !need_lists)) return 0;
-  bump_list_epoch(h);                // (new tables, new lists: nothing written before this is kept)
+  bump_list_epoch(h);                // LISTS ONLY (new tables, new lists: nothing written before this is kept)
   swb_params& p = h->p;
   int nb = h->nbands;
   // Bands: about Ho / nb rows each; for the resample kernel the first row of a band is moved so that the number of
@@ -365,7 +380,7 @@ int drop_run_lists(swb_engine* h) {
   HIP_TRY(hipDeviceSynchronize());
   h->d_runs.release(); h->d_rhdr.release(); h->d_arena_head.release();
   h->p.runs = nullptr; h->p.rhdr = nullptr; h->p.arena_head = nullptr;
-  bump_list_epoch(h);
+  bump_list_epoch(h);                // LISTS ONLY (a trim, or a pool call that bumps both itself)
   h->lists_valid = false;
   h->tables_dirty = true;
   return 0;
@@ -423,6 +438,13 @@ swb_params bind_step(const swb_engine* h, const void* actions, const swb_outputs
   p.success = out ? out->success : nullptr;
   p.error = out ? out->error : nullptr;
   p.render_only = render_only;
+  // the task cache (swb_params::task_cache) and its counters: steps only -- h->p itself never carries them, so renders,
+  // evaluations and the rollouts' forked blocks neither read nor write a record (bind_view: nor a launch on another state)
+  if (render_only == 0) {
+    p.task_cache = h->d_task_cache.ptr;
+    p.task_stats = h->d_task_stats.ptr;
+    p.task_epoch = h->task_epoch;
+  }
   return p;
 }
 
@@ -432,6 +454,7 @@ void bind_view(swb_params* p, const swb_state_view* view) {
   if (!view) return;
   p->x = view->x; p->y = view->y; p->nspr = view->nspr; p->entry = view->entry; p->step_count = view->step_count;
   p->episode = view->episode; p->pool_base = view->pool_base; p->pool_len = view->pool_len; p->reset_next = view->reset_next;
+  p->task_cache = nullptr; p->task_stats = nullptr;
 }
 
 // Launch configuration of cover build `fn` of variant `v`: the dynamic LDS of a wave, and how the kernel finds its way in it.
@@ -521,7 +544,7 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
       h->d_ovf.release(); h->d_ovf_bitmap.release();
     }
     if (int rc = ensure_overflow_slots(h, fn_family, h->d_ov_flag ? v->fn_paint_ov : v->fn_paint, lds)) return rc;
-    bump_list_epoch(h);
+    bump_list_epoch(h);              // LISTS ONLY (new overflow slots)
     h->ovf_lds_bytes = (int)lds;
     h->ovf_fn = fn_family;
     p.ovf = h->p.ovf; p.ovf_bitmap = h->p.ovf_bitmap; p.ovf_slots = h->p.ovf_slots;
@@ -536,6 +559,7 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   // (split bands: a copy is always the whole frame)
   p.copy_cost = h->copy_cost / ((p.band_tasks && !p.split_bands) ? std::max(p.nbands, 1) : 1);
   p.split_carry = view ? 1 : 0;
+  // LISTS ONLY: the step itself keeps every task record it leaves in step with the positions it writes
   if (!p.obs && render_only == 0 && !view) bump_list_epoch(h);
   step_timer timer(h, stream);
   if (int rc = timer.begin()) return rc;
@@ -570,7 +594,7 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   // the next launch builds every list and resets every word.
   struct epoch_guard {
     swb_engine* h; bool armed = true;
-    ~epoch_guard() { if (armed) bump_list_epoch(h); }
+    ~epoch_guard() { if (armed) bump_list_epoch(h); }     // LISTS ONLY (a cover wave that ran left positions and record in step)
   } guard{h};
   if (int rc = timer.mid()) return rc;            // (a painting cover kernel is the whole step: nothing follows before end())
   if (p.obs && !p.paint_in_cover) launch_resample(0, p.N, stream);
@@ -1093,7 +1117,7 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
       h->d_step_count.fill(nullptr, p.N) || h->d_episode.fill(nullptr, p.N) || h->d_reset_next.fill(nullptr, p.N))
     return SWB_ERR_HIP;
   if (getenv("SWB_LIST_STATS")) {
-    if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 6)) return SWB_ERR_HIP;
+    if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 6) || h->d_task_stats.fill(nullptr, 2)) return SWB_ERR_HIP;
     p.list_stats = h->d_list_stats;
     p.frame_stats = h->d_frame_stats;
     if (h->split_bands) {
@@ -1113,6 +1137,18 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
       p.frame_cache = h->d_frame_cache;
     } else {
       h->d_frame_cache.ptr = nullptr;
+      (void)hipGetLastError();
+    }
+  }
+  // The task cache: 16 zeroed bytes per environment, on every path (swb_params::task_cache is bound by bind_step, for steps
+  // only).  As above: a handle that cannot have the memory runs without it, no error left behind.
+  if (!getenv("SWB_NO_TASK_CACHE")) {
+    const size_t bytes = (size_t)p.N * sizeof(swb_task_record);
+    if (hipMalloc(reinterpret_cast<void**>(&h->d_task_cache.ptr), bytes) == hipSuccess && hipMemset(h->d_task_cache.ptr, 0, bytes) == hipSuccess) {
+      h->d_task_cache.count = (size_t)p.N;
+    } else {
+      if (h->d_task_cache.ptr) (void)hipFree(h->d_task_cache.ptr);
+      h->d_task_cache.ptr = nullptr;
       (void)hipGetLastError();
     }
   }
@@ -1141,7 +1177,7 @@ int swb_destroy(swb_handle h) {
 
 int swb_upload_shapes(swb_handle h, const double* verts, const int32_t* offsets, int32_t n_shapes) {
   if (!h || !verts || !offsets) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (the task reads no shape; in doubt)
   if (n_shapes < 1 || n_shapes > SWB_MAX_SHAPES) return fail(SWB_ERR_INVALID, "n_shapes must be in [1, %d]", SWB_MAX_SHAPES);
   HIP_TRY(hipSetDevice(h->device));
   int maxv = 0;
@@ -1182,7 +1218,7 @@ int swb_upload_shapes(swb_handle h, const double* verts, const int32_t* offsets,
 int swb_upload_resample(swb_handle h, int32_t axis, int32_t out_size, int32_t ksize, const int32_t* bounds,
                         const int32_t* coeffs) {
   if (!h || !bounds || !coeffs) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_list_epoch(h);                // LISTS ONLY (resampling tables: frames, not the state)
   HIP_TRY(hipSetDevice(h->device));
   if (h->large_frames) return upload_resample_large(h, axis, out_size, ksize, bounds, coeffs);
   const swb_params& p = h->p;
@@ -1269,7 +1305,7 @@ int swb_upload_resample(swb_handle h, int32_t axis, int32_t out_size, int32_t ks
 
 int swb_set_pool(swb_handle h, const swb_pool* pool) {
   if (!h || !pool) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (a new pool: labels and rows in use)
   HIP_TRY(hipSetDevice(h->device));
   const int P = pool->n_entries, S = h->p.S, T = h->p.n_tasks, N = h->p.N;
   if (P < 1) return fail(SWB_ERR_INVALID, "pool is empty");
@@ -1336,7 +1372,7 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
 int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, const int32_t* pool_base_host,
                     const int32_t* pool_len_host, uint64_t seed, uint64_t first_entry, void* stream) {
   if (!h || !spec || !pool_base_host || !pool_len_host) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (a new pool)
   HIP_TRY(hipSetDevice(h->device));
   const int P = n_entries, S = h->p.S, N = h->p.N;
   if (P < 1) return fail(SWB_ERR_INVALID, "pool is empty");
@@ -1424,7 +1460,7 @@ int swb_sample_pool(swb_handle h, const swb_sampler* spec, int32_t n_entries, co
 
 int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (pool rows redrawn)
   if (!h->have_pool || !h->pool_sampled) return fail(SWB_ERR_STATE, "swb_sample_pool has not been called");
   if (!h->pool_uniform)
     return fail(SWB_ERR_STATE, "swb_resample_pool needs the env-major layout pool_base[n] = n * pool_len, equal pool_len");
@@ -1441,7 +1477,7 @@ int swb_resample_pool(swb_handle h, uint64_t seed, uint64_t first_entry, void* s
 int swb_sample_pool_tree(swb_handle h, const swb_tree_sampler* spec, int32_t n_entries, const int32_t* pool_base_host,
                          const int32_t* pool_len_host, uint64_t seed, uint64_t first_entry, void* stream) {
   if (!h || !spec || !pool_base_host || !pool_len_host) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (a new pool)
   HIP_TRY(hipSetDevice(h->device));
   const int P = n_entries, S = h->p.S, N = h->p.N;
   if (P < 1) return fail(SWB_ERR_INVALID, "pool is empty");
@@ -1546,7 +1582,7 @@ int swb_get_pool(swb_handle h, const swb_pool* pool) {
 
 int swb_reset_all(swb_handle h, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
-  bump_list_epoch(h);
+  bump_list_epoch(h);                // LISTS ONLY (the reset step evaluates the task and leaves a record for the new episode)
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipMemsetAsync(h->d_reset_next, 1, h->p.N, (hipStream_t)stream));
   return SWB_OK;
@@ -1901,6 +1937,17 @@ int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream) {
   return SWB_OK;
 }
 
+int swb_task_stats(swb_handle h, int64_t* reused, int64_t* evaluated, void* stream) {
+  if (!h || !reused || !evaluated) return fail(SWB_ERR_INVALID, "null argument");
+  if (!h->d_task_stats) return fail(SWB_ERR_STATE, "swb_task_stats: SWB_LIST_STATS was not set when the handle was created");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long w[2] = {0ull, 0ull};
+  HIP_TRY(hipMemcpy(w, h->d_task_stats, sizeof(w), hipMemcpyDeviceToHost));
+  *reused = (int64_t)w[0]; *evaluated = (int64_t)w[1];
+  return SWB_OK;
+}
+
 int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream) {
   if (!h || !copied || !filled || !resampled) return fail(SWB_ERR_INVALID, "null argument");
   if (!h->d_frame_stats) return fail(SWB_ERR_STATE, "swb_frame_stats: SWB_LIST_STATS was not set when the handle was created");
@@ -1992,7 +2039,7 @@ int swb_get_sprite_types(swb_handle h, int32_t env, int32_t sprite, int32_t* fla
 
 int swb_set_positions(swb_handle h, const double* x_host, const double* y_host, void* stream) {
   if (!h || !x_host || !y_host) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (positions)
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   const size_t NS = (size_t)h->p.N * h->p.S;
@@ -2079,6 +2126,9 @@ int swb_load_state(swb_handle h, const swb_snapshot* snap, int32_t C, const int3
   // builds (and resets SWB_RHDR_FRAME); the epoch stays, the others keep lists and cached frames.  A handle without headers
   // has nothing to clear: painting builds, large frames and many sprites have no lists and pass epoch 0 at every launch, and
   // headers that are not allocated yet (no launch so far, or dropped by a trim or a pool call) come back zeroed -- no stamp.
+  // The task records have no per-environment invalidation: positions, labels and counts of the loaded environments change, so
+  // the task epoch moves for all (one evaluation each at the next step) -- the list epoch still stays.
+  if (++h->task_epoch == 0u) h->task_epoch = 1u;
   uint32_t* const rhdr = h->d_rhdr ? h->d_rhdr.ptr : nullptr;
   // (the ranges may have moved between environments: swb_resample_pool's skip of live entries needs the env-major layout)
   h->pool_uniform = false;
@@ -2141,7 +2191,7 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
   if (have_angle) dst->d_p_angle.swap(t_angle);
   if (have_color) dst->d_p_color.swap(t_color);
   dst->d_pool_base.swap(t_base); dst->d_pool_len.swap(t_len);
-  bump_list_epoch(dst);
+  bump_state_epochs(dst);            // BOTH (dst plays another pool)
   dst->rollout_stale = true;
   bind_pool(dst, have_angle, have_color);
   dst->pool_entries = P;
@@ -2294,7 +2344,7 @@ int ov_store(swb_engine* h, int env, const env_override& r) {
 int swb_set_sprite_attr(swb_handle h, int32_t env, int32_t sprite, int32_t attr, double value, const double* delta,
                         const int8_t* label, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (a position, a label, or what a filter reads)
   if (!h->have_pool || !h->have_shapes) return fail(SWB_ERR_STATE, "no pool / shape table installed");
   if (env < 0 || env >= h->p.N) return fail(SWB_ERR_INVALID, "environment %d out of range", env);
   if (attr < SWB_ATTR_SHAPE || attr > SWB_ATTR_SCALE) return fail(SWB_ERR_INVALID, "unknown sprite attribute %d", attr);
@@ -2347,7 +2397,7 @@ int swb_set_sprite_attr(swb_handle h, int32_t env, int32_t sprite, int32_t attr,
 
 int swb_set_sprite_cell_labels(swb_handle h, int32_t env, int32_t sprite, const int8_t* cells, void* stream) {
   if (!h || !cells) return fail(SWB_ERR_INVALID, "null argument");
-  bump_list_epoch(h);
+  bump_state_epochs(h);              // BOTH (labels per cell)
   if (!h->keyed) return fail(SWB_ERR_INVALID, "no task of this handle keys on position");
   if (env < 0 || env >= h->p.N || sprite < 0 || sprite >= h->p.S) return fail(SWB_ERR_INVALID, "environment %d / sprite %d out of range", env, sprite);
   HIP_TRY(hipSetDevice(h->device));
@@ -2385,6 +2435,7 @@ int swb_get_sprite(swb_handle h, int32_t env, int32_t sprite, int32_t* shape, do
 
 int swb_variant(swb_handle h, swb_variant_info* out) {
   if (!h || !out) return fail(SWB_ERR_INVALID, "null argument");
+  out->task_cache_bytes = (int64_t)(h->d_task_cache.count * sizeof(swb_task_record));
   if (h->large_frames) {                 // the narrowest cover build (state phase only), then the large-frame render kernels
     const variant* v0 = &kVariants[0];
     out->nw = v0->nw; out->ncol = 1; out->vs = 0;

@@ -68,6 +68,15 @@
 #define SWB_TUNED_SPRITES 16
 #define PRECISION_BITS 22
 
+// One environment's last task evaluation (swb_params::task_cache): 16 bytes, read and written as one uint4.
+struct swb_task_record {
+  uint32_t tr_lo, tr_hi;       // the task reward, float64 bits
+  uint8_t ok, err;             // task.success; the swb_env_error bits the evaluation raised
+  uint16_t pad_;
+  uint32_t stamp;              // swb_params::task_epoch of the launch that wrote it (0: never written)
+};
+static_assert(sizeof(swb_task_record) == 16, "a task record is one 16-byte load");
+
 struct swb_params {
   // ---- config
   int32_t N, S, AA;
@@ -232,6 +241,15 @@ struct swb_params {
   // read, no task is evaluated), and its frame is drawn from the state as it is -- on the two-kernel path its wave keeps its
   // lists like any wave whose sprites did not move.  Read once per wave, in load_env_state.  (Appended last, as above.)
   const uint8_t* active;       // [N], NULL: every environment takes part (and everything but a step: renders, evaluations, rollouts)
+  // ---- task cache (finish_step; DESIGN.md section 28).  The task's reward, success and error bits are a pure function of the
+  // sprites' positions, the episode's labels, the sprite count and the task block above: a step that is no reset and moved no
+  // sprite bitwise takes them from the record the environment's last evaluation left, if that record carries `task_epoch`.  The
+  // host bumps the epoch whenever something other than a step changes what the task depends on.  Bound only for launches that
+  // step the live state (render_only == 0, no state view); the rollout kernels compile the cache out.  (Appended last, as above.)
+  swb_task_record* task_cache; // [N], NULL: the handle has none (SWB_NO_TASK_CACHE), or the launch is no step: every wave evaluates
+  uint32_t task_epoch;         // never 0: a zeroed record is stale
+  uint32_t task_pad_;
+  unsigned long long* task_stats;   // [2] stepping waves that reused / evaluated the task (SWB_LIST_STATS; else NULL)
 };
 
 // --------------------------------------------------------------------------------------------
@@ -600,14 +618,16 @@ __device__ __forceinline__ int task_clustering_wave(const swb_task& t, int pos_f
 }
 
 // task.reward + task.success incl. tasks.py:248-296 MetaAggregated; all lanes, uniform result.
+// n_tasks: swb_params::n_tasks -- or -1 from a caller that will not use the result (finish_step: no task is evaluated then,
+// nothing of the scratch but MetaAggregated's own words is touched, and what comes back is not meaningful).
 template <typename SC>
-__device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double px, double py, const int8_t* label,
+__device__ __forceinline__ int eval_task_wave(const swb_params& p, int n_tasks, int n, double px, double py, const int8_t* label,
                                               SC* sc, double* reward, int* success) {
   const int l = lane_id();
   int err = 0;
   double r0 = 0.0;
   int ok0 = 0;
-  for (int t = 0; t < p.n_tasks; ++t) {
+  for (int t = 0; t < n_tasks; ++t) {
     const swb_task& tk = p.tasks[t];
     const int8_t* lab = label + t * p.S;
     double r = 0.0;
@@ -622,7 +642,7 @@ __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double
   const double* r = sc->tr;
   const int* ok = sc->tok;
   int succ = (p.meta_termination == SWB_TERM_ALL);
-  for (int t = 0; t < p.n_tasks; ++t) succ = (p.meta_termination == SWB_TERM_ALL) ? (succ && ok[t]) : (succ || ok[t]);
+  for (int t = 0; t < n_tasks; ++t) succ = (p.meta_termination == SWB_TERM_ALL) ? (succ && ok[t]) : (succ || ok[t]);
   double agg;
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   if (p.meta_aggregator == SWB_AGG_SUM || p.meta_aggregator == SWB_AGG_MEAN) {
@@ -631,22 +651,22 @@ __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n, double
     double v[SWB_MAX_TASKS];
 #pragma unroll
     for (int t = 0; t < SWB_MAX_TASKS; ++t) {
-      const double x = (t < p.n_tasks) ? r[t] : 0.0;
+      const double x = (t < n_tasks) ? r[t] : 0.0;
       const bool isn = (x != x);
       v[t] = isn ? 0.0 : x;
-      cnt += (t < p.n_tasks) && !isn;
+      cnt += (t < n_tasks) && !isn;
     }
-    if (p.n_tasks < 8) {
+    if (n_tasks < 8) {
       agg = -0.0;
 #pragma unroll
-      for (int t = 0; t < SWB_MAX_TASKS; ++t) if (t < p.n_tasks) agg = __dadd_rn(agg, v[t]);
+      for (int t = 0; t < SWB_MAX_TASKS; ++t) if (t < n_tasks) agg = __dadd_rn(agg, v[t]);
     } else {
       agg = __dadd_rn(__dadd_rn(__dadd_rn(v[0], v[1]), __dadd_rn(v[2], v[3])), __dadd_rn(__dadd_rn(v[4], v[5]), __dadd_rn(v[6], v[7])));
     }
     if (p.meta_aggregator == SWB_AGG_MEAN) agg = __ddiv_rn(agg, (double)cnt);
   } else {
     agg = qnan;
-    for (int t = 0; t < p.n_tasks; ++t) {
+    for (int t = 0; t < n_tasks; ++t) {
       if (r[t] != r[t]) continue;
       if (agg != agg) agg = r[t];
       else if (p.meta_aggregator == SWB_AGG_MAX ? (r[t] > agg) : (r[t] < agg)) agg = r[t];
@@ -838,9 +858,30 @@ __device__ __forceinline__ step_cost act_and_move(const swb_params& p, int env, 
   return step_cost{cost, cost_f32, cost_is_f32, step_count, changed};
 }
 
+// The environment's task record (swb_params::task_cache) joins the state phase's first round of loads -- its address depends on
+// `env` alone -- and waits in the scratch's `pres` words, idle until a clustering is evaluated, not in registers across the hit
+// tests.  A plain load: this wave may write the record again in finish_step.  Two halves around load_env_state: the load is issued
+// before the state's own, the word goes to LDS behind them -- written where it is loaded, the LDS store waits for the load with
+// nothing else in flight, one more memory round trip at the head of every wave (measured: +1.1 us on a single-round launch).
+__device__ __forceinline__ uint32_t load_task_record(const swb_params& p, int env) {
+  const int l = lane_id();
+  uint32_t w = 0u;                                      // lane l < 4: word l of the record
+  if (p.task_cache != nullptr && l < 4) w = reinterpret_cast<const uint32_t*>(p.task_cache)[4 * (size_t)env + l];
+  return w;
+}
+template <typename SC>
+__device__ __forceinline__ void park_task_record(const swb_params& p, uint32_t w, SC* tscratch) {
+  static_assert(sizeof(SC::pres) == sizeof(swb_task_record), "the record waits in task_scratch::pres");
+  if (p.task_cache != nullptr && lane_id() < 4) tscratch->pres[lane_id()] = w;
+}
+
 // Task reward / success (spread over the lanes), out-of-frame, termination; the outputs of the step.  Returns the error
 // bits of the environment (lane 0; the caller stores them).
-template <bool OV, typename SC>
+// CACHE (swb_params::task_cache; the caller has run stage_task_record): a step that is no reset and moved no sprite takes the
+// task's reward, success and error bits from the environment's record when it carries the launch's epoch -- the error bits as
+// a fresh evaluation would return them (p.error is sticky and the caller may have cleared it); every other step evaluates and
+// leaves the record.  CACHE = false: a caller on forked parameter blocks (the rollout kernels) compiles all of it out.
+template <bool OV, bool CACHE = true, typename SC>
 __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, const env_state& es, const step_cost& c, SC* tscratch) {
   const int l = lane_id(), S = p.S, n = es.n;
   const double px = es.px, py = es.py;
@@ -866,8 +907,41 @@ __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, co
   const bool oof_l = (l < n) && !(px >= 0. && py >= 0. && px <= 1. && py <= 1.);   // sprite.py:135-138
   const int oof = __ballot(oof_l) != 0ull;
   double tr = 0.0; int ok = 0;
-  const int terr = eval_task_wave(p, n, px, py, tscratch->labels, tscratch, &tr, &ok);
+  // (A wave that reuses its record runs the evaluation over a task count of -1 instead of branching around it: the task loop
+  // has a run-time trip count already, so the kernel's control flow -- and with it the register allocation of the cover builds,
+  // which a branch around the whole evaluation cost two spilled VGPRs each -- stays what it was.  No fence is needed between
+  // the stamp's read and an evaluation's writes to `pres`: the loop is entered on a count that depends on the value read.)
+  int n_tasks = p.n_tasks;                              // (wave-uniform; -1: the record is reused)
+  if constexpr (CACHE) {
+    if (p.task_cache != nullptr) {
+      // (every lane reads the same word and decides the same; the decision goes through a ballot so that the compiler KNOWS the
+      // count is uniform -- `changed` and `first` are set under branches it takes for divergent -- and the task loop stays scalar)
+      const uint32_t stamp = tscratch->pres[3];
+      if (__ballot(stamp != p.task_epoch || c.changed || es.first) == 0ull) n_tasks = -1;
+    }
+  }
+  int terr = eval_task_wave(p, n_tasks, n, px, py, tscratch->labels, tscratch, &tr, &ok);
+  const bool reuse = CACHE && n_tasks < 0;
+  if constexpr (CACHE) {
+    if (reuse) {                                        // (no task ran: `pres` still holds the record)
+      const uint32_t w0 = tscratch->pres[0], w1 = tscratch->pres[1], w2 = tscratch->pres[2];
+      tr = __longlong_as_double((long long)(((unsigned long long)w1 << 32) | w0));
+      ok = (int)(w2 & 0xffu);
+      terr = (int)((w2 >> 8) & 0xffu);
+    }
+  }
   if (l == 0) {
+    if constexpr (CACHE) {
+      if (p.task_cache != nullptr && !reuse) {          // (one 16-byte vector store; only where the task was in fact evaluated)
+        const unsigned long long trb = (unsigned long long)__double_as_longlong(tr);
+        uint4 rec;
+        rec.x = (uint32_t)trb; rec.y = (uint32_t)(trb >> 32);
+        rec.z = (uint32_t)(ok & 0xff) | ((uint32_t)(terr & 0xff) << 8);
+        rec.w = p.task_epoch;
+        *reinterpret_cast<uint4*>(&p.task_cache[env]) = rec;
+      }
+      if (p.task_stats != nullptr) atomicAdd(&p.task_stats[reuse ? 0 : 1], 1ull);
+    }
     if (p.success) p.success[env] = (uint8_t)ok;
     if (p.render_only) {
       // (swb_evaluate: environment.py:80-81 success() of the current sprites, no time step)
@@ -2105,7 +2179,9 @@ swb_cover_kernel(const swb_params p) {
   if constexpr (!PAINT) {
     if (p.list_epoch != 0u && l <= SWB_MAX_CG + 2) L->outrow[l] = p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_COST + l];
   }
+  const uint32_t task_rec_l = load_task_record(p, env);
   env_state es = load_env_state<OV>(p, env, tscratch);
+  park_task_record(p, task_rec_l, tscratch);
   const int n = es.n, nv_l = es.nv_l;
   const double scale_l = es.scale_l;
   uint32_t rgb_reg = 0u;                                // lane s: fill colour of sprite s
@@ -3155,7 +3231,9 @@ swb_ms_state_kernel(const swb_params p) {
   swb_ms_lds* M = reinterpret_cast<swb_ms_lds*>(smem);
   task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
   double2* cpath = M->path;
+  const uint32_t task_rec_l = load_task_record(p, env);
   env_state es = load_env_state<OV>(p, env, tscratch);
+  park_task_record(p, task_rec_l, tscratch);
   // sprite.py:113-115 contains_point of sprite s2 (wave-uniform): its centred path into LDS, lanes = vertices, then the
   // even-odd test of contains_point_wave -- the values P1a of the cover kernel computes for the same sprite
   auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
@@ -3437,7 +3515,7 @@ swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep,
       return contains_point_wave(cpath, nv, tx, ty);
     };
     const step_cost sc = act_and_move(q, v, es, hit);
-    err |= finish_step<false>(q, v, es, sc, tscratch);
+    err |= finish_step<false, false>(q, v, es, sc, tscratch);       // (forked parameter blocks: no task cache, compiled out)
     if constexpr (KEEP) {
       const size_t slot = (size_t)k * gridDim.x + v;    // (one workgroup per virtual environment: gridDim.x = N * M)
       ep += es.first ? 1 : 0;

@@ -445,6 +445,14 @@ class Engine(object):
     self._check(self.lib.swb_list_stats(self._h, C.byref(kept), C.byref(built), self._stream()))
     return kept.value, built.value
 
+  def task_stats(self):
+    """(reused, evaluated): the environment-steps -- environments that took part in a step -- that took the task's reward,
+    success and error bits from the engine's task cache / evaluated the task, since the engine was created (swb_task_stats;
+    blocking).  Needs SWB_LIST_STATS like list_stats."""
+    reused, evaluated = C.c_int64(0), C.c_int64(0)
+    self._check(self.lib.swb_task_stats(self._h, C.byref(reused), C.byref(evaluated), self._stream()))
+    return reused.value, evaluated.value
+
   def frame_stats(self):
     """(copied, filled, resampled): the tasks of the resample kernel -- one per environment, column group and band task of a
     rendering launch -- that copied their part of the frame from the engine's frame cache / resampled it and left it in the
