@@ -442,7 +442,8 @@ int swb_step(swb_handle h, const void* actions_dev, const swb_outputs* out, void
  *     environment's last active step left there (a held reward must not be summed twice);
  *   - out->obs[n] IS written, with the frame of the environment's state as it is -- byte for byte what swb_render gives.  On the
  *     two-kernel path the environment's cover wave keeps its run lists and its frame is copied from the frame cache like that of
- *     any environment whose sprites did not move (swb_list_stats counts it as kept, swb_frame_stats as filled, then copied);
+ *     any environment whose sprites did not move -- by the copy workgroups of the cover launch, which know nothing of the mask
+ *     (swb_list_stats counts it as kept, swb_frame_stats as filled, then copied);
  *     painting builds, large frames and many-sprite handles draw the unchanged state again.
  * One case is unspecified: the frame of an environment that has had no FIRST step since its pool was installed (swb_set_pool,
  * swb_sample_pool, swb_copy_pool) and is inactive -- it has no sprites of its own yet.
@@ -659,17 +660,29 @@ int swb_list_stats(swb_handle h, int64_t* kept, int64_t* built, void* stream);
  * tables.  A handle whose frames come from the resample kernel (anti_aliasing > 1, not the large-frame or many-sprite path, not
  * SWB_NO_KEEP_LISTS) owns one frame per environment of device memory (swb_variant_info::frame_cache_bytes: 12 KB per environment
  * at 64x64, 49 KB at 128x128).  The first launch that keeps an environment's lists leaves its frame there as well; every
- * further launch that keeps them copies the caller's frame from it instead of resampling the lists again.  The caller's buffer
+ * further launch that keeps them copies the caller's frame from it instead of resampling the lists again.  The copies are made
+ * in the COVER launch, speculatively: a rendering launch on the live state has one more workgroup per (environment, column
+ * group), which copies the cached frame of every environment whose cache may hold it before it is known whether the environment
+ * keeps its lists in this launch -- beside the waves that build lists, while the memory system is idle.  An environment that
+ * keeps files no task for the resample kernel; one that builds, or keeps for the first time, has its frame overwritten in full
+ * by the resample kernel, one launch boundary later.  (A handle without cost order -- SWB_NO_COST_ORDER -- copies in the
+ * resample kernel as before.)  The caller's buffer
  * is written in full at every rendering launch either way and is never read back across launches: it may be another buffer at
  * every step, and the caller may do with it what it likes.  Whatever makes the lists stale (see above) makes the cache stale.
- * A handle that cannot get the memory runs without a cache.  Switch of the environment, read at swb_create:
+ * A handle that cannot get the memory runs without a cache.  Switches of the environment, read at swb_create:
  *   SWB_NO_FRAME_CACHE  no cache: every wave resamples (tests, A/B runs); results are identical either way
- * swb_frame_stats: the tasks of the resample kernel -- one per (environment, column group[, band]) and launch -- since
- * swb_create that copied from the cache / resampled and filled it / only resampled.  Blocking; needs SWB_LIST_STATS like
- * swb_list_stats.  swb_frame_cycles (measurement): out3 = wave cycles of the copying tasks, of all others, and the list bytes
- * the others walked. */
+ *   SWB_SPEC_COPY       `behind` (the default): the copy workgroups stand behind the cover workgroups; `first` (tests): in
+ *                       front of them, the order in which every copy workgroup sees the word of the previous launch.  Results
+ *                       are identical either way; any other value is SWB_ERR_INVALID
+ * swb_frame_stats: frames taken from the cache, counted as the tasks of the resample kernel that would have copied them -- one
+ * per (environment, column group[, band]) and launch -- / tasks of the resample kernel that resampled and filled the cache /
+ * only resampled, since swb_create.  Blocking; needs SWB_LIST_STATS like
+ * swb_list_stats.  swb_frame_cycles (measurement): out3 = wave cycles of the copy workgroups that copied, of the resample
+ * kernel's tasks, and the list bytes those walked.  swb_spec_copy_stats (measurement): the copy workgroups -- one per
+ * (environment, column group) and launch -- that copied; those whose environment then built or filled are the wasted copies. */
 int swb_frame_stats(swb_handle h, int64_t* copied, int64_t* filled, int64_t* resampled, void* stream);
 int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream);
+int swb_spec_copy_stats(swb_handle h, int64_t* copy_groups, void* stream);
 
 /* Task cache.  The task's reward, success and error bits are a pure function of the sprites' positions, the episode's labels,
  * the sprite count and the task configuration.  The handle owns one 16-byte record per environment
@@ -691,7 +704,8 @@ int swb_task_stats(swb_handle h, int64_t* reused, int64_t* evaluated, void* stre
 /* Split bands.  A batch that the band rule leaves at one band per frame, but whose resample launch is at most two rounds of
  * resident waves, ends with its last resampling wave while most tasks only copy (frame cache).  Such a handle builds its lists
  * and tables for swb_variant_info::split_bands bands and decides at every launch, on the device, which environments use them:
- * one that copies files ONE whole task per column group; one that resamples or fills files its band tasks when the previous
+ * one whose frame is copied files no task (the cover launch's copy workgroups copied its whole rows: one whole copy per column
+ * group); one that resamples or fills files its band tasks when the previous
  * launch had at most SWB_SPLIT_WHEN frames that resampled or filled, else one whole task that walks the whole list.  Results
  * never depend on it.  swb_variant_info::n_bands keeps reporting the nominal 1.  Switches of the environment, read at swb_create:
  *   SWB_SPLIT_BANDS=n  0: never the mode; n >= 2: the mode with n bands at any batch size (tests, A/B runs)
@@ -701,7 +715,7 @@ int swb_task_stats(swb_handle h, int64_t* reused, int64_t* evaluated, void* stre
  * Not under SWB_BANDS, SWB_NO_FRAME_CACHE, SWB_NO_KEEP_LISTS, SWB_NO_COST_ORDER, anti_aliasing = 1, the large-frame paths.
  * swb_frame_stats keeps counting frames -- (environment, column group) pairs -- on such a handle, not waves.
  * swb_split_stats: the tasks of the resample kernel since swb_create that were whole and resampled or filled / band tasks /
- * whole and copied.  Blocking; needs SWB_LIST_STATS; SWB_ERR_STATE on a handle that is not in the mode. */
+ * the whole copies of kept frames (one per column group, counted by the keeping wave).  Blocking; needs SWB_LIST_STATS; SWB_ERR_STATE on a handle that is not in the mode. */
 int swb_split_stats(swb_handle h, int64_t* whole, int64_t* bands, int64_t* whole_copies, void* stream);
 
 /* SpriteFactors observation (renderers/handcrafted.py:29-82): factors_dev f64[N,S,10] in

@@ -392,6 +392,7 @@ PROTOTYPES = {
     'swb_frame_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_split_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_frame_cycles': (None, [_h, _P(C.c_int64), _h]),
+    'swb_spec_copy_stats': (None, [_h, _P(C.c_int64), _h]),
     'swb_factors': (None, [_h, _p, _h]),
     'swb_get_env_state': (None, [_h, _i32, _p, _h]),
     'swb_get_sprite_types': (None, [_h, _i32, _i32, _P(_i32), _h]),

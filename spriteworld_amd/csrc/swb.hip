@@ -153,8 +153,8 @@ struct swb_engine {
   // waves of an environment whose lists were kept write the caller's frame.  Only on handles whose frames come from
   // swb_resample_kernel under a live list epoch; SWB_NO_FRAME_CACHE (tests, A/B runs) and a failed allocation leave it out
   dev_buf<uint8_t> d_frame_cache;
-  int copy_cost = 0;                 // what a task that copies a column group's whole frame is filed under (SWB_COPY_COST)
-  dev_buf<unsigned long long> d_frame_stats;  // SWB_LIST_STATS: what the resample tasks did (swb_frame_stats)
+  int spec_copy = 1;                 // where the cover launch's copy workgroups stand (swb_params::spec_copy): 1 behind, 2 first (SWB_SPEC_COPY)
+  dev_buf<unsigned long long> d_frame_stats;  // SWB_LIST_STATS: frames copied, tasks that filled / resampled (swb_frame_stats)
   // task cache (swb_params::task_cache): one record per environment of its last task evaluation, stamped with task_epoch -- never
   // 0, a counter of its own beside list_epoch: a step without a frame moves the list epoch and must not empty this cache.
   // SWB_NO_TASK_CACHE (tests, A/B runs) and a failed allocation leave it out: every wave evaluates
@@ -555,9 +555,11 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   p.list_epoch = (view || !p.obs || paint || !p.rhdr || h->no_keep_lists) ? 0u : h->list_epoch;
   // (the frame cache's mover takes 16 bytes per lane where the caller's buffer and every row segment of it start on 16)
   p.obs_aligned16 = (p.obs && (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0 && (p.Wo & 15) == 0) ? 1 : 0;
-  // (a band task copies its band's rows only: measured, 465 units for a whole frame, 67 for one band of eight)
-  // (split bands: a copy is always the whole frame)
-  p.copy_cost = h->copy_cost / ((p.band_tasks && !p.split_bands) ? std::max(p.nbands, 1) : 1);
+  // Speculative copies (swb_params::spec_copy): a rendering launch on the live state of a handle with a
+  // frame cache that files its tasks by cost grows its cover grid by one copy workgroup per (environment, column group).  State
+  // views, epoch-0 launches, the painting builds and handles without a cache launch the grid they always launched; so does a
+  // handle without cost order, whose resample grid has a wave for every environment: there that wave copies, as before.
+  p.spec_copy = (p.obs && p.frame_cache && p.list_epoch != 0u && !paint && p.cost_cnt) ? h->spec_copy : 0;
   p.split_carry = view ? 1 : 0;
   // LISTS ONLY: the step itself keeps every task record it leaves in step with the positions it writes
   if (!p.obs && render_only == 0 && !view) bump_list_epoch(h);
@@ -577,8 +579,10 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
     if (p.N > 2 * slots) p.prio_levels &= ~2;          // (cover waves' priorities: measured +1.3 % at three rounds of waves)
   }
   // (cost-ordered: block b serves rank b / 8 of shard b % 8; a shard holds up to cost_cap environments)
+  // (N < 2^24 where tasks are filed by cost, ncg <= 4: the grid with the copy workgroups stays below 2^27)
   auto launch_cover = [&](int e0, int e1) {
-    hipLaunchKernelGGL(fn, dim3(e1 - e0), dim3(SWB_WAVE), lds, stream, p);
+    const unsigned copy_groups = p.spec_copy ? (unsigned)(e1 - e0) * (unsigned)p.ncg : 0u;
+    hipLaunchKernelGGL(fn, dim3((unsigned)(e1 - e0) + copy_groups), dim3(SWB_WAVE), lds, stream, p);
   };
   auto launch_resample = [&](int e0, int e1, hipStream_t st) {
     const int blocks_x = p.cost_cnt ? SWB_COST_SHARDS * ((p.cost_cap + SWB_RS_WAVES_PER_BLOCK - 1) / SWB_RS_WAVES_PER_BLOCK)
@@ -1117,7 +1121,7 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
       h->d_step_count.fill(nullptr, p.N) || h->d_episode.fill(nullptr, p.N) || h->d_reset_next.fill(nullptr, p.N))
     return SWB_ERR_HIP;
   if (getenv("SWB_LIST_STATS")) {
-    if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 6) || h->d_task_stats.fill(nullptr, 2)) return SWB_ERR_HIP;
+    if (h->d_list_stats.fill(nullptr, 2) || h->d_frame_stats.fill(nullptr, 7) || h->d_task_stats.fill(nullptr, 2)) return SWB_ERR_HIP;
     p.list_stats = h->d_list_stats;
     p.frame_stats = h->d_frame_stats;
     if (h->split_bands) {
@@ -1128,8 +1132,12 @@ int swb_create(const swb_config* cfg, int device, swb_handle* out) {
   // The frame cache: N frames, for the handles whose frames the resample kernel computes from lists that can be kept -- not the
   // fill kernel and the painting builds (anti_aliasing = 1), not the large-frame and many-sprite paths, not SWB_NO_KEEP_LISTS.
   // A handle that cannot have the memory runs without it (every wave resamples, as before): no error, and none left behind.
-  h->copy_cost = h->split_bands ? SWB_SPLIT_COPY_COST : SWB_COPY_COST;
-  if (const char* x = getenv("SWB_COPY_COST")) h->copy_cost = std::max(0, atoi(x));      // A/B runs
+  // SWB_SPEC_COPY (tests): `first` puts the cover launch's copy workgroups in front of the state workgroups -- the order in which
+  // every one of them reads the word the previous launch left; `behind` is the default
+  if (const char* x = getenv("SWB_SPEC_COPY")) {
+    if (!strcmp(x, "first")) h->spec_copy = 2;
+    else if (strcmp(x, "behind")) return fail(SWB_ERR_INVALID, "SWB_SPEC_COPY must be `behind` or `first`, not `%s`", x);
+  }
   if (p.AA != 1 && !h->large_frames && !h->no_keep_lists && !getenv("SWB_NO_FRAME_CACHE")) {
     const size_t bytes = (size_t)p.N * p.Wo * p.Ho * 3;
     if (hipMalloc(reinterpret_cast<void**>(&h->d_frame_cache.ptr), bytes) == hipSuccess) {
@@ -1979,6 +1987,17 @@ int swb_frame_cycles(swb_handle h, int64_t* out3, void* stream) {
   unsigned long long w[3] = {0ull, 0ull, 0ull};
   HIP_TRY(hipMemcpy(w, h->d_frame_stats + 3, sizeof(w), hipMemcpyDeviceToHost));
   for (int i = 0; i < 3; ++i) out3[i] = (int64_t)w[i];
+  return SWB_OK;
+}
+
+int swb_spec_copy_stats(swb_handle h, int64_t* copy_groups, void* stream) {
+  if (!h || !copy_groups) return fail(SWB_ERR_INVALID, "null argument");
+  if (!h->d_frame_stats) return fail(SWB_ERR_STATE, "swb_spec_copy_stats: SWB_LIST_STATS was not set when the handle was created");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long w = 0ull;
+  HIP_TRY(hipMemcpy(&w, h->d_frame_stats + 6, sizeof(w), hipMemcpyDeviceToHost));
+  *copy_groups = (int64_t)w;
   return SWB_OK;
 }
 

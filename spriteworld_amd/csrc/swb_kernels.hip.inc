@@ -221,11 +221,14 @@ struct swb_params {
   // would compute is the one they computed at the previous launch.  The engine keeps its own copy of every environment's last
   // frame, laid out like `obs`; the header word SWB_RHDR_FRAME says what the resample waves of an environment do with it.
   // The caller's buffer is written in full at every launch all the same -- from the copy instead of from the lists.
+  // The copies are made in the COVER launch, speculatively (spec_copy; DESIGN.md section 29): one more workgroup per
+  // (environment, column group) copies the cached frame of every environment whose word is not 0, beside the waves that build.
   uint8_t* frame_cache;        // [N][Ho][Wo][3], NULL: the handle has none (every wave resamples)
-  unsigned long long* frame_stats;  // [6] resample tasks that copied / filled / resampled, then the wave cycles of the copying
-                                    // tasks, of the others, and the list bytes of the others (SWB_LIST_STATS; else NULL)
+  unsigned long long* frame_stats;  // [7] frames taken from the cache (counted as the tasks that copied them were) / resample tasks that
+                                    // filled / resampled, then the wave cycles of the copies, of the others, the list bytes of the
+                                    // others, and the copy workgroups that copied (SWB_LIST_STATS; else NULL)
   int32_t obs_aligned16;       // `obs` and every row segment of a column group start on 16 bytes: the copy moves 16 bytes per lane
-  int32_t copy_cost;           // the cost a task that copies is filed under (SWB_COPY_COST, over the bands of a band task)
+  int32_t spec_copy;           // the cover grid holds N * ncg copy workgroups: 1 behind the N cover workgroups, 2 in front (SWB_SPEC_COPY); 0 none
   // ---- split bands (DESIGN.md section 26): lists and tables are built for nbands bands and band_tasks is on, but an environment
   // files its nbands band tasks only when it resamples or fills AND the launch's decision word (SWB_COST_WORD_SPLIT) says split;
   // otherwise -- and always when its frame is copied -- it files ONE task per column group with SWB_TASK_WHOLE set, which takes
@@ -1773,11 +1776,12 @@ __device__ __forceinline__ void cost_housekeeping(const swb_params& p, int shard
 // among the waves beyond it (a sharded maximum those waves keep); log2(16 / (highest bucket used + 1)) narrower when
 // everything fitted in the lower third.  Launches 0 and 1 file with the initial 2^12 cycles, launch 2 with the right width
 // (measured before, one step of +-1 per launch: 12 sprites at 128x128 needed 2^16 and reached it -- and its order -- at launch 7).
-__device__ __forceinline__ void cover_cost_housekeeping(const swb_params& p, int prev, int cur, int next) {
+// `block`: the workgroup's index among the launch's state workgroups (the cover kernel's grid may hold copy workgroups as well).
+__device__ __forceinline__ void cover_cost_housekeeping(const swb_params& p, uint32_t block, int prev, int cur, int next) {
   const int l = lane_id();
-  if (blockIdx.x < SWB_COST_SHARDS && l < SWB_COST_BUCKETS) p.cost_cnt[cost_row1(next, (int)blockIdx.x) + l] = 0u;
-  if (blockIdx.x < SWB_COST_SHARDS && l == 0) p.cost_cnt[SWB_COST_WORD_COVER_MAX(next, (int)blockIdx.x)] = 0u;
-  if (blockIdx.x == 0) {
+  if (block < SWB_COST_SHARDS && l < SWB_COST_BUCKETS) p.cost_cnt[cost_row1(next, (int)block) + l] = 0u;
+  if (block < SWB_COST_SHARDS && l == 0) p.cost_cnt[SWB_COST_WORD_COVER_MAX(next, (int)block)] = 0u;
+  if (block == 0) {
     int c = 0;
     if (l < SWB_COST_BUCKETS)
       for (int sh = 0; sh < SWB_COST_SHARDS; ++sh) c += (int)p.cost_cnt[cost_row1(prev, sh) + l];
@@ -1830,19 +1834,11 @@ __device__ __forceinline__ int dealt_block(const swb_params& p, int j, int block
 #define SWB_RHDR_CYCLES (SWB_RHDR_STAMP + 1)
 // ... and the state of the environment's frame in the engine's cache (swb_params::frame_cache), written by the cover wave alone:
 // 0 the cache does not hold it (the wave BUILT its lists, or the handle has no cache), 1 the resample waves of this launch
-// leave it there (the first launch that kept the lists), 2 it is there: they copy it.  A wave that keeps writes min(old + 1, 2).
+// leave it there (the first launch that kept the lists), 2 it is there: the frame is a copy of it.  A wave that keeps writes
+// min(old + 1, 2).  The copy workgroups of the cover launch (swb_params::spec_copy) read the word while that wave may be writing it.
 #define SWB_RHDR_FRAME (SWB_RHDR_CYCLES + 1)
-// What a task that copies a column group's whole frame is filed under for the order of the resample launch (a band task: that
-// over the number of bands, swb.hip).  Measured on the headline workload with the wave clocks of swb_frame_cycles
-// (profiles/r18_frame_cache.md section 4): a copying wave lives 307 743 cycles beside its seven neighbours, a resampling wave
-// 441 692 for a list of 1 336 bytes = 668 units of cost, that is 661 cycles per unit: 307 743 / 661 = 465.  (1 024 environments
-// in 8 bands, every band a task: 194 248 cycles against 2 908 per unit = 67, an eighth of it.)  Swept from 64 to 1 500: the
-// kernel is flat from 64 to 700 and 7 % longer from 1 000 on, where copies stand in front of the tasks that resample.
-#define SWB_COPY_COST 460
-// Split bands (swb_params::split_bands): the bands a changed frame is cut into, and what a whole-frame copy is filed under there --
-// below the cost of a band of the mean list (about 220), so that no copy stands in front of a task that resamples.
+// Split bands (swb_params::split_bands): the bands a changed frame is cut into.
 #define SWB_SPLIT_BANDS_DEFAULT 8
-#define SWB_SPLIT_COPY_COST 64
 #define SWB_RHDR_DWORDS (SWB_RHDR_STAMP + 4)
 #define SWB_BST_STRIDE (SWB_MAX_BANDS + 1)   // band starts of a list + its end, in LDS (swb_params::band_tasks: see emit_runs)
 __device__ __forceinline__ int run_units(int spans) { return spans <= 1 ? 1 : 2 + (spans > 3 ? (spans - 2) >> 1 : 0); }
@@ -2078,6 +2074,67 @@ __device__ __forceinline__ void emit_runs(const swb_params& p, const uint32_t* s
     err |= SWB_ENV_ERR_SPAN_OVERFLOW;                                                            \
   }
 
+// The frame cache's mover (swb_params::frame_cache): `rows` row segments of `seg_bytes` bytes, `row_bytes` apart, from src to dst
+// at the same offsets -- a wave's rectangle of the frame, which lies alike in the caller's buffer and in the cache.  Lanes take
+// consecutive chunks of T (16 bytes where both sides are aligned, else a dword: the same bytes either way), BATCH of
+// them loaded before the first is stored -- a copying wave does nothing else, so the loads in flight are its whole latency hiding.
+template <typename T, int BATCH>
+__device__ __forceinline__ void copy_frame_rect_as(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows) {
+  const int l = lane_id();
+  const int cpr = (int)(seg_bytes / (uint32_t)sizeof(T)), total = rows * cpr;      // chunks per row segment (uniform), in all
+  const int step_rows = 64 / cpr, step_cols = 64 - step_rows * cpr;               // what 64 chunks further means
+  int row = l / cpr, col = l - row * cpr;
+  for (int base = 0; base < total; base += 64 * BATCH) {
+    T v[BATCH];
+    uint32_t off[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      off[j] = (uint32_t)row * row_bytes + (uint32_t)col * (uint32_t)sizeof(T);
+      if (base + 64 * j + l < total) v[j] = *reinterpret_cast<const T*>(src + off[j]);
+      row += step_rows; col += step_cols;
+      if (col >= cpr) { col -= cpr; ++row; }
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j)
+      if (base + 64 * j + l < total) *reinterpret_cast<T*>(dst + off[j]) = v[j];
+  }
+}
+typedef uint32_t swb_c16 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void copy_frame_rect(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows, bool aligned16) {
+  if (aligned16) copy_frame_rect_as<swb_c16, 6>(src, dst, row_bytes, seg_bytes, rows);
+  else copy_frame_rect_as<uint32_t, 8>(src, dst, row_bytes, seg_bytes, rows);
+}
+
+// --------------------------------------------------------------------------------------------
+// A COPY workgroup of the cover launch (swb_params::spec_copy; DESIGN.md section 29): copy workgroup c serves column group
+// c % ncg of environment c / ncg -- the plain index, never the cost order.  It copies the whole rows of its column group from the
+// frame cache to the caller's buffer if the environment's header says the cache may hold its frame (SWB_RHDR_FRAME != 0),
+// BEFORE anyone knows whether the environment keeps its lists in this launch: the copies run beside the few waves that build,
+// while the memory system has nothing else to do, and the resample launch is left with the frames that changed.
+//
+// The word is read with one plain load while the environment's own cover wave -- its only writer during the launch -- may be
+// writing it: the load returns the value the previous launch left or the new one, and either is right.
+//   old -> new   the cover wave      this workgroup                     why the frame is right
+//   1, 2 -> 2    kept                reads 1 or 2: copies               the cache holds the frame since the launch that wrote 1; the
+//                                                                       wave files no resample task: the ONE case whose frame is the copy
+//   0 -> 1       kept, fill          reads 0: nothing; 1: stale bytes   the resample waves rewrite every byte, and fill the cache
+//   any -> 0     built               may copy                           the resample waves rewrite every byte
+// Nothing writes the cache during the cover launch, and the launch boundary orders these stores before those of the resample
+// launch.  No wave waits for another: no flag, no poll, no fence.  The workgroup touches no LDS, no cost table and no dispatch
+// word, and stays at priority 0.
+// --------------------------------------------------------------------------------------------
+__device__ __forceinline__ void spec_copy_group(const swb_params& p, uint32_t c) {
+  const uint32_t env = p.ncg == 1 ? c : c / (uint32_t)p.ncg, g = c - env * (uint32_t)p.ncg;
+  if (p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_FRAME] == 0u) return;
+  const uint32_t cycles0 = p.frame_stats ? (uint32_t)__builtin_amdgcn_s_memtime() : 0u;
+  const size_t off = (size_t)env * p.Wo * p.Ho * 3 + 192u * g;
+  copy_frame_rect(p.frame_cache + off, p.obs + off, 3u * (uint32_t)p.Wo, 3u * (uint32_t)min(64, p.Wo - 64 * (int)g), p.Ho, p.obs_aligned16 != 0);
+  if (p.frame_stats && lane_id() == 0) {
+    atomicAdd(&p.frame_stats[3], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memtime() - cycles0));
+    atomicAdd(&p.frame_stats[6], 1ull);
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // Kernel 1 of a step, "cover": P0 state, P1 geometry, P2 coverage -> run lists.  One wave = one environment.
 // --------------------------------------------------------------------------------------------
@@ -2091,10 +2148,21 @@ __global__ void __launch_bounds__(SWB_WAVE, SWB_COVER_WAVES(NW))
 swb_cover_kernel(const swb_params p) {
   static_assert(!PAINT || NW == 2, "painting in the cover kernel: images of up to 64 columns at anti_aliasing = 1");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // The copy workgroups of a launch with a frame cache (swb_params::spec_copy, never in the painting builds): behind the N
+  // state workgroups, or (tests) in front of them.  `block` is the workgroup's index among the state workgroups.
+  uint32_t block = blockIdx.x;
+  if constexpr (!PAINT) {
+    if (p.spec_copy != 0) {
+      const uint32_t ncopy = (uint32_t)p.N * (uint32_t)p.ncg;
+      const uint32_t c = p.spec_copy == 2 ? block : block - (uint32_t)p.N;      // (behind: wraps above ncopy for a state workgroup)
+      if (c < ncopy) { spec_copy_group(p, c); return; }
+      if (p.spec_copy == 2) block -= ncopy;
+    }
+  }
   const int l = lane_id();
   const uint32_t cycles0 = (uint32_t)__builtin_amdgcn_s_memtime();
   // the environment of this block: its own index, or (cover_order) the next one in order of decreasing cost of the previous step
-  int env = blockIdx.x;
+  int env = (int)block;
   // ... and, as in the resample kernel, the wave's priority follows the work it has left: the cycles it took last time (its
   // bucket) minus the cycles since it began, one level per 2^prio_q cycles (about half a mean wave), re-evaluated at the end of
   // every phase and batch.  0 cycles predicted = no priorities (plain order, or switched off).
@@ -2109,16 +2177,16 @@ swb_cover_kernel(const swb_params p) {
   // builds file no lists and keep three lanes)
   if (p.cost_cnt != nullptr && l < ((!PAINT && p.split_bands) ? 4 : 3))
     filing_words_l = p.cost_cnt[l == 0 ? SWB_COST_WORD_KEY_LO(p.parity) : (l == 1 ? SWB_COST_WORD_KEY_SCALE(p.parity) : ((PAINT || l == 2) ? SWB_COST_WORD_COVER_SHIFT(ph) : SWB_COST_WORD_SPLIT(p.parity)))];
-  if (p.ccost_list) cover_cost_housekeeping(p, ph_prev, ph, ph_next);
+  if (p.ccost_list) cover_cost_housekeeping(p, block, ph_prev, ph, ph_next);
   // (the run lists' arena: every launch -- whether it lists runs or not -- leaves the NEXT launch's counter at zero)
-  if (p.arena_head != nullptr && blockIdx.x == 0 && l == 0) p.arena_head[p.parity ^ 1] = 0u;
+  if (p.arena_head != nullptr && block == 0 && l == 0) p.arena_head[p.parity ^ 1] = 0u;
   if (p.cover_order) {
-    const int sh = (int)(blockIdx.x & (SWB_COST_SHARDS - 1)), cap = (p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS;
+    const int sh = (int)(block & (SWB_COST_SHARDS - 1)), cap = (p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS;
     int bucket = 0;
     env = cost_ordered_entry(p.cost_cnt + cost_row1(ph_prev, sh),
                              as_const(p.ccost_list) + (size_t)(ph_prev * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS * cap, cap,
-                             (int)(blockIdx.x >> 3), &bucket);
-    if (env < 0) return;                                 // (cannot happen: the host orders a launch only after one that filed all)
+                             (int)(block >> 3), &bucket);
+    if (env < 0) return;                                // (cannot happen: the host orders a launch only after one that filed all)
     prio_q = (p.prio_levels & 2) ? as_const(p.cost_cnt)[SWB_COST_WORD_COVER_PRIO(ph)] : 0u;
     if (prio_q) predicted = (uint32_t)(2 * bucket + 1) << (as_const(p.cost_cnt)[SWB_COST_WORD_COVER_SHIFT(ph_prev)] - 1u);
   }
@@ -2253,15 +2321,16 @@ swb_cover_kernel(const swb_params p) {
   // their copy in LDS (`bst`; reading the header back takes an agent-scope fence, which writes the XCD's L2 back: measured, the
   // cover kernel of 4096 environments 0.052 -> 0.133 ms).
   // cost_l: lane g, the cost of the list of column group g; built_cycles: 0, or (kept lists) the cycles of the wave that built
-  // them, in place of this wave's own; copies: the second kernel copies this environment's frame (swb_params::frame_cache).  Then the overflow slot goes back and the error flags out.
-  [[maybe_unused]] auto file_lists = [&](int cost_l, const uint32_t* bst, uint32_t built_cycles, bool copies) __attribute__((always_inline)) {
-    // Split bands (swb_params::split_bands): the band tasks only where the environment resamples or fills and the launch's word
-    // says split; else one WHOLE task per column group, under the whole list's cost -- a copy always.  Lane 0 of a wave that does
-    // not copy counts its frames for the next launch's word.
-    const bool whole = p.split_bands && (copies || __builtin_amdgcn_readlane((int)filing_words_l, 3) == 0);
+  // them, in place of this wave's own; copied: the environment's frame is the copy this launch's copy workgroups make
+  // (swb_params::spec_copy, SWB_RHDR_FRAME = 2) -- the wave files NO task for the second kernel, only its environment for the
+  // next cover launch.  Then the overflow slot goes back and the error flags out.
+  [[maybe_unused]] auto file_lists = [&](int cost_l, const uint32_t* bst, uint32_t built_cycles, bool copied) __attribute__((always_inline)) {
+    // Split bands (swb_params::split_bands): the band tasks only where the launch's word says split; else one WHOLE task per
+    // column group, under the whole list's cost.  Lane 0 counts the wave's frames for the next launch's word.
+    const bool whole = p.split_bands && (copied || __builtin_amdgcn_readlane((int)filing_words_l, 3) == 0);
     const bool bt = bst != nullptr && !whole;
     const int ntask = bt ? p.ncg * p.nbands : p.ncg;
-    const bool file0 = p.cost_cnt != nullptr && l < ntask, file1 = p.ccost_list != nullptr && l == 0;
+    const bool file0 = p.cost_cnt != nullptr && l < ntask && !copied, file1 = p.ccost_list != nullptr && l == 0;
     const int sh = env & (SWB_COST_SHARDS - 1);
     int task_cost = cost_l, task_bits = l << 24;
     if (bt) {
@@ -2273,9 +2342,6 @@ swb_cover_kernel(const swb_params p) {
       task_bits = (g2 << 24) | (b2 << 26);
     }
     if (whole) task_bits |= SWB_TASK_WHOLE;
-    // (the tasks of an environment whose frame is copied from the cache, SWB_RHDR_FRAME = 2: a twentieth of a resampling task's
-    // work whatever the list -- filed under the stored cost they would stand between the tasks that resample)
-    if (copies) task_cost = p.copy_cost;
     const int key0 = cost_key(task_cost, (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 0), (uint32_t)__builtin_amdgcn_readlane((int)filing_words_l, 1));
     int key1 = 0;
     uint32_t cycles = built_cycles;
@@ -2286,14 +2352,15 @@ swb_cover_kernel(const swb_params p) {
       if (l == 0 && (cycles >> width) >= (uint32_t)SWB_COST_BUCKETS) atomicMax(&p.cost_cnt[SWB_COST_WORD_COVER_MAX(ph, sh)], cycles);
     }
     uint32_t pos0 = 0u, pos1 = 0u;
-    // (copying tasks all carry one cost, so all of a wave's tasks -- and most of the launch's -- meet in one bucket: lane 0 takes
-    // the wave's ntask places with one atomic.  Measured without this, 1024 environments in 8 band tasks each: the cover kernel
-    // +15 %, eight returning atomics per wave queueing on one word per shard.)
-    if (copies) { if (file0 && l == 0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], (uint32_t)ntask); }
-    else if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);
+    if (file0) pos0 = atomicAdd(&p.cost_cnt[cost_row0(p.parity, sh) + key0], 1u);
     if (file1) pos1 = atomicAdd(&p.cost_cnt[cost_row1(ph, sh) + key1], 1u);
-    if (p.split_bands && !copies && p.cost_cnt != nullptr && l == 0) atomicAdd(&p.cost_cnt[SWB_COST_WORD_SPLIT_CNT(p.parity, sh, (env >> 3) & (SWB_COST_BUCKETS - 1))], (uint32_t)p.ncg);
-    if (copies) pos0 = (uint32_t)__builtin_amdgcn_readlane((int)pos0, 0) + (uint32_t)l;
+    if (p.split_bands && !copied && p.cost_cnt != nullptr && l == 0) atomicAdd(&p.cost_cnt[SWB_COST_WORD_SPLIT_CNT(p.parity, sh, (env >> 3) & (SWB_COST_BUCKETS - 1))], (uint32_t)p.ncg);
+    // (SWB_LIST_STATS: the counters keep the meaning they had while tasks of the second kernel made the copies -- what those would
+    // have counted: a task per column group, and per band where the grid or the filing is per band; split bands: whole copies)
+    if (copied && p.frame_stats && l == 0) {
+      atomicAdd(&p.frame_stats[0], (unsigned long long)(p.split_bands ? p.ncg : p.ncg * p.nbands));
+      if (p.split_stats) atomicAdd(&p.split_stats[2], (unsigned long long)p.ncg);
+    }
     if (file0) p.cost_list[((size_t)(p.parity * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key0) * p.cost_cap + pos0] = env | task_bits;
     if (file1) p.ccost_list[((size_t)(ph * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS + key1) * ((p.N + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS) + pos1] = env;
     if (l == 0) ovf_slot_release(p, ovf);
@@ -2321,22 +2388,25 @@ swb_cover_kernel(const swb_params p) {
     }
     if (p.list_stats != nullptr && l == 0) atomicAdd(&p.list_stats[keep ? 0 : 1], 1ull);
     if (keep) {
-      // the frame (SWB_RHDR_FRAME): kept once, the resample waves of this launch fill the cache; kept again, they copy from it
+      // the frame (SWB_RHDR_FRAME): kept once, the resample waves of this launch fill the cache; kept again, the frame is the copy
+      // this launch's copy workgroups make of it (spec_copy_group: they copied on the old word, 1 or 2) and no task is filed
       // (written only where it changes: a wave that keeps on through a still period writes nothing at all, as before)
       const uint32_t frame_word_was = (uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 2);
       const uint32_t frame_word = p.frame_cache ? min(frame_word_was + 1u, 2u) : 0u;
       uint32_t* bst = nullptr;
       // the band starts (and, in slot nbands, the list's end) from the header -- split bands: not for a wave that files whole
       // tasks (file_lists decides the same way), which is nearly every wave that keeps (a round trip to memory at the wave's end, with nothing behind it to hide it)
+      // -- and not for a wave whose frame is the copy: it files no task at all
+      const bool copied = frame_word == 2u && p.spec_copy != 0;
       const bool files_whole = p.split_bands && (frame_word == 2u || __builtin_amdgcn_readlane((int)filing_words_l, 3) == 0);
-      if (p.band_tasks && !files_whole) {
+      if (p.band_tasks && !files_whole && !copied) {
         bst = L->outrow + 64;
         const uint32_t* hg = p.rhdr + (size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_GROUPS;
         const int g = l / SWB_BST_STRIDE, b = l - g * SWB_BST_STRIDE;
         if (g < p.ncg && b <= p.nbands) bst[l] = hg[g * SWB_RHDR_GSTRIDE + (b < p.nbands ? 1 + b : 0)];
       }
       if (l == 0 && frame_word != frame_word_was) p.rhdr[(size_t)env * SWB_RHDR_DWORDS + SWB_RHDR_FRAME] = frame_word;
-      file_lists((int)keep_words_l, bst, max((uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 1), 1u), frame_word == 2u);
+      file_lists((int)keep_words_l, bst, max((uint32_t)__builtin_amdgcn_readlane((int)keep_words_l, SWB_MAX_CG + 1), 1u), copied);
       return;
     }
   }
@@ -2522,36 +2592,6 @@ swb_cover_kernel(const swb_params p) {
 // continuation run -- the rows below a forced run end that have the spans of the run before it -- is one unit: the loop skips
 // from the two table loads straight to the vertical pass with the h[0..2] it holds (clipped, live across iterations); the
 // list position moves by one unit, so the "untouched slot" test above works as before.
-// The frame cache's mover (swb_params::frame_cache): `rows` row segments of `seg_bytes` bytes, `row_bytes` apart, from src to dst
-// at the same offsets -- a wave's rectangle of the frame, which lies alike in the caller's buffer and in the cache.  Lanes take
-// consecutive chunks of T (16 bytes where both sides are aligned, else a dword: the same bytes either way), BATCH of
-// them loaded before the first is stored -- a copying wave does nothing else, so the loads in flight are its whole latency hiding.
-template <typename T, int BATCH>
-__device__ __forceinline__ void copy_frame_rect_as(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows) {
-  const int l = lane_id();
-  const int cpr = (int)(seg_bytes / (uint32_t)sizeof(T)), total = rows * cpr;      // chunks per row segment (uniform), in all
-  const int step_rows = 64 / cpr, step_cols = 64 - step_rows * cpr;               // what 64 chunks further means
-  int row = l / cpr, col = l - row * cpr;
-  for (int base = 0; base < total; base += 64 * BATCH) {
-    T v[BATCH];
-    uint32_t off[BATCH];
-#pragma unroll
-    for (int j = 0; j < BATCH; ++j) {
-      off[j] = (uint32_t)row * row_bytes + (uint32_t)col * (uint32_t)sizeof(T);
-      if (base + 64 * j + l < total) v[j] = *reinterpret_cast<const T*>(src + off[j]);
-      row += step_rows; col += step_cols;
-      if (col >= cpr) { col -= cpr; ++row; }
-    }
-#pragma unroll
-    for (int j = 0; j < BATCH; ++j)
-      if (base + 64 * j + l < total) *reinterpret_cast<T*>(dst + off[j]) = v[j];
-  }
-}
-typedef uint32_t swb_c16 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void copy_frame_rect(const unsigned char* src, unsigned char* dst, uint32_t row_bytes, uint32_t seg_bytes, int rows, bool aligned16) {
-  if (aligned16) copy_frame_rect_as<swb_c16, 6>(src, dst, row_bytes, seg_bytes, rows);
-  else copy_frame_rect_as<uint32_t, 8>(src, dst, row_bytes, seg_bytes, rows);
-}
 typedef uint32_t swb_u4 __attribute__((ext_vector_type(4), aligned(8)));      // a run record starts on an 8-byte unit
 typedef int32_t swb_i8 __attribute__((ext_vector_type(8), aligned(32)));
 template <int VS>
@@ -2593,7 +2633,9 @@ swb_resample_kernel(const swb_params p) {
   cptr<uint32_t> hdr = as_const(p.rhdr) + (size_t)env * SWB_RHDR_DWORDS;
   // The frame cache (swb_params::frame_cache), decided once and wave-uniform from the word the cover wave left (SWB_RHDR_FRAME):
   // 0 resample, as ever; 1 resample, then leave the wave's rectangle -- output rows [o_lo, o_hi) of column group g -- in the
-  // cache; 2 copy the rectangle from the cache to the frame and return: no list, no prefix table, no lane constants.
+  // cache; 2 copy the rectangle from the cache to the frame and return: no list, no prefix table, no lane constants.  (2 is met only
+  // on handles that dispatch without cost order, whose grid has a wave for every environment: where tasks are filed, the cover
+  // launch made the copy and the environment filed none -- swb_params::spec_copy.)
   const uint32_t frame_mode = p.frame_cache ? hdr[SWB_RHDR_FRAME] : 0u;
   const uint32_t rect_row_bytes = 3u * (uint32_t)p.Wo, rect_seg_bytes = 3u * (uint32_t)min(64, p.Wo - 64 * g);
   const size_t frame_off = (size_t)env * p.Wo * p.Ho * 3 + (size_t)(p.Ho - o_hi) * rect_row_bytes + 192u * (uint32_t)g;

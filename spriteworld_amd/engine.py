@@ -475,6 +475,14 @@ class Engine(object):
     self._check(self.lib.swb_frame_cycles(self._h, w, self._stream()))
     return tuple(w)
 
+  def spec_copy_stats(self):
+    """The copy workgroups of the cover launches -- one per environment and column group of a rendering launch -- that copied
+    from the frame cache, since the engine was created (swb_spec_copy_stats; blocking): the frames counted by frame_stats as
+    copied, plus the copies a resample task overwrote.  Needs SWB_LIST_STATS like list_stats."""
+    w = C.c_int64(0)
+    self._check(self.lib.swb_spec_copy_stats(self._h, C.byref(w), self._stream()))
+    return w.value
+
   def render(self):
     self._check(self.lib.swb_render(self._h, C.c_void_p(self.obs.data_ptr()), self._stream()))
     return self.obs

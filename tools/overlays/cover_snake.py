@@ -10,7 +10,7 @@ def apply(files, arg, replace_once):
   tiers = int(arg or 5)
   replace_once(files, k, '''    env = cost_ordered_entry(p.cost_cnt + cost_row1(ph_prev, sh),
                              as_const(p.ccost_list) + (size_t)(ph_prev * SWB_COST_SHARDS + sh) * SWB_COST_BUCKETS * cap, cap,
-                             (int)(blockIdx.x >> 3), &bucket);''', '''    int rank = (int)(blockIdx.x >> 3);
+                             (int)(block >> 3), &bucket);''', '''    int rank = (int)(block >> 3);
     {
       const int n_sh = (p.N - sh + SWB_COST_SHARDS - 1) / SWB_COST_SHARDS, tier = rank >> 7;
       if (tier < %d && (tier & 1) && ((tier + 1) << 7) <= n_sh) rank = (tier << 7) + 127 - (rank & 127);
