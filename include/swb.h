@@ -629,6 +629,54 @@ int swb_rollout_sampled(swb_handle h, int32_t mode /* enum swb_action_sampling *
                         int32_t M, int32_t K, int32_t keep_steps, const swb_rollout_outputs* out,
                         const swb_rollout_step_outputs* steps, const swb_rollout_sampled_outputs* sampled, void* stream);
 
+/* A rollout that draws its candidates from a PLAN: swb_rollout_sampled in every respect -- outputs, limits, refusals, the
+ * one-stream rule, the scratch and the trajectory block, the handle "holding a rollout" afterwards, sampled->actions required,
+ * in swb_rollout's layout and reproducing every output bit for bit when replayed through swb_rollout (swb_rollout_trajectory),
+ * (float) stored on a float32-action handle, SWB_ERR_STATE after a setter -- except that step k of every candidate of
+ * environment n is drawn from the caller's distribution of (k, n): a categorical over sprite indices, a uniform point inside the
+ * chosen sprite WHERE THAT CANDIDATE HAS IT at that step, and a bell-shaped motion around a mean.  It is what an iterative
+ * planner (CEM, MPPI) refits between its rounds: a click distribution that survives a refit has to name the sprite, not the
+ * place, because every candidate has moved its sprites somewhere else.
+ * Random numbers: swb_rollout_sampled's streams -- Philox4x32-10, key = seed, counter = (entry lo, block, entry hi, 1 + m), entry
+ * = first_env + n, one stream per virtual environment consumed step by step, independent of M and K.  Per step the position in
+ * the stream depends on the rejected tries only, as in SWB_SAMPLE_ON_SPRITE: never on step types (a FIRST step draws from the
+ * fresh episode's sprites), on choice_cdf being NULL, or on a fallback.
+ * Draw order per step, SelectMove / DragAndDrop, on the n sprites the step acts on (float64, one rounding per operation;
+ * tests/_rollout_guided_model.py restates it bit for bit):
+ *   1. u_c = uniform -- always drawn.
+ *   2. n == 0: sprite = -1, tries = 0, click = (uniform, uniform).
+ *   3. else W' = min(n, width), total = cdf[k, n, W' - 1].  choice_cdf NULL, or total not both finite and > 0:
+ *      s = min((int)(u_c * n), n - 1).  Else t = u_c * total and s = the first j < W' with cdf[j] > t; if there is none (t
+ *      rounded up to total), the first j with cdf[j] >= total.  A sprite of weight 0 is therefore never chosen while total > 0,
+ *      and sprites at index >= width have weight 0.
+ *   4. the click: SWB_SAMPLE_ON_SPRITE's tries for sprite s, unchanged (bounding box of the centred path, the containment test,
+ *      the cap SWB_CONTAINED_MAX_TRIES with tries = -1 and the sprite's own position).
+ *   5. motion, c = 0, 1: z = (((u1 + u2) + (u3 + u4)) - 2.0) * 1.7320508075688772 from four uniforms; v = mean[c] + std[c] * z;
+ *      a[2 + c] = v > 0 ? (v < 1 ? v : 1) : 0 -- a NaN gives 0: always in [0, 1].
+ *   Embodied: u_c = uniform, idx by rule 3 over exactly 8 weights (fallback (int)(u_c * 8)); carry = idx / 4, direction =
+ *   idx % 4; no click, no motion draws.
+ * DEVIATION from "Gaussian": z is Irwin-Hall with n = 4 (a sum of four uniforms, centred and scaled): mean 0, variance exactly 1,
+ * support +-2 sqrt(3) = +-3.46, kurtosis 2.7.  Every operation of it is an IEEE add or multiply, so a numpy model reproduces
+ * the draws bit for bit, which is how this library pins its samplers; Box-Muller's log and cos would not be.
+ * The weights are NOT validated (that would synchronise): the rules above make every value safe -- negative, NaN or infinite
+ * entries change which sprite is chosen, never what memory is read; nothing is indexed by a floating-point value beyond the
+ * clamps stated.
+ * sampled->sprite (may be NULL) receives s (Embodied: idx); sampled->tries is SWB_SAMPLE_ON_SPRITE's and must be NULL for Embodied.
+ * Two kernels, asynchronous on `stream`: the fork kernel of swb_rollout and swb_rollout_guided_kernel<KEEP> (the rollout
+ * kernel's step code, a drawer and a register budget of its own).
+ * SWB_ERR_INVALID besides swb_rollout's / swb_rollout_trajectory's, each message naming swb_rollout_guided: plan NULL; width
+ * outside its range; motion_mean / motion_std NULL on a click space, or given on Embodied; tries given on Embodied; sampled or
+ * sampled->actions NULL; steps given with keep_steps == 0. */
+typedef struct swb_rollout_plan {     /* device memory, caller-owned, only read */
+  const double* choice_cdf;   /* f64[K,N,W] running sums of non-negative weights along W, or NULL (uniform choice)              */
+  int32_t       width;        /* W: 1..max_sprites for SelectMove / DragAndDrop; exactly 8 for Embodied (index = carry*4 + direction) */
+  const double* motion_mean;  /* f64[K,N,2]  SelectMove / DragAndDrop: REQUIRED; Embodied: must be NULL                          */
+  const double* motion_std;   /* f64[K,N,2]  likewise                                                                           */
+} swb_rollout_plan;
+int swb_rollout_guided(swb_handle h, const swb_rollout_plan* plan, uint64_t seed, uint64_t first_env, int32_t M, int32_t K,
+                       int32_t keep_steps, const swb_rollout_outputs* out, const swb_rollout_step_outputs* steps,
+                       const swb_rollout_sampled_outputs* sampled, void* stream);
+
 /* Memory of the hand-off lists (what the cover kernel hands the resample / fill kernel: swb_variant_info::run_list_bytes).
  * A handle starts with a list of max(4, max_sprites + 1) units of 8 bytes per canvas row for every environment and group of 64
  * output columns -- enough for ANY scene of convex sprites, about ten times what the usual scene needs (133 KB per environment

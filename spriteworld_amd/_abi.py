@@ -146,6 +146,15 @@ class SwbRolloutSampledOutputs(C.Structure):
   ]
 
 
+class SwbRolloutPlan(C.Structure):
+  _fields_ = [
+      ('choice_cdf', C.c_void_p),
+      ('width', C.c_int32),
+      ('motion_mean', C.c_void_p),
+      ('motion_std', C.c_void_p),
+  ]
+
+
 class SwbState(C.Structure):
   _fields_ = [
       ('x', C.c_void_p),
@@ -386,6 +395,8 @@ PROTOTYPES = {
     'swb_sample_actions': (None, [_h, _i32, _u64, _u64, _P(SwbSampledActions), _h]),
     'swb_rollout_sampled': (None, [_h, _i32, _u64, _u64, _i32, _i32, _i32, _P(SwbRolloutOutputs), _P(SwbRolloutStepOutputs),
                                    _P(SwbRolloutSampledOutputs), _h]),
+    'swb_rollout_guided': (None, [_h, _P(SwbRolloutPlan), _u64, _u64, _i32, _i32, _i32, _P(SwbRolloutOutputs), _P(SwbRolloutStepOutputs),
+                                  _P(SwbRolloutSampledOutputs), _h]),
     'swb_trim_run_lists': (None, [_h, _P(_i32), _h]),
     'swb_list_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _h]),
     'swb_task_stats': (None, [_h, _P(C.c_int64), _P(C.c_int64), _h]),

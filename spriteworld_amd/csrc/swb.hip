@@ -1673,10 +1673,12 @@ static swb_state_view advanced(swb_state_view v, size_t e, size_t e_pool, size_t
   return v;
 }
 
-// swb_rollout (steps == nullptr, keep == false), swb_rollout_trajectory and swb_rollout_sampled (`name` is the caller's, for the
-// messages).  `sampled` (swb_rollout_sampled; its `actions` is actions_dev): the rollout kernel's builds that draw the actions.
+// swb_rollout (steps == nullptr, keep == false), swb_rollout_trajectory, swb_rollout_sampled and swb_rollout_guided (`name` is the
+// caller's, for the messages).  `sampled` (swb_rollout_sampled; its `actions` is actions_dev): the rollout kernel's builds that
+// draw the actions; `guided` (swb_rollout_guided, likewise): the kernels that draw them from a plan.
 static int rollout_launch(swb_handle h, const char* name, const void* actions_dev, int32_t M, int32_t K, const swb_rollout_outputs* out,
-                          bool keep, const swb_rollout_step_outputs* steps, void* stream, const swb_rollout_sample_args* sampled = nullptr) {
+                          bool keep, const swb_rollout_step_outputs* steps, void* stream, const swb_rollout_sample_args* sampled = nullptr,
+                          const swb_rollout_guided_args* guided = nullptr) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
   if (M <= 0 || K <= 0) return fail(SWB_ERR_INVALID, "%s: M and K must be positive (M = %d, K = %d)", name, M, K);
   if (!actions_dev) return fail(SWB_ERR_INVALID, "%s: actions is NULL", name);
@@ -1734,7 +1736,12 @@ static int rollout_launch(swb_handle h, const char* name, const void* actions_de
   memset(&sa, 0, sizeof(sa));
   if (sampled) sa = *sampled;
   const dim3 grid((unsigned)NV), block(SWB_WAVE);
-  if (sampled && keep) hipLaunchKernelGGL((swb_rollout_kernel<true, true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
+  if (guided) {
+    swb_rollout_guided_args ga = *guided;
+    ga.N = p.N;
+    if (keep) hipLaunchKernelGGL((swb_rollout_guided_kernel<true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, ga);
+    else hipLaunchKernelGGL((swb_rollout_guided_kernel<false>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, ga);
+  } else if (sampled && keep) hipLaunchKernelGGL((swb_rollout_kernel<true, true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
   else if (sampled) hipLaunchKernelGGL((swb_rollout_kernel<false, true>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
   else if (keep) hipLaunchKernelGGL((swb_rollout_kernel<true, false>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
   else hipLaunchKernelGGL((swb_rollout_kernel<false, false>), grid, block, sizeof(swb_ms_lds), st, a, p.S, kp, sa);
@@ -1771,6 +1778,39 @@ int swb_rollout_sampled(swb_handle h, int32_t mode, uint64_t seed, uint64_t firs
   sa.mode = mode; sa.seed = seed; sa.first_env = first_env;
   sa.actions = sampled->actions; sa.sprite = sampled->sprite; sa.tries = sampled->tries;
   return rollout_launch(h, "swb_rollout_sampled", sampled->actions, M, K, out, keep_steps != 0, steps, stream, &sa);
+}
+
+// A rollout that draws its candidates' actions from a plan distribution (include/swb.h): rollout_launch with the plan.  The
+// weights are not looked at here (that would synchronise): the kernel's rules make every value of them safe.
+int swb_rollout_guided(swb_handle h, const swb_rollout_plan* plan, uint64_t seed, uint64_t first_env, int32_t M, int32_t K,
+                       int32_t keep_steps, const swb_rollout_outputs* out, const swb_rollout_step_outputs* steps,
+                       const swb_rollout_sampled_outputs* sampled, void* stream) {
+  if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (!plan) return fail(SWB_ERR_INVALID, "swb_rollout_guided: plan is NULL");
+  if (!sampled || !sampled->actions)
+    return fail(SWB_ERR_INVALID, "swb_rollout_guided: sampled->actions is NULL (the drawn actions are a required output)");
+  const bool embodied = h->p.action_space == SWB_ACTION_EMBODIED;
+  if (embodied) {
+    if (plan->width != 8)
+      return fail(SWB_ERR_INVALID, "swb_rollout_guided: width = %d, an Embodied plan has exactly 8 action weights (carry * 4 + direction)",
+                  plan->width);
+    if (plan->motion_mean || plan->motion_std)
+      return fail(SWB_ERR_INVALID, "swb_rollout_guided: motion_mean and motion_std must be NULL for an Embodied action space");
+    if (sampled->tries) return fail(SWB_ERR_INVALID, "swb_rollout_guided: tries must be NULL for an Embodied action space (no click is drawn)");
+  } else {
+    if (plan->width < 1 || plan->width > h->p.S)
+      return fail(SWB_ERR_INVALID, "swb_rollout_guided: width = %d is outside [1, %d] (max_sprites)", plan->width, h->p.S);
+    if (!plan->motion_mean || !plan->motion_std)
+      return fail(SWB_ERR_INVALID, "swb_rollout_guided: motion_mean and motion_std are required (f64[K,N,2] in device memory)");
+  }
+  if (!keep_steps && steps)
+    return fail(SWB_ERR_INVALID, "swb_rollout_guided: per-step outputs (steps) need keep_steps != 0");
+  swb_rollout_guided_args ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.seed = seed; ga.first_env = first_env;
+  ga.actions = sampled->actions; ga.sprite = sampled->sprite; ga.tries = sampled->tries;
+  ga.cdf = plan->choice_cdf; ga.mean = plan->motion_mean; ga.std = plan->motion_std; ga.W = plan->width;
+  return rollout_launch(h, "swb_rollout_guided", sampled->actions, M, K, out, keep_steps != 0, steps, stream, nullptr, &ga);
 }
 
 // Frames of a rollout's end states (include/swb.h): render launches of the path the handle renders with, their state pointers

@@ -3588,4 +3588,88 @@ swb_rollout_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep,
     if (a.error && err) a.error[v] |= (uint8_t)err;     // sticky: the caller clears
   }
 }
+
+// GUIDED (swb_rollout_guided): the wave draws every step's action from the caller's plan distribution of (step, environment) --
+// a categorical over sprite indices, a uniform point inside the chosen sprite where it is now, a bell-shaped motion around a
+// mean -- rollout_guided_drawer, beside rollout_drawer<true> in swb_sampler.hip.inc.  Kernels of their own, not a run-time mode
+// of the SAMPLE builds: those sit at their register limit, and a drawer handed to swb_rollout_kernel as a template argument
+// renames its four builds, while a body shared through an inlined function was compiled to other code for them (2 more spilled
+// VGPRs in the plain build).  So the step loop below is swb_rollout_kernel's, line for line, with the other drawer; a change to
+// one is a change to both.  Register budget: profiles/r24_rollout_guided.md.
+#ifndef SWB_ROLLOUT_GUIDED_WAVES_PER_SIMD
+#define SWB_ROLLOUT_GUIDED_WAVES_PER_SIMD 6
+#endif
+struct swb_rollout_guided_args {
+  uint64_t seed, first_env;
+  void* actions;               // [K][N * M][4] f64 / f32 or [K][N * M][2] i32: what was drawn
+  int32_t *sprite, *tries;     // [K][N * M], may be NULL (tries: NULL for Embodied)
+  const double* cdf;           // [K][N][W] running sums of the choice weights, or NULL: uniform choice
+  const double *mean, *std;    // [K][N][2] of the motion; NULL for Embodied
+  int32_t W, N;                // the plan's width; the environments of the handle (the plan's row of (k, n) is k * N + n)
+};
+static_assert(sizeof(swb_rollout_args) + sizeof(swb_rollout_keep) + sizeof(swb_rollout_guided_args) + 8 <= 4096,
+              "kernel arguments of swb_rollout_guided_kernel");
+struct rollout_guided_drawer;                           // swb_sampler.hip.inc
+template <bool KEEP, class DRAWER = rollout_guided_drawer>
+__global__ void __launch_bounds__(SWB_WAVE, SWB_ROLLOUT_GUIDED_WAVES_PER_SIMD)
+swb_rollout_guided_kernel(const swb_rollout_args a, int S, const swb_rollout_keep keep, const swb_rollout_guided_args ga) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int l = lane_id();
+  const int v = blockIdx.x;
+  swb_ms_lds* M = reinterpret_cast<swb_ms_lds*>(smem);
+  task_scratch_t<SWB_MAX_SPRITES>* tscratch = &M->ts;
+  double2* cpath = M->path;
+  uint32_t err = 0;
+  int ep = 0;                                           // KEEP: the episode number the virtual environment is in
+  if constexpr (KEEP) ep = a.episode[v];                // (written by the fork launch)
+  DRAWER drawer;
+  drawer.start(ga, v / a.M, v % a.M);
+  for (int k = 0; k < a.K; ++k) {
+    const swb_params& q = *(const swb_params*)as_const(a.steps + k);
+    env_state es = load_env_state<false, false>(q, v, tscratch);
+    drawer.draw(ga, q, k, es, cpath);
+    auto hit = [&](int s2, double tx, double ty) __attribute__((always_inline)) {
+      const int nv = __builtin_amdgcn_readlane(es.nv_l, s2), so = __builtin_amdgcn_readlane(es.so_l, s2);
+      const double sc = readlane_d(es.scale_l, s2), ca = readlane_d(es.ca_l, s2), sa = readlane_d(es.sa_l, s2);
+      wave_sync();                                      // (the previous sprite's test has read the path)
+      if (l < nv) {
+        double cx, cy;
+        centered_vertex(q, so, l, sc, ca, sa, cx, cy);
+        cpath[l] = make_double2(cx, cy);
+      }
+      wave_sync();
+      return contains_point_wave(cpath, nv, tx, ty);
+    };
+    const step_cost sc = act_and_move(q, v, es, hit);
+    err |= finish_step<false, false>(q, v, es, sc, tscratch);       // (forked parameter blocks: no task cache, compiled out)
+    if constexpr (KEEP) {
+      const size_t slot = (size_t)k * gridDim.x + v;    // (one workgroup per virtual environment: gridDim.x = N * M)
+      ep += es.first ? 1 : 0;
+      if (l < S) {
+        keep.traj.x[slot * S + l] = es.px;
+        keep.traj.y[slot * S + l] = es.py;
+        if (keep.out_x) keep.out_x[slot * S + l] = es.px;
+        if (keep.out_y) keep.out_y[slot * S + l] = es.py;
+      }
+      if (l == 0) {
+        keep.traj.nspr[slot] = es.n; keep.traj.entry[slot] = es.en; keep.traj.step_count[slot] = sc.step_count;
+        keep.traj.episode[slot] = ep;
+        if (k > 0) keep.traj.reset_next[slot - gridDim.x] = es.first ? 1 : 0;
+        if (keep.out_n) keep.out_n[slot] = es.n;
+      }
+    }
+    wave_sync();                                        // the next iteration reads what this one stored (state words, LDS scratch)
+  }
+  if constexpr (KEEP) {
+    if (l == 0) keep.traj.reset_next[(size_t)(a.K - 1) * gridDim.x + v] = a.reset_next[v];
+  }
+  if (l < S) {
+    if (a.out_x) a.out_x[(size_t)v * S + l] = a.x[(size_t)v * S + l];
+    if (a.out_y) a.out_y[(size_t)v * S + l] = a.y[(size_t)v * S + l];
+  }
+  if (l == 0) {
+    if (a.out_n) a.out_n[v] = a.nspr[v];
+    if (a.error && err) a.error[v] |= (uint8_t)err;     // sticky: the caller clears
+  }
+}
 #endif  // SWB_WIDE_TU

@@ -707,4 +707,121 @@ struct rollout_drawer<true> {
     }
   }
 };
+
+// --------------------------------------------------------------------------------------------
+// Rollouts that draw their candidates from a plan (swb_rollout_guided, include/swb.h): what swb_rollout_guided_kernel calls, in
+// the place and under the rules of rollout_drawer<true> above -- the same stream per virtual environment, the same registers
+// read, the same path buffer and wave_sync()s, the same stores.  The plan's row of (step k, environment n) is only read, and
+// was written by earlier launches: its wave-uniform words (the row's total, the four motion parameters) are scalar loads
+// (as_const) made once per step ahead of the tries loop, the running sum of lane l's sprite a plain vector load.
+// Draw order per step (tests/_rollout_guided_model.py restates it, bit for bit; float64, no contraction):
+//   SelectMove / DragAndDrop, n = es.n sprites, W' = min(n, W):
+//     1. u_c = uniform(), always.
+//     2. n == 0: sprite = -1, tries = 0, click = (uniform(), uniform()).
+//     3. total = cdf[W' - 1].  No cdf, or total not finite and > 0: s = min((int)(u_c * n), n - 1).  Else t = u_c * total and
+//        s = the first j < W' with cdf[j] > t; none (t rounded up to total): the first j with cdf[j] >= total -- lanes =
+//        sprites, two ballots, a find-first.  A sprite of weight 0 has the running sum of its predecessor and is never first.
+//     4. the click: ON_SPRITE's tries loop on sprite s.
+//     5. c = 0, 1: z = (((u1 + u2) + (u3 + u4)) - 2) * sqrt(3) of four uniform()s (Irwin-Hall, n = 4: mean 0, variance 1,
+//        |z| <= 2 sqrt(3)); v = mean[c] + std[c] * z; a[2 + c] = v > 0 ? (v < 1 ? v : 1) : 0 (a NaN gives 0).
+//   Embodied: u_c = uniform(); idx by rule 3 with n = W' = 8; carry = idx / 4, direction = idx % 4.
+// Nothing is indexed by a drawn or loaded floating-point value: s comes out of a ballot over lanes < W' <= n, or is clamped.
+// --------------------------------------------------------------------------------------------
+struct rollout_guided_drawer {
+  rollout_rng rng;
+  int n_env;
+
+  __device__ __forceinline__ void start(const swb_rollout_guided_args& ga, int n_env_, int m) {
+    rng.key0 = (uint32_t)ga.seed; rng.key1 = (uint32_t)(ga.seed >> 32); rng.next = 0u; rng.word = 0u;
+    const uint64_t ge = ga.first_env + (uint64_t)n_env_;
+    rng.entry = (uint32_t)ge; rng.entry_hi = (uint32_t)(ge >> 32);
+    rng.word3 = 1u + (uint32_t)m;
+    n_env = n_env_;
+  }
+
+  // rule 3 over the first `wp` running sums of the row at `cdf` (NULL: none), for `n` choices: wave-uniform
+  __device__ __forceinline__ int choose(const double* cdf, int wp, int n, double u_c) {
+    const int l = lane_id();
+    double total = 0.0;
+    if (cdf) total = as_const(cdf)[wp - 1];
+    if (!(total > 0.0 && total < __builtin_huge_val())) return min((int)__dmul_rn(u_c, (double)n), n - 1);
+    const double t = __dmul_rn(u_c, total);
+    const double c = (l < wp) ? cdf[l] : 0.0;
+    const unsigned long long above = __ballot(l < wp && c > t), reach = __ballot(l < wp && c >= total);
+    return above ? __builtin_ctzll(above) : (reach ? __builtin_ctzll(reach) : wp - 1);
+  }
+
+  __device__ __forceinline__ void draw(const swb_rollout_guided_args& ga, const swb_params& q, int k, env_state& es, double2* cpath) {
+    const int l = lane_id();
+    const int v = blockIdx.x;
+    const size_t slot = (size_t)k * gridDim.x + v;      // (one workgroup per virtual environment: gridDim.x = N * M)
+    const size_t row = (size_t)k * ga.N + n_env;
+    const double* cdf = ga.cdf ? ga.cdf + row * ga.W : nullptr;
+    const double u_c = rng.uniform();
+    if (q.action_space == SWB_ACTION_EMBODIED) {
+      const int idx = choose(cdf, 8, 8, u_c);
+      es.acti = (l == 0) ? idx / 4 : idx % 4;
+      if (l < 2) reinterpret_cast<int32_t*>(ga.actions)[2 * slot + l] = es.acti;
+      if (l == 0 && ga.sprite) ga.sprite[slot] = idx;
+      return;
+    }
+    const double mean0 = as_const(ga.mean)[2 * row], mean1 = as_const(ga.mean)[2 * row + 1];
+    const double std0 = as_const(ga.std)[2 * row], std1 = as_const(ga.std)[2 * row + 1];
+    const int n = es.n;
+    double a0 = 0.0, a1 = 0.0;
+    int sprite = -1, tries = 0;
+    if (n == 0) {
+      a0 = rng.uniform(); a1 = rng.uniform();
+    } else {
+      sprite = choose(cdf, min(n, ga.W), n, u_c);
+      const int nv = min(__builtin_amdgcn_readlane(es.nv_l, sprite), SWB_MAX_SHAPE_VERTS), so = __builtin_amdgcn_readlane(es.so_l, sprite);
+      const double sc = readlane_d(es.scale_l, sprite), ca = readlane_d(es.ca_l, sprite), sn = readlane_d(es.sa_l, sprite);
+      const double px = readlane_d(es.px, sprite), py = readlane_d(es.py, sprite);
+      double cx = 0.0, cy = 0.0;
+      wave_sync();                                      // (the previous step's hit tests have read the path)
+      if (l < nv) {
+        centered_vertex(q, so, l, sc, ca, sn, cx, cy);
+        cpath[l] = make_double2(cx, cy);
+      }
+      wave_sync();
+      // sprite.py:119-120: np.min / np.max over the vertices (lanes beyond the path repeat vertex 0)
+      const double fx = readlane_d(cx, 0), fy = readlane_d(cy, 0);
+      const double vx = (l < nv) ? cx : fx, vy = (l < nv) ? cy : fy;
+      const double lo_x = wave_min_d(vx), lo_y = wave_min_d(vy), hi_x = wave_max_d(vx), hi_y = wave_max_d(vy);
+      const double w_x = __dsub_rn(hi_x, lo_x), w_y = __dsub_rn(hi_y, lo_y);
+      a0 = px; a1 = py; tries = -1;
+      for (int t = 1; t <= SWB_CONTAINED_MAX_TRIES; ++t) {
+        const double ux = rng.uniform(), uy = rng.uniform();
+        const double sx = __dadd_rn(px, __dadd_rn(lo_x, __dmul_rn(w_x, ux)));
+        const double sy = __dadd_rn(py, __dadd_rn(lo_y, __dmul_rn(w_y, uy)));
+        if (contains_point_wave(cpath, nv, __dsub_rn(sx, px), __dsub_rn(sy, py))) {   // (the test point is sample - pos)
+          a0 = sx; a1 = sy; tries = t;
+          break;
+        }
+      }
+    }
+    if (l == 0) {
+      if (ga.sprite) ga.sprite[slot] = sprite;
+      if (ga.tries) ga.tries[slot] = tries;
+    }
+    const double a2 = motion(mean0, std0), a3 = motion(mean1, std1);
+    const double mine = (l == 0) ? a0 : ((l == 1) ? a1 : ((l == 2) ? a2 : a3));
+    if (q.action_is_f32) {
+      const float f = (float)mine;
+      es.act = (double)f;
+      if (l < 4) reinterpret_cast<float*>(ga.actions)[4 * slot + l] = f;
+    } else {
+      es.act = mine;
+      if (l < 4) reinterpret_cast<double*>(ga.actions)[4 * slot + l] = mine;
+    }
+  }
+
+  // rule 5: one motion component
+  __device__ __forceinline__ double motion(double mean, double std) {
+    const double u1 = rng.uniform(), u2 = rng.uniform(), u3 = rng.uniform(), u4 = rng.uniform();
+    const double z = __dmul_rn(__dsub_rn(__dadd_rn(__dadd_rn(u1, u2), __dadd_rn(u3, u4)), 2.0), 1.7320508075688772);
+    const double v = __dadd_rn(mean, __dmul_rn(std, z));
+    return v > 0.0 ? (v < 1.0 ? v : 1.0) : 0.0;
+  }
+};
 #endif  // SWB_WIDE_TU

@@ -358,6 +358,81 @@ class Engine(object):
     res.update((k, drawn[k]) for k in outputs)
     return res
 
+  def rollout_guided(self, seed, M, K, choice_cdf=None, width=None, motion_mean=None, motion_std=None, first_env=0, positions=False,
+                     keep_steps=False, outputs=('actions', 'sprite')):
+    """A rollout whose candidates are drawn by the rollout kernel from a plan distribution per (step, environment)
+    (swb_rollout_guided: two kernels, asynchronous, the live state untouched): a categorical over sprite indices, a uniform
+    point inside the chosen sprite where the candidate has it at that step, and a motion mean + std * z clipped to [0, 1], z
+    Irwin-Hall (n = 4) with mean 0 and variance 1.  choice_cdf: f64[K, N, W] device tensor of running sums of non-negative
+    weights along W, or None (uniform choice; `width` then defaults to max_sprites, 8 for Embodied); motion_mean, motion_std:
+    f64[K, N, 2] device tensors, required for SelectMove / DragAndDrop and None for Embodied (W = 8: index = carry * 4 +
+    direction).  The streams are `rollout_sampled`'s.  Returns the dict of `rollout(..., positions, keep_steps)` plus the
+    `outputs` asked for among 'actions' (as `rollout_sampled`'s), 'sprite' (i32[K, N, M]: the chosen sprite, -1 without
+    sprites; Embodied: the chosen index) and 'tries' (i32[K, N, M], not for Embodied).  Afterwards the engine holds a rollout
+    as after `rollout`."""
+    embodied = self.cfg.action_space == _abi.ACTION_EMBODIED
+    if embodied:
+      a_dtype, a_width = torch.int32, 2
+    else:
+      a_dtype, a_width = (torch.float32 if self.cfg.action_is_f32 else torch.float64), 4
+    M, K = int(M), int(K)
+    layout = {'actions': ((K, self.N, M, a_width), a_dtype), 'sprite': ((K, self.N, M), torch.int32), 'tries': ((K, self.N, M), torch.int32)}
+    unknown = [k for k in outputs if k not in layout]
+    if unknown:
+      raise ValueError('rollout_guided outputs must be among %s, got %s' % (sorted(layout), unknown))
+    if M <= 0 or K <= 0:
+      raise ValueError('rollout_guided: M and K must be positive, got M = %d, K = %d' % (M, K))
+
+    def plan_tensor(t, last, what):
+      if t is None:
+        return None
+      if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[:2]) != (K, self.N) or (last is not None and t.shape[2] != last):
+        raise ValueError('rollout_guided: %s must be a tensor [%d, %d, %s], got %s' % (
+            what, K, self.N, 'W' if last is None else last, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+      if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+        t = t.to(device=self.device, dtype=torch.float64).contiguous()
+      return t
+
+    cdf = plan_tensor(choice_cdf, None, 'choice_cdf')
+    mean, std = plan_tensor(motion_mean, 2, 'motion_mean'), plan_tensor(motion_std, 2, 'motion_std')
+    if width is None:
+      width = int(cdf.shape[2]) if cdf is not None else (8 if embodied else self.S)
+    if cdf is not None and cdf.shape[2] != int(width):
+      raise ValueError('rollout_guided: choice_cdf has %d columns, width is %d' % (cdf.shape[2], int(width)))
+    self._rollout_M = self._rollout_K = 0
+    with self._device_scope():
+      new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+      res = {'reward': new((K, self.N, M), torch.float64), 'discount': new((K, self.N, M), torch.float32),
+             'step_type': new((K, self.N, M), torch.uint8), 'success': new((K, self.N, M), torch.uint8),
+             'error': torch.zeros((self.N, M), dtype=torch.uint8, device=self.device)}
+      if positions:
+        res.update(x=new((self.N, M, self.S), torch.float64), y=new((self.N, M, self.S), torch.float64),
+                   n_sprites=new((self.N, M), torch.int32))
+      steps = {}
+      if positions and keep_steps:
+        steps = {'x': new((K, self.N, M, self.S), torch.float64), 'y': new((K, self.N, M, self.S), torch.float64),
+                 'n_sprites': new((K, self.N, M), torch.int32)}
+      drawn = {k: new(*layout[k]) for k in set(outputs) | {'actions'}}
+    o, so, sa, plan = _abi.SwbRolloutOutputs(), _abi.SwbRolloutStepOutputs(), _abi.SwbRolloutSampledOutputs(), _abi.SwbRolloutPlan()
+    for k, t in res.items():
+      setattr(o, k, t.data_ptr())
+    for k, t in steps.items():
+      setattr(so, k, t.data_ptr())
+    for k, t in drawn.items():
+      setattr(sa, k, t.data_ptr())
+    plan.width = int(width)
+    for k, t in (('choice_cdf', cdf), ('motion_mean', mean), ('motion_std', std)):
+      if t is not None:
+        setattr(plan, k, t.data_ptr())
+    self._last_rollout_actions = (drawn['actions'], cdf, mean, std)  # keep alive until the launch is consumed
+    self._check(self.lib.swb_rollout_guided(self._h, C.byref(plan), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(first_env)),
+                                            M, K, int(bool(keep_steps)), C.byref(o), C.byref(so) if keep_steps else None, C.byref(sa),
+                                            self._stream()))
+    self._rollout_M, self._rollout_K = M, (K if keep_steps else 0)
+    res.update((k + '_steps', t) for k, t in steps.items())
+    res.update((k, drawn[k]) for k in outputs)
+    return res
+
   def rollout_frames(self, candidates=None, step=None):
     """The frames the candidates of the LAST rollout end in (swb_rollout_frames: the render path of this engine on the
     rollout's scratch state, asynchronous, on the rollout's stream; the live state, `self.obs`, `self.error` and the pool

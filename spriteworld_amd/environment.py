@@ -72,6 +72,34 @@ class Rollout(collections.namedtuple('Rollout', ['step_type', 'reward', 'discoun
 # i32[N, M, K] views, entry [n, m, k] the sprites of environment n after step k + 1 of candidate m.
 RolloutSteps = collections.namedtuple('RolloutSteps', ['x', 'y', 'n_sprites'])
 
+# What `BatchedEnvironment.plan_cem` returns, device tensors: actions [N, K, A] and episode_return f64[N] of the best sequence found
+# per environment, best_per_iteration f64[N, I] (the best return known after each round: never decreasing), and the plan
+# distribution after the last refit -- sprite_weights f64[N, K, W], motion_mean, motion_std f64[N, K, 2] --, which `init=` takes.
+CemPlan = collections.namedtuple('CemPlan', ['actions', 'episode_return', 'best_per_iteration', 'sprite_weights', 'motion_mean',
+                                             'motion_std'])
+
+
+def cem_refit(actions, sprite, elite, width, weight_floor, min_std):
+  """One refit of `plan_cem`: actions [N, M, K, A] and sprite i32[N, M, K] as `rollout_guided` returns them, elite int64[N, E]
+  the candidates to fit -> (sprite_weights f64[N, K, width], motion_mean, motion_std f64[N, K, 2]).  Weights: the number of
+  elites that picked sprite j at step k (indices outside [0, width) pick none) plus `weight_floor`.  Motion: the elites'
+  population mean and standard deviation (divisor E) of actions[..., 2:4], the deviation at least `min_std`; for Embodied
+  actions (A = 2) mean and deviation are None.  Torch operations on the tensors' device, no synchronisation."""
+  N, E = elite.shape
+  rows = torch.arange(N, device=elite.device)[:, None]
+  picked = sprite[rows, elite].permute(0, 2, 1).to(torch.int64)          # [N, K, E]
+  valid = (picked >= 0) & (picked < width)
+  counts = torch.zeros((N, picked.shape[1], width), dtype=torch.float64, device=elite.device)
+  counts.scatter_add_(2, picked.clamp(0, width - 1), valid.to(torch.float64))
+  weights = counts + weight_floor
+  if actions.shape[-1] != 4:
+    return weights, None, None
+  motion = actions[rows, elite][..., 2:4].to(torch.float64)              # [N, E, K, 2]
+  # (the sum divided by a device tensor: mean(), and a division by a Python number, multiply by a rounded 1 / E on the device,
+  # which a restatement elsewhere does not reproduce)
+  count = torch.full((), float(E), dtype=torch.float64, device=elite.device)
+  return weights, motion.sum(dim=1) / count, motion.std(dim=1, unbiased=False).clamp_min(min_std)
+
 
 # What `BatchedEnvironment.run_episodes` returns, device tensors [N]: episode_return f64 (the rewards of the environment's active
 # non-FIRST steps, summed in step order), length i64 (how many such steps), episodes i32 (LAST steps seen) and success bool (the
@@ -431,6 +459,114 @@ class BatchedEnvironment(object):
     per_step = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
     return Rollout(*(per_step + [res['x'], res['y'], res['n_sprites'], res['error']])), res['actions'].permute(1, 2, 0, 3)
 
+  def rollout_guided(self, num_candidates, num_steps, sprite_weights=None, motion_mean=0.5, motion_std=0.25, keep_steps=False):
+    """An iterative planner's rollout: as `rollout_random(click='sprite')`, but step k of every candidate of environment n is
+    drawn from a plan distribution of (n, k) the caller owns and refits between calls (swb_rollout_guided):
+      sprite_weights [N, K, W] (tensor or array, W <= max_sprites; None: uniform): the sprite to click is drawn with
+        probability proportional to its weight among those the candidate has at that step -- negative weights count as 0,
+        sprites at index >= W have weight 0, a row that sums to 0 (or is not finite) means uniform --, the click is a uniform
+        point inside that sprite WHERE THE CANDIDATE HAS IT at that step;
+      motion_mean, motion_std [N, K, 2] or scalars: action[2:4] = clip(mean + std * z, 0, 1).  z is NOT Gaussian: it is a sum
+        of four uniforms, centred and scaled (Irwin-Hall, n = 4): mean 0, variance 1, bell-shaped, support +-3.46 -- every
+        operation of it is an IEEE add or multiply, so the draws are reproducible bit for bit.
+    Embodied: sprite_weights are ACTION weights [N, K, 8] over index = carry * 4 + direction; motion_mean / motion_std are not
+    used.  Returns `(Rollout, actions, sprite)`: the first two as `rollout_random`'s -- `rollout(actions)` returns the same
+    `Rollout` bit for bit --, sprite i32[N, M, K] the index drawn (-1: the candidate had no sprite; Embodied: the action index).
+    Keys, streams, `global_env_offset`, `keep_steps` and what works afterwards (`rollout_frames`, `rollout_positions`,
+    `rollout_snapshot`) are `rollout_random`'s.  Torch operations and two kernels, no host synchronisation."""
+    e = self._engine
+    N, K = self._num_envs, int(num_steps)
+    embodied = e.cfg.action_space == _abi.ACTION_EMBODIED
+
+    def per_step(t, last, what):      # [N, K, last] (or a scalar) -> f64[K, N, last] on the device
+      if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+      t = t.to(device=e.device, dtype=torch.float64)
+      if t.dim() == 0:
+        return t.expand(K, N, last).contiguous()
+      if t.dim() != 3 or tuple(t.shape[:2]) != (N, K) or (last is not None and t.shape[2] != last):
+        raise ValueError('rollout_guided: %s must be [N, K, %s] with N = %d, K = %d, got %s' % (what, last or 'W', N, K, tuple(t.shape)))
+      return t.permute(1, 0, 2).contiguous()
+
+    cdf = width = None
+    if sprite_weights is not None:
+      w = sprite_weights if isinstance(sprite_weights, torch.Tensor) else torch.as_tensor(np.asarray(sprite_weights))
+      if w.dim() != 3:
+        raise ValueError('rollout_guided: sprite_weights must be [N, K, W], got %s' % (tuple(w.shape),))
+      cdf = per_step(w.to(device=e.device).clamp_min(0).double().cumsum(-1), None, 'sprite_weights')
+      width = int(cdf.shape[2])
+    mean = std = None
+    if not embodied:
+      mean, std = per_step(motion_mean, 2, 'motion_mean'), per_step(motion_std, 2, 'motion_std')
+    self._rollout_steps = None
+    res = e.rollout_guided(self._next_action_seed(), int(num_candidates), K, choice_cdf=cdf, width=width, motion_mean=mean,
+                           motion_std=std, first_env=self._global_env_offset, positions=True, keep_steps=keep_steps)
+    if keep_steps:
+      self._rollout_steps = RolloutSteps(res['x_steps'].permute(1, 2, 0, 3), res['y_steps'].permute(1, 2, 0, 3),
+                                         res['n_sprites_steps'].permute(1, 2, 0))
+    fields = [res[k].permute(1, 2, 0) for k in ('step_type', 'reward', 'discount', 'success')]
+    return (Rollout(*(fields + [res['x'], res['y'], res['n_sprites'], res['error']])), res['actions'].permute(1, 2, 0, 3),
+            res['sprite'].permute(1, 2, 0))
+
+  def plan_cem(self, num_candidates, num_steps, iterations=3, num_elites=None, weight_floor=0.1, min_std=0.02, init=None):
+    """A cross-entropy-method planner on the device: `iterations` (I) rounds of `rollout_guided` with M = `num_candidates`
+    sequences of K = `num_steps` steps per environment, the plan distribution refitted to each round's elites.  Returns
+    `CemPlan(actions [N, K, A], episode_return f64[N], best_per_iteration f64[N, I], sprite_weights [N, K, W], motion_mean,
+    motion_std [N, K, 2])`: the best sequence found per environment, its `Rollout.episode_return()`, the best return known
+    after each round, and the distribution the last refit left.
+    Round 0 draws from `init` -- a `CemPlan` or a `(sprite_weights, motion_mean, motion_std)` triple; None: uniform weights,
+    mean 0.5, std 0.25.  To warm-start MPC pass the returned fields shifted by one step.  Every round
+      * takes the `num_elites` (E; default max(1, M // 8)) candidates of highest `episode_return()` per environment (topk);
+      * refits the weights: how many elites picked sprite j at step k (scatter_add over [N, K, W]; a candidate without sprites
+        picks none), plus `weight_floor`, so that no sprite's probability falls below floor / (E + W * floor) and an
+        environment whose elites agree still looks elsewhere (default 0.1: an eleventh of one elite's vote);
+      * refits the motion: the elites' population mean and standard deviation of actions[2:4] per (n, k), the deviation at least
+        `min_std` (default 0.02 of the motion range: below it the next round's candidates would all but repeat the elites).
+        Embodied: the weights are ACTION weights (W = 8) and the motion parameters stay as given.
+    An incumbent -- the best sequence so far and its return -- is replaced only where a round's best is STRICTLY greater, so
+    best_per_iteration never decreases; `actions` and `episode_return` are the incumbent's, and `rollout(actions[:, None])`
+    returns that return bit for bit (the rollouts are noiseless).
+    Afterwards the engine holds the LAST round's rollout, not the incumbent's: `rollout_frames`, `rollout_positions` and
+    `rollout_snapshot` speak of that round's candidates.  To adopt the plan, step with `actions[:, k]`, or call
+    `rollout(actions[:, None])` first and take `rollout_snapshot()`.
+    Everything is torch on the device and two kernels per round: no host synchronisation."""
+    e = self._engine
+    N, M, K, I = self._num_envs, int(num_candidates), int(num_steps), int(iterations)
+    if I <= 0:
+      raise ValueError('plan_cem: iterations must be positive, got %d' % I)
+    E = max(1, M // 8) if num_elites is None else int(num_elites)
+    if not 1 <= E <= M:
+      raise ValueError('plan_cem: num_elites must be in [1, %d], got %d' % (M, E))
+    embodied = e.cfg.action_space == _abi.ACTION_EMBODIED
+    W = 8 if embodied else e.S
+    f64 = dict(dtype=torch.float64, device=e.device)
+    if init is None:
+      weights, mean, std = torch.ones((N, K, W), **f64), torch.full((N, K, 2), 0.5, **f64), torch.full((N, K, 2), 0.25, **f64)
+    else:
+      weights, mean, std = (init.sprite_weights, init.motion_mean, init.motion_std) if isinstance(init, CemPlan) else init
+      weights, mean, std = [torch.as_tensor(t).to(**f64) for t in (weights, mean, std)]
+      if tuple(weights.shape) != (N, K, W) or tuple(mean.shape) != (N, K, 2) or tuple(std.shape) != (N, K, 2):
+        raise ValueError('plan_cem: init must be sprite_weights [%d, %d, %d] and motion_mean, motion_std [%d, %d, 2], got %s, %s, %s' % (
+            N, K, W, N, K, tuple(weights.shape), tuple(mean.shape), tuple(std.shape)))
+    rows = torch.arange(N, device=e.device)
+    best_actions = best_return = None
+    history = []
+    for it in range(I):
+      r, actions, sprite = self.rollout_guided(M, K, weights, mean, std)
+      top, elite = r.episode_return().topk(E, dim=1)                  # [N, E], best first
+      round_actions, round_return = actions[rows, elite[:, 0]], top[:, 0]
+      if it == 0:
+        best_actions, best_return = round_actions.clone(), round_return
+      else:
+        better = round_return > best_return
+        best_actions = torch.where(better[:, None, None], round_actions, best_actions)
+        best_return = torch.where(better, round_return, best_return)
+      history.append(best_return)
+      weights, fit_mean, fit_std = cem_refit(actions, sprite, elite, W, weight_floor, min_std)
+      if not embodied:
+        mean, std = fit_mean, fit_std
+    return CemPlan(best_actions, best_return, torch.stack(history, dim=1), weights, mean, std)
+
   def rollout_positions(self):
     """`RolloutSteps(x, y, n_sprites)` of the last `rollout(..., keep_steps=True)`: x, y f64[N, M, K, S] and n_sprites
     i32[N, M, K] views of device tensors, entry [n, m, k] the sprites of environment n after step k + 1 of candidate m
@@ -703,6 +839,13 @@ class EnvironmentGroups(object):
     The groups' global_env_offset keeps their candidates' streams apart under one seed."""
     with torch.cuda.stream(self.streams[g]):
       return self.groups[g].rollout_random(num_candidates, num_steps, click=click, keep_steps=keep_steps)
+
+  def rollout_guided(self, g, num_candidates, num_steps, sprite_weights=None, motion_mean=0.5, motion_std=0.25, keep_steps=False):
+    """`BatchedEnvironment.rollout_guided` of group `g`, on its stream; the plan tensors must be valid on `self.streams[g]`, as
+    the returned ones are."""
+    with torch.cuda.stream(self.streams[g]):
+      return self.groups[g].rollout_guided(num_candidates, num_steps, sprite_weights=sprite_weights, motion_mean=motion_mean,
+                                           motion_std=motion_std, keep_steps=keep_steps)
 
   def synchronize(self):
     for s in self.streams:

@@ -36,6 +36,9 @@ def kernels_of(asm):
         flags = [f for f, on in zip(('KEEP', 'SAMPLE'), m.groups()) if on == '1'] if m else []
         key = 'swb_rollout_kernel' + ('<%s>' % ','.join(flags) if flags else '') if m else None
       if key is None:
+        m = re.search(r'swb_rollout_guided_kernelILb([01])E', name)
+        key = 'swb_rollout_guided_kernel' + ('<KEEP>' if m.group(1) == '1' else '') if m else None
+      if key is None:
         m = re.search(r'_Z\d+(swb_\w+?_kernel)', name)
         key = m.group(1) if m else name
     f = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))
