@@ -836,9 +836,58 @@ int swb_load_state(swb_handle h, const swb_snapshot* snap, int32_t C, const int3
  * (synchronises the device before the old arrays are freed).
  * SWB_ERR_INVALID: a null argument, dst == src, handles that differ in device, max_sprites, n_tasks, position dtype or in whether
  * a task keys on position, a range outside the pool, a pool whose scenes the large-frame raster kernel of dst cannot hold.
+ * Task sets (swb_set_task_sets): the set of every entry is copied with the pool; SWB_ERR_INVALID when the handles' tables differ.
  * SWB_ERR_STATE: src has no pool; override buffers exist on either handle.  dst cannot redraw the pool (the sampler's
  * specification stays with src): swb_resample_pool on it is refused until it is given a pool of its own. */
 int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host, const int32_t* pool_len_host, void* stream);
+
+/* Task sets: the task an episode is played under travels with its pool entry.  A task set is a
+ * contiguous range of the sub-task table swb_config::tasks with the aggregation and the time limit of ONE reference task:
+ * a plain task is one sub-task with is_meta = 0, a MetaAggregated its sub-tasks with is_meta = 1 (tasks.py:248-296).  Every
+ * pool entry names one set (a byte per entry); a step looks the set of the environment's entry up and
+ *   - evaluates the sub-tasks of that set only (tasks[first_task .. first_task + n_tasks), their labels at rows
+ *     first_task .. of swb_pool::label / cell_label: the rows of other sets are never read),
+ *   - aggregates them with the set's meta_aggregator, meta_termination and meta_terminate_bonus (is_meta = 1) or takes the one
+ *     sub-task's reward and success as they are (is_meta = 0),
+ *   - adds a float32 motion cost in float32 when the set's task returns a Python float (is_meta = 0 and not FIND_GOAL), and
+ *   - ends the episode at the set's max_episode_length.
+ * So an environment's consecutive episodes may be played under different tasks; resets, masked steps, snapshots, swb_copy_pool
+ * and swb_evaluate need to know nothing of it: the set follows swb_state::pool_entry. */
+#define SWB_MAX_TASK_SETS 8
+typedef struct swb_task_set {
+  int32_t first_task, n_tasks;      /* sub-tasks cfg.tasks[first_task .. first_task + n_tasks), n_tasks >= 1, inside [0, cfg.n_tasks); sets may overlap */
+  int32_t is_meta, meta_aggregator, meta_termination;   /* as swb_config's */
+  int32_t max_episode_length;
+  double  meta_terminate_bonus;
+} swb_task_set;
+
+/* Installs the handle's table of 1 .. SWB_MAX_TASK_SETS task sets.  Once, after swb_create and before any pool is installed:
+ * SWB_ERR_STATE on a handle that has a pool or a table already.  SWB_ERR_INVALID: a count outside [1, SWB_MAX_TASK_SETS], a
+ * sub-task range outside cfg.tasks[0 .. cfg.n_tasks), an unknown aggregator or termination rule, max_episode_length < 0.
+ * From then on cfg.n_tasks is only the stride T of the label arrays, and cfg.is_meta, cfg.meta_* and cfg.max_episode_length
+ * are unused.  A handle that never calls this behaves exactly as before, and launches the same kernels.
+ * A handle with task sets runs builds of the step kernels of its own (swb_cover_sets_kernel, swb_ms_state_sets_kernel: the
+ * only ones that carry the lookup; they honour setter overrides too); table and entry bytes live in device memory owned by the
+ * handle, not in the kernel arguments.  Rollouts are out of scope on such a handle: swb_rollout, swb_rollout_trajectory,
+ * swb_rollout_sampled, swb_rollout_guided, swb_rollout_frames and swb_rollout_step_frames return SWB_ERR_STATE. */
+int swb_set_task_sets(swb_handle h, int32_t n_sets, const swb_task_set* sets);
+
+/* The set of every pool entry: set_of_entry_host is u8[P], P the entries of the pool the handle holds.  swb_set_pool,
+ * swb_sample_pool and swb_sample_pool_tree put every entry in set 0; swb_copy_pool copies the source's assignment (and refuses
+ * with SWB_ERR_INVALID when the two handles' tables differ); swb_resample_pool keeps it.
+ * Validated first: a value >= the number of sets returns SWB_ERR_INVALID and changes nothing.  Uploaded on `stream`
+ * (synchronous with respect to the host array: it may be freed on return).  Takes effect at once, also for running episodes
+ * -- the set is looked up by entry at every step --, and makes every task record stale (swb_task_stats: one evaluation per
+ * environment at its next step); run lists and cached frames stay valid.  SWB_ERR_STATE: no task sets, no pool. */
+int swb_set_entry_task_sets(swb_handle h, const uint8_t* set_of_entry_host /* [P] */, void* stream);
+
+/* ... and back, into u8[P] of host memory.  Synchronous.  SWB_ERR_STATE: no task sets, no pool. */
+int swb_get_entry_task_sets(swb_handle h, uint8_t* set_of_entry_host /* [P] */);
+
+/* What an agent conditions on: set_dev[n] = the set of the entry environment n is in (i32[N], device memory).  One small
+ * kernel (swb_env_task_sets_kernel), asynchronous on `stream`; the handle is only read.  Unspecified (but a valid set index)
+ * for an environment that has had no FIRST step since its pool was installed.  SWB_ERR_STATE: no task sets, no pool. */
+int swb_env_task_sets(swb_handle h, int32_t* set_dev /* i32[N], device */, void* stream);
 
 /* Sprite attribute setters on a LIVE sprite (sprite.py:152-175; pinned by the reference's
  * tests/sprite_test.py:138-174), for sprite `sprite` of environment `env` in its current episode:

@@ -71,6 +71,22 @@ class SwbConfig(C.Structure):
   ]
 
 
+SWB_MAX_TASK_SETS = 8
+
+
+class SwbTaskSet(C.Structure):
+  """swb_task_set: a range of SwbConfig.tasks with the aggregation and the time limit of one reference task."""
+  _fields_ = [
+      ('first_task', C.c_int32),
+      ('n_tasks', C.c_int32),
+      ('is_meta', C.c_int32),
+      ('meta_aggregator', C.c_int32),
+      ('meta_termination', C.c_int32),
+      ('max_episode_length', C.c_int32),
+      ('meta_terminate_bonus', C.c_double),
+  ]
+
+
 class SwbPool(C.Structure):
   _fields_ = [
       ('n_entries', C.c_int32),
@@ -413,6 +429,10 @@ PROTOTYPES = {
     'swb_save_state': (None, [_h, _i32, _p, _i32, _P(SwbSnapshot), _h]),
     'swb_load_state': (None, [_h, _P(SwbSnapshot), _i32, _p, _u64, _p, _h]),
     'swb_copy_pool': (None, [_h, _h, _p, _p, _h]),
+    'swb_set_task_sets': (None, [_h, _i32, _P(SwbTaskSet)]),
+    'swb_set_entry_task_sets': (None, [_h, _p, _h]),
+    'swb_get_entry_task_sets': (None, [_h, _p]),
+    'swb_env_task_sets': (None, [_h, _p, _h]),
     'swb_set_sprite_attr': (None, [_h, _i32, _i32, _i32, _f64, _p, _p, _h]),
     'swb_set_sprite_cell_labels': (None, [_h, _i32, _i32, _p, _h]),
     'swb_get_sprite': (None, [_h, _i32, _i32, _p, _p, _p, _p, _p, _h]),

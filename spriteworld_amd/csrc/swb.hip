@@ -24,6 +24,14 @@
 // the cover kernels of canvases wider than 320 px are instantiated in swb_wide.hip (other scheduler flags)
 extern template __global__ void swb_cover_kernel<20, false>(const swb_params);
 extern template __global__ void swb_cover_kernel<20, true>(const swb_params);
+// ... and so is every kernel of handles with task sets (swb_cover_sets_kernel), at every width: this unit's code object does
+// not know of them
+extern template __global__ void swb_cover_sets_kernel<2, false>(const swb_params);
+extern template __global__ void swb_cover_sets_kernel<2, true>(const swb_params);
+extern template __global__ void swb_cover_sets_kernel<4, false>(const swb_params);
+extern template __global__ void swb_cover_sets_kernel<5, false>(const swb_params);
+extern template __global__ void swb_cover_sets_kernel<10, false>(const swb_params);
+extern template __global__ void swb_cover_sets_kernel<20, false>(const swb_params);
 
 namespace {
 
@@ -172,6 +180,13 @@ struct swb_engine {
   dev_buf<double> d_ov_scale, d_ov_angle, d_ov_cpath;
   dev_buf<int8_t> d_ov_label;
   dev_buf<int8_t> d_ov_cell_label;
+  bool setters = false;              // swb_set_sprite_attr has been called: the override arrays exist (d_ov_flag alone does not say
+                                     // so: a handle with task sets allocates the flags to run the OV kernels)
+  // task sets (swb_set_task_sets): the table, and the set of every pool entry (every entry 0 after a pool is installed).
+  // n_sets == 0: the handle has none, and the pointer behind its override flags, if it has flags, stays NULL
+  int n_sets = 0;
+  swb_task_set sets[SWB_MAX_TASK_SETS] = {};   // the table as installed (normalised); its device copy heads d_p_set
+  dev_buf<uint8_t> d_p_set;          // SWB_SET_TABLE_BYTES of table, then one byte per pool entry (allocated with every pool)
   // timing
   bool timing = false;
   struct step_events { hipEvent_t e0, e1, e2; };     // before cover, between the kernels, after resample / fill
@@ -212,17 +227,30 @@ typedef void (*kernel_fn)(const swb_params);
 
 // cover kernel by canvas width (NW 32-pixel words per canvas row); resample kernel by the output rows a canvas
 // row can feed at once (VS)
-struct variant { int nw; kernel_fn fn, fn_ov, fn_paint, fn_paint_ov; size_t lds_fixed, outrow_bytes; };
+// (fn_sets / fn_paint_sets: the builds of handles with task sets, swb_cover_sets_kernel)
+struct variant { int nw; kernel_fn fn, fn_ov, fn_paint, fn_paint_ov; size_t lds_fixed, outrow_bytes; kernel_fn fn_sets, fn_paint_sets; };
 
 template <int NW>
 variant make_variant() {
   const size_t outrow = 528;          // wave_lds::outrow is build_all_edges' scratch (132 dwords)
   kernel_fn paint = nullptr, paint_ov = nullptr;       // the builds that paint the frame themselves: canvases of up to 64 px only
+  kernel_fn paint_sets = nullptr;
   if constexpr (NW == 2) { paint = swb_cover_kernel<NW, false, true>; paint_ov = swb_cover_kernel<NW, true, true>; }
-  return {NW, swb_cover_kernel<NW>, swb_cover_kernel<NW, true>, paint, paint_ov, (sizeof(wave_lds<NW>) + outrow + 15) & ~(size_t)15, outrow};
+  if constexpr (NW == 2) paint_sets = swb_cover_sets_kernel<NW, true>;
+  return {NW, swb_cover_kernel<NW>, swb_cover_kernel<NW, true>, paint, paint_ov, (sizeof(wave_lds<NW>) + outrow + 15) & ~(size_t)15, outrow,
+          swb_cover_sets_kernel<NW, false>, paint_sets};
 }
 
+// The cover build a handle launches: with task sets the SETS build (overrides included), after a sprite setter the OV build.
+kernel_fn cover_fn(const swb_engine* h, const variant* v);
+kernel_fn cover_paint_fn(const swb_engine* h, const variant* v);
+
 const variant kVariants[] = {make_variant<2>(), make_variant<4>(), make_variant<5>(), make_variant<10>(), make_variant<20>()};
+
+kernel_fn cover_fn(const swb_engine* h, const variant* v) { return h->n_sets ? v->fn_sets : (h->d_ov_flag ? v->fn_ov : v->fn); }
+kernel_fn cover_paint_fn(const swb_engine* h, const variant* v) {
+  return h->n_sets ? v->fn_paint_sets : (h->d_ov_flag ? v->fn_paint_ov : v->fn_paint);
+}
 
 const variant* pick_variant(int Wc) {
   for (const variant& v : kVariants)
@@ -531,19 +559,19 @@ int launch(swb_engine* h, const void* actions, const swb_outputs* out, int rende
   }
   // engines on which a sprite setter has been called run the build that reads the per-environment overrides
   const bool paint = p.obs && paints_in_cover(h, v);
-  const kernel_fn fn = paint ? (h->d_ov_flag ? v->fn_paint_ov : v->fn_paint) : (h->d_ov_flag ? v->fn_ov : v->fn);
+  const kernel_fn fn = paint ? cover_paint_fn(h, v) : cover_fn(h, v);
   size_t lds = 0;
   if (int rc = cover_launch_config(h, v, fn, &p, &lds)) return rc;
   // first launch, a new pool that shrank the LDS footprint (more waves resident), or the switch to the override build -- not
   // the switch between the painting and the plain build of a family, which alternating launches with and without an
   // observation buffer make at every launch (the cache is keyed on the family's plain build)
-  const kernel_fn fn_family = h->d_ov_flag ? v->fn_ov : v->fn;
+  const kernel_fn fn_family = cover_fn(h, v);
   if (!h->d_ovf || (int)lds < h->ovf_lds_bytes || fn_family != h->ovf_fn) {
     if (h->d_ovf) {
       HIP_TRY(hipDeviceSynchronize());
       h->d_ovf.release(); h->d_ovf_bitmap.release();
     }
-    if (int rc = ensure_overflow_slots(h, fn_family, h->d_ov_flag ? v->fn_paint_ov : v->fn_paint, lds)) return rc;
+    if (int rc = ensure_overflow_slots(h, fn_family, cover_paint_fn(h, v), lds)) return rc;
     bump_list_epoch(h);              // LISTS ONLY (new overflow slots)
     h->ovf_lds_bytes = (int)lds;
     h->ovf_fn = fn_family;
@@ -694,11 +722,11 @@ int launch_large(swb_engine* h, const void* actions, const swb_outputs* out, int
   kernel_fn fn;
   size_t lds;
   if (h->many_sprites) {
-    fn = h->d_ov_flag ? swb_ms_state_kernel<true> : swb_ms_state_kernel<false>;
+    fn = h->n_sets ? swb_ms_state_sets_kernel : (h->d_ov_flag ? swb_ms_state_kernel<true> : swb_ms_state_kernel<false>);
     lds = sizeof(swb_ms_lds);
   } else {
     const variant* v = &kVariants[0];
-    fn = h->d_ov_flag ? v->fn_ov : v->fn;
+    fn = cover_fn(h, v);
     if (int rc = cover_launch_config(h, v, fn, &p, &lds)) return rc;
   }
   step_timer timer(h, stream);
@@ -750,6 +778,35 @@ int upload_resample_large(swb_engine* h, int axis, int out_size, int ksize, cons
   return SWB_OK;
 }
 
+// The override flags of a handle, allocated ONCE and only here: N flag bytes, then -- on a 64-byte line of its own -- the
+// pointer to the task-set block (SWB_OV_SLOT; NULL until publish_entry_sets).  The layout is an agreement between this file and
+// task_view_of<true> in the kernels: nothing else allocates, resizes or clears d_ov_flag as a whole (the flags are written
+// one byte at a time, by ov_store and by the kernels' reset), and publish_entry_sets alone writes the pointer.
+static_assert(SWB_OV_SLOT(1) == 64 && SWB_OV_SLOT(64) == 64 && SWB_OV_SLOT(65) == 128 && SWB_OV_FLAG_BYTES(64) == 128 &&
+              sizeof(const uint8_t*) <= 64, "the block's pointer has a line of its own behind the flags");
+int alloc_ov_flags(swb_engine* h) {
+  if (h->d_ov_flag) return 0;
+  return h->d_ov_flag.fill(nullptr, SWB_OV_FLAG_BYTES(h->p.N));
+}
+
+// Task sets: the kernels find the handle's block through the pointer behind the override flags (swb_params::ov_flag,
+// SWB_OV_SLOT).  Synchronous: the block it replaces has been freed behind a device synchronise already.
+int publish_entry_sets(swb_engine* h) {
+  if (!h->n_sets) return 0;
+  const uint8_t* block = h->d_p_set.ptr;
+  HIP_TRY(hipMemcpy(h->d_ov_flag.ptr + SWB_OV_SLOT(h->p.N), &block, sizeof(block), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// ... a fresh block for a pool of P entries: the handle's table, then every entry in set 0.
+int fill_entry_sets(swb_engine* h, int P) {
+  if (!h->n_sets) return 0;
+  std::vector<uint8_t> block(SWB_SET_TABLE_BYTES + (size_t)P, 0);
+  memcpy(block.data(), h->sets, sizeof(h->sets));
+  if (h->d_p_set.fill(block.data(), block.size())) return SWB_ERR_HIP;
+  return publish_entry_sets(h);
+}
+
 // The pool's device arrays as the kernels see them (swb_set_pool, swb_sample_pool).  The angle and colour columns are optional in
 // a pool set from the host, the per-cell labels exist on handles with a task that keys on position.
 void bind_pool(swb_engine* h, bool have_angle, bool have_color) {
@@ -793,6 +850,7 @@ int alloc_sampled_pool(swb_engine* h, int P, const int32_t* pool_base_host, cons
   }
   rc |= h->d_pool_base.fill(pool_base_host, N);
   rc |= h->d_pool_len.fill(pool_len_host, N);
+  rc |= fill_entry_sets(h, P);                                         // (task sets: every entry in set 0)
   if (rc) return SWB_ERR_HIP;
   h->pool_entries = P;
   bind_pool(h, true, true);
@@ -1364,6 +1422,7 @@ int swb_set_pool(swb_handle h, const swb_pool* pool) {
   rc |= h->d_pool_len.fill(pool->pool_len, N);
   if (pool->angle) rc |= h->d_p_angle.fill(pool->angle, PS);
   if (pool->color) rc |= h->d_p_color.fill(pool->color, PS * 3);
+  rc |= fill_entry_sets(h, P);                                         // (task sets: every entry in set 0)
   if (rc) return SWB_ERR_HIP;
   bind_pool(h, pool->angle != nullptr, pool->color != nullptr);
   h->pool_entries = P;
@@ -1692,8 +1751,10 @@ static int rollout_launch(swb_handle h, const char* name, const void* actions_de
                 name, K, p.N, M, p.S);
   if (!h->have_shapes) return fail(SWB_ERR_STATE, "swb_upload_shapes has not been called");
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_set_pool has not been called");
-  if (h->d_ov_flag)
+  if (h->setters)
     return fail(SWB_ERR_STATE, "%s: sprite setters have been called on this handle; rollouts under live overrides are not supported", name);
+  if (h->n_sets)
+    return fail(SWB_ERR_STATE, "%s: the handle has task sets (swb_set_task_sets); rollouts under task sets are not supported", name);
   HIP_TRY(hipSetDevice(h->device));
   const hipStream_t st = (hipStream_t)stream;
   const size_t NV = (size_t)p.N * M, S = (size_t)p.S;
@@ -1818,6 +1879,8 @@ int swb_rollout_guided(swb_handle h, const swb_rollout_plan* plan, uint64_t seed
 // slots are sized for --, or one launch on a staging block swb_rollout_pick_kernel gathers the picked candidates into.
 int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev, void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (h->n_sets)
+    return fail(SWB_ERR_STATE, "swb_rollout_frames: the handle has task sets (swb_set_task_sets); rollouts under task sets are not supported");
   if (!h->rollout_M) return fail(SWB_ERR_STATE, "swb_rollout_frames: no rollout has run on this handle (swb_rollout first)");
   if (!obs_dev) return fail(SWB_ERR_INVALID, "swb_rollout_frames: obs is NULL");
   if (M != h->rollout_M)
@@ -1825,7 +1888,7 @@ int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t
   if (h->rollout_stale)
     return fail(SWB_ERR_STATE, "swb_rollout_frames: the pool has changed since the last rollout (swb_set_pool, swb_sample_pool or "
                 "swb_resample_pool): its candidates may sit in entries that have been redrawn; roll out again");
-  if (h->d_ov_flag)
+  if (h->setters)
     return fail(SWB_ERR_STATE, "swb_rollout_frames: sprite setters have been called on this handle; rollouts under live overrides are not supported");
   if (int rc = check_ready(h, nullptr, 1)) return rc;
   HIP_TRY(hipSetDevice(h->device));
@@ -1865,6 +1928,8 @@ int swb_rollout_frames(swb_handle h, int32_t M, const int32_t* cand_dev, uint8_t
 int swb_rollout_step_frames(swb_handle h, int32_t M, int32_t step, const int32_t* cand_dev, uint8_t* obs_dev, uint8_t* error_dev,
                             void* stream) {
   if (!h) return fail(SWB_ERR_INVALID, "null handle");
+  if (h->n_sets)
+    return fail(SWB_ERR_STATE, "swb_rollout_step_frames: the handle has task sets (swb_set_task_sets); rollouts under task sets are not supported");
   if (!h->rollout_M) return fail(SWB_ERR_STATE, "swb_rollout_step_frames: no rollout has run on this handle (swb_rollout_trajectory first)");
   if (!h->rollout_kept_K)
     return fail(SWB_ERR_STATE, "swb_rollout_step_frames: the last rollout of this handle was a plain swb_rollout, which kept no steps "
@@ -1882,7 +1947,7 @@ int swb_rollout_step_frames(swb_handle h, int32_t M, int32_t step, const int32_t
   if (h->rollout_stale)
     return fail(SWB_ERR_STATE, "swb_rollout_step_frames: the pool has changed since the last rollout (swb_set_pool, swb_sample_pool or "
                 "swb_resample_pool): its candidates may sit in entries that have been redrawn; roll out again");
-  if (h->d_ov_flag)
+  if (h->setters)
     return fail(SWB_ERR_STATE, "swb_rollout_step_frames: sprite setters have been called on this handle; rollouts under live overrides are not supported");
   if (int rc = check_ready(h, nullptr, 1)) return rc;
   HIP_TRY(hipSetDevice(h->device));
@@ -2144,7 +2209,7 @@ int swb_save_state(swb_handle h, int32_t source, const int32_t* index_dev, int32
   if (int rc = check_snapshot_call(h, "swb_save_state", snap, C, &dst)) return rc;
   if (source != SWB_STATE_LIVE && source != SWB_STATE_ROLLOUT_END) return fail(SWB_ERR_INVALID, "swb_save_state: unknown source %d", source);
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_save_state: swb_set_pool has not been called");
-  if (h->d_ov_flag)
+  if (h->setters)
     return fail(SWB_ERR_STATE, "swb_save_state: sprite setters have been called on this handle; snapshots under live overrides are not supported");
   long long n_src = h->p.N;
   swb_state_view src = live_state_view(h);
@@ -2174,7 +2239,7 @@ int swb_load_state(swb_handle h, const swb_snapshot* snap, int32_t C, const int3
     return fail(SWB_ERR_INVALID, "swb_load_state: slot is NULL (environment n takes slot n) but C = %d and the handle has %d environments",
                 C, h->p.N);
   if (!h->have_pool) return fail(SWB_ERR_STATE, "swb_load_state: swb_set_pool has not been called");
-  if (h->d_ov_flag)
+  if (h->setters)
     return fail(SWB_ERR_STATE, "swb_load_state: sprite setters have been called on this handle; snapshots under live overrides are not supported");
   if (pool_id != 0 && pool_id != h->pool_id)
     return fail(SWB_ERR_STATE, "swb_load_state: the snapshot was saved under pool %llu, the handle holds pool %llu (a pool call since "
@@ -2206,8 +2271,11 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
     return fail(SWB_ERR_INVALID, "swb_copy_pool: the handles differ (device %d / %d, max_sprites %d / %d, n_tasks %d / %d, pos_is_f32 %d / %d, "
                 "a task keys on position %d / %d)", dst->device, src->device, dst->p.S, src->p.S, dst->p.n_tasks, src->p.n_tasks,
                 dst->p.pos_is_f32, src->p.pos_is_f32, (int)dst->keyed, (int)src->keyed);
+  if (dst->n_sets != src->n_sets || memcmp(dst->sets, src->sets, sizeof(swb_task_set) * (size_t)src->n_sets) != 0)
+    return fail(SWB_ERR_INVALID, "swb_copy_pool: the handles' task sets differ (%d / %d sets, or their fields): the entries' sets would "
+                "mean another task in dst", dst->n_sets, src->n_sets);
   if (!src->have_pool) return fail(SWB_ERR_STATE, "swb_copy_pool: src has no pool (swb_set_pool has not been called on it)");
-  if (dst->d_ov_flag || src->d_ov_flag)
+  if (dst->setters || src->setters)
     return fail(SWB_ERR_STATE, "swb_copy_pool: sprite setters have been called on one of the handles; snapshots under live overrides are not supported");
   const int P = src->pool_entries, N = dst->p.N;
   for (int i = 0; i < N; ++i)
@@ -2224,7 +2292,7 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
   dev_buf<double> t_x, t_y, t_xv, t_yv, t_scale, t_ca, t_sa, t_angle, t_color;
   dev_buf<uint32_t> t_rgb;
   dev_buf<int8_t> t_label, t_cell_label;
-  dev_buf<uint8_t> t_attr;
+  dev_buf<uint8_t> t_attr, t_set;
   const bool have_angle = src->p.p_angle != nullptr, have_color = src->p.p_color != nullptr;
   int made = 0, fail_at = -1;
   if (const char* x = getenv("SWB_COPY_POOL_FAIL_AT")) fail_at = atoi(x);
@@ -2240,6 +2308,7 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
   if (src->keyed) SWB_CLONE(t_cell_label, d_p_cell_label);
   if (have_angle) SWB_CLONE(t_angle, d_p_angle);
   if (have_color) SWB_CLONE(t_color, d_p_color);
+  if (src->n_sets) SWB_CLONE(t_set, d_p_set);
 #undef SWB_CLONE
   if (t_base.fill(pool_base_host, N) || t_len.fill(pool_len_host, N)) return SWB_ERR_HIP;
   HIP_TRY(hipDeviceSynchronize());                 // (the copies are made; work in flight may still read dst's old arrays)
@@ -2249,6 +2318,7 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
   if (src->keyed) dst->d_p_cell_label.swap(t_cell_label);
   if (have_angle) dst->d_p_angle.swap(t_angle);
   if (have_color) dst->d_p_color.swap(t_color);
+  if (src->n_sets) { dst->d_p_set.swap(t_set); if (int rc = publish_entry_sets(dst)) return rc; }
   dst->d_pool_base.swap(t_base); dst->d_pool_len.swap(t_len);
   bump_state_epochs(dst);            // BOTH (dst plays another pool)
   dst->rollout_stale = true;
@@ -2264,6 +2334,82 @@ int swb_copy_pool(swb_handle dst, swb_handle src, const int32_t* pool_base_host,
   HIP_TRY(hipMemsetAsync(dst->d_step_count, 0, sizeof(int32_t) * N, st));
   dst->have_pool = true;
   return restore_run_list_reservation(dst);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Task sets: the table lives in device memory in front of the set of every pool entry (d_p_set,
+// the block), not in the kernel arguments, and the block's pointer behind the override flags: swb_params does not grow.  A handle with a table runs the OV builds of the step kernels -- the ones that carry the lookup --: it owns the
+// override FLAGS (all zero) from here on, the override arrays only once a setter is called (swb_engine::setters).
+// ---------------------------------------------------------------------------------------------------
+int swb_set_task_sets(swb_handle h, int32_t n_sets, const swb_task_set* sets) {
+  if (!h || !sets) return fail(SWB_ERR_INVALID, "swb_set_task_sets: null argument");
+  if (h->n_sets) return fail(SWB_ERR_STATE, "swb_set_task_sets: the handle has its task sets already (set once, after swb_create)");
+  if (h->have_pool) return fail(SWB_ERR_STATE, "swb_set_task_sets: a pool has been installed (call it after swb_create, before any pool)");
+  if (n_sets < 1 || n_sets > SWB_MAX_TASK_SETS)
+    return fail(SWB_ERR_INVALID, "swb_set_task_sets: n_sets = %d is outside [1, %d]", n_sets, SWB_MAX_TASK_SETS);
+  for (int g = 0; g < n_sets; ++g) {
+    const swb_task_set& s = sets[g];
+    if (s.n_tasks < 1 || s.first_task < 0 || (long long)s.first_task + s.n_tasks > h->p.n_tasks)
+      return fail(SWB_ERR_INVALID, "swb_set_task_sets: set %d: sub-tasks [%d, +%d) outside the %d of the handle", g, s.first_task, s.n_tasks,
+                  h->p.n_tasks);
+    if (!s.is_meta && s.n_tasks != 1)
+      return fail(SWB_ERR_INVALID, "swb_set_task_sets: set %d: %d sub-tasks without is_meta (a plain task is one sub-task)", g, s.n_tasks);
+    if (s.is_meta && (s.meta_aggregator < SWB_AGG_SUM || s.meta_aggregator > SWB_AGG_MEAN || s.meta_termination < SWB_TERM_ALL ||
+                      s.meta_termination > SWB_TERM_ANY))
+      return fail(SWB_ERR_INVALID, "swb_set_task_sets: set %d: unknown aggregator %d or termination rule %d", g, s.meta_aggregator,
+                  s.meta_termination);
+    if (s.max_episode_length < 0) return fail(SWB_ERR_INVALID, "swb_set_task_sets: set %d: max_episode_length = %d", g, s.max_episode_length);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (alloc_ov_flags(h)) return SWB_ERR_HIP;
+  h->p.ov_flag = h->d_ov_flag;
+  memset(h->sets, 0, sizeof(h->sets));
+  for (int g = 0; g < n_sets; ++g) {
+    h->sets[g] = sets[g];
+    h->sets[g].is_meta = sets[g].is_meta ? 1 : 0;
+    if (!sets[g].is_meta) { h->sets[g].meta_aggregator = 0; h->sets[g].meta_termination = 0; h->sets[g].meta_terminate_bonus = 0.0; }
+  }
+  h->n_sets = n_sets;
+  bump_state_epochs(h);              // BOTH (nothing is kept across the switch of kernels)
+  return SWB_OK;
+}
+
+static int check_entry_sets_call(swb_handle h, const char* name, const void* arg) {
+  if (!h || !arg) return fail(SWB_ERR_INVALID, "%s: null argument", name);
+  if (!h->n_sets) return fail(SWB_ERR_STATE, "%s: the handle has no task sets (swb_set_task_sets)", name);
+  if (!h->have_pool) return fail(SWB_ERR_STATE, "%s: swb_set_pool has not been called", name);
+  return 0;
+}
+
+int swb_set_entry_task_sets(swb_handle h, const uint8_t* set_of_entry_host, void* stream) {
+  if (int rc = check_entry_sets_call(h, "swb_set_entry_task_sets", set_of_entry_host)) return rc;
+  for (int e = 0; e < h->pool_entries; ++e)
+    if (set_of_entry_host[e] >= h->n_sets)
+      return fail(SWB_ERR_INVALID, "swb_set_entry_task_sets: entry %d names set %d, the handle has %d", e, (int)set_of_entry_host[e], h->n_sets);
+  HIP_TRY(hipSetDevice(h->device));
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(h->d_p_set.ptr + SWB_SET_TABLE_BYTES, set_of_entry_host, (size_t)h->pool_entries, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st)); // (the host array is the caller's, and pageable: it may be gone on return)
+  // the task of running episodes changes: no record stamped before this is reused.  Lists and cached frames do not depend on it.
+  if (++h->task_epoch == 0u) h->task_epoch = 1u;
+  return SWB_OK;
+}
+
+int swb_get_entry_task_sets(swb_handle h, uint8_t* set_of_entry_host) {
+  if (int rc = check_entry_sets_call(h, "swb_get_entry_task_sets", set_of_entry_host)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(set_of_entry_host, h->d_p_set.ptr + SWB_SET_TABLE_BYTES, (size_t)h->pool_entries, hipMemcpyDeviceToHost));
+  return SWB_OK;
+}
+
+int swb_env_task_sets(swb_handle h, int32_t* set_dev, void* stream) {
+  if (int rc = check_entry_sets_call(h, "swb_env_task_sets", set_dev)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  hipLaunchKernelGGL(swb_env_task_sets_kernel, dim3((unsigned)((h->p.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const int32_t*)h->d_entry.ptr, (const uint8_t*)h->d_p_set.ptr + SWB_SET_TABLE_BYTES, set_dev, (int)h->p.N, (int)h->pool_entries);
+  HIP_TRY(hipGetLastError());
+  return SWB_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2312,7 +2458,7 @@ struct env_override {
 };
 
 int ov_allocate(swb_engine* h) {
-  if (h->d_ov_flag) return 0;
+  if (h->setters) return 0;
   const size_t N = h->p.N, NS = N * h->p.S, T = h->p.n_tasks;
   int rc = 0;
   rc |= h->d_ov_shape.fill(nullptr, NS);
@@ -2321,8 +2467,9 @@ int ov_allocate(swb_engine* h) {
   rc |= h->d_ov_label.fill(nullptr, NS * T);
   rc |= h->d_ov_cpath.fill(nullptr, NS * SWB_MAX_SHAPE_VERTS * 2);
   if (h->keyed) rc |= h->d_ov_cell_label.fill(nullptr, NS * T * SWB_MAX_CELLS);
-  rc |= h->d_ov_flag.fill(nullptr, N);       // last: its presence switches the engine to the OV kernels
+  rc |= alloc_ov_flags(h);                   // last: its presence switches the engine to the OV kernels
   if (rc) return SWB_ERR_HIP;
+  h->setters = true;
   swb_params& p = h->p;
   p.ov_flag = h->d_ov_flag; p.ov_shape = h->d_ov_shape; p.ov_scale = h->d_ov_scale; p.ov_angle = h->d_ov_angle;
   p.ov_label = h->d_ov_label; p.ov_cpath = h->d_ov_cpath;

@@ -33,6 +33,7 @@
 //
 // Arithmetic follows oracle/sw_oracle.c operation for operation (which is pinned against the
 // unmodified reference); reference citations are on each device function.
+#ifndef SWB_SETS_PASS       // (the second pass of this file over itself compiles two kernel bodies only: see swb_cover_kernel)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -202,7 +203,11 @@ struct swb_params {
   // OV = true kernels, which an engine launches once a setter has been called; an environment whose flag is
   // set takes shape / scale / labels / centred paths of its sprites from these arrays instead of the pool,
   // until its next reset clears the flag.  (Appended last: the other kernels' argument offsets do not move.)
-  uint8_t* ov_flag;            // [N]
+  uint8_t* ov_flag;            // [N]; then, on a 64-byte line of its own (SWB_OV_SLOT), ONE device pointer: the task-set block
+                               // of the handle (swb_set_task_sets; DESIGN.md section 31) -- SWB_SET_TABLE_BYTES of
+                               // swb_task_set[SWB_MAX_TASK_SETS], then [P] the set of every pool entry -- or NULL.  It hangs
+                               // here, behind memory only the OV kernels read, so that this block does not grow by a byte:
+                               // the kernels of handles without task sets, their argument sizes and offsets stay what they were
   const int32_t* ov_shape;     // [N][S]
   const double* ov_scale;      // [N][S]
   const double* ov_angle;      // [N][S]  degrees (SpriteFactors observation)
@@ -253,6 +258,36 @@ struct swb_params {
   uint32_t task_epoch;         // never 0: a zeroed record is stale
   uint32_t task_pad_;
   unsigned long long* task_stats;   // [2] stepping waves that reused / evaluated the task (SWB_LIST_STATS; else NULL)
+};
+
+#define SWB_SET_TABLE_BYTES ((int)(SWB_MAX_TASK_SETS * sizeof(swb_task_set)))    // the table in front of the entries' bytes
+#define SWB_OV_SLOT(N) (((size_t)(N) + 63) & ~(size_t)63)                        // offset of the block's pointer behind ov_flag[N]
+#define SWB_OV_FLAG_BYTES(N) (SWB_OV_SLOT(N) + 64)
+// The task of one environment's episode, all wave-uniform: sub-tasks tasks[first() .. first() + n()) -- rows first() .. of the
+// labels, too --, how they are aggregated, and when the episode times out.  SETS = false: the handle's one task, every member
+// read from the config block where it is used -- the code of the kernels that know no task sets is the code they had before
+// there were any.  SETS = true (task_view_of): the set the episode's pool entry names, or the config block where the block's pointer is NULL.
+template <bool SETS> struct task_view;
+template <> struct task_view<false> {
+  const swb_params& p;
+  __device__ __forceinline__ int first() const { return 0; }
+  __device__ __forceinline__ int n() const { return p.n_tasks; }
+  __device__ __forceinline__ int is_meta() const { return p.is_meta; }
+  __device__ __forceinline__ int aggregator() const { return p.meta_aggregator; }
+  __device__ __forceinline__ int termination() const { return p.meta_termination; }
+  __device__ __forceinline__ int max_episode_length() const { return p.max_episode_length; }
+  __device__ __forceinline__ double terminate_bonus() const { return p.meta_terminate_bonus; }
+};
+template <> struct task_view<true> {
+  int first_, n_, is_meta_, aggregator_, termination_, max_episode_length_;
+  double terminate_bonus_;
+  __device__ __forceinline__ int first() const { return first_; }
+  __device__ __forceinline__ int n() const { return n_; }
+  __device__ __forceinline__ int is_meta() const { return is_meta_; }
+  __device__ __forceinline__ int aggregator() const { return aggregator_; }
+  __device__ __forceinline__ int termination() const { return termination_; }
+  __device__ __forceinline__ int max_episode_length() const { return max_episode_length_; }
+  __device__ __forceinline__ double terminate_bonus() const { return terminate_bonus_; }
 };
 
 // --------------------------------------------------------------------------------------------
@@ -621,34 +656,35 @@ __device__ __forceinline__ int task_clustering_wave(const swb_task& t, int pos_f
 }
 
 // task.reward + task.success incl. tasks.py:248-296 MetaAggregated; all lanes, uniform result.
-// n_tasks: swb_params::n_tasks -- or -1 from a caller that will not use the result (finish_step: no task is evaluated then,
+// tv: the task of the episode (task_view_of); sub-task t of it is swb_params::tasks[tv.first() + t], its labels row tv.first() + t.
+// n_tasks: tv.n() -- or -1 from a caller that will not use the result (finish_step: no task is evaluated then,
 // nothing of the scratch but MetaAggregated's own words is touched, and what comes back is not meaningful).
-template <typename SC>
-__device__ __forceinline__ int eval_task_wave(const swb_params& p, int n_tasks, int n, double px, double py, const int8_t* label,
-                                              SC* sc, double* reward, int* success) {
+template <typename TV, typename SC>
+__device__ __forceinline__ int eval_task_wave(const swb_params& p, const TV& tv, int n_tasks, int n, double px, double py,
+                                              const int8_t* label, SC* sc, double* reward, int* success) {
   const int l = lane_id();
   int err = 0;
   double r0 = 0.0;
   int ok0 = 0;
   for (int t = 0; t < n_tasks; ++t) {
-    const swb_task& tk = p.tasks[t];
-    const int8_t* lab = label + t * p.S;
+    const swb_task& tk = p.tasks[tv.first() + t];
+    const int8_t* lab = label + (tv.first() + t) * p.S;
     double r = 0.0;
     int ok = 0;
     if (tk.kind == SWB_TASK_FIND_GOAL) task_find_goal_wave(tk, n, px, py, lab, sc, &r, &ok);
     else if (tk.kind == SWB_TASK_CLUSTERING) err |= task_clustering_wave(tk, p.pos_is_f32, n, px, py, lab, sc, &r, &ok);
     if (t == 0) { r0 = r; ok0 = ok; }
-    if (p.is_meta && l == 0) { sc->tr[t] = r; sc->tok[t] = ok; }
+    if (tv.is_meta() && l == 0) { sc->tr[t] = r; sc->tok[t] = ok; }
   }
-  if (!p.is_meta) { *reward = r0; *success = ok0; return err; }
+  if (!tv.is_meta()) { *reward = r0; *success = ok0; return err; }
   wave_sync();
   const double* r = sc->tr;
   const int* ok = sc->tok;
-  int succ = (p.meta_termination == SWB_TERM_ALL);
-  for (int t = 0; t < n_tasks; ++t) succ = (p.meta_termination == SWB_TERM_ALL) ? (succ && ok[t]) : (succ || ok[t]);
+  int succ = (tv.termination() == SWB_TERM_ALL);
+  for (int t = 0; t < n_tasks; ++t) succ = (tv.termination() == SWB_TERM_ALL) ? (succ && ok[t]) : (succ || ok[t]);
   double agg;
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-  if (p.meta_aggregator == SWB_AGG_SUM || p.meta_aggregator == SWB_AGG_MEAN) {
+  if (tv.aggregator() == SWB_AGG_SUM || tv.aggregator() == SWB_AGG_MEAN) {
     // np.nansum / np.nanmean over the sub-task rewards (uniform: every lane sums the same values)
     int cnt = 0;
     double v[SWB_MAX_TASKS];
@@ -666,16 +702,16 @@ __device__ __forceinline__ int eval_task_wave(const swb_params& p, int n_tasks, 
     } else {
       agg = __dadd_rn(__dadd_rn(__dadd_rn(v[0], v[1]), __dadd_rn(v[2], v[3])), __dadd_rn(__dadd_rn(v[4], v[5]), __dadd_rn(v[6], v[7])));
     }
-    if (p.meta_aggregator == SWB_AGG_MEAN) agg = __ddiv_rn(agg, (double)cnt);
+    if (tv.aggregator() == SWB_AGG_MEAN) agg = __ddiv_rn(agg, (double)cnt);
   } else {
     agg = qnan;
     for (int t = 0; t < n_tasks; ++t) {
       if (r[t] != r[t]) continue;
       if (agg != agg) agg = r[t];
-      else if (p.meta_aggregator == SWB_AGG_MAX ? (r[t] > agg) : (r[t] < agg)) agg = r[t];
+      else if (tv.aggregator() == SWB_AGG_MAX ? (r[t] > agg) : (r[t] < agg)) agg = r[t];
     }
   }
-  agg = __dadd_rn(agg, __dmul_rn(p.meta_terminate_bonus, (double)succ));
+  agg = __dadd_rn(agg, __dmul_rn(tv.terminate_bonus(), (double)succ));
   *reward = agg;
   *success = succ;
   wave_sync();
@@ -878,16 +914,39 @@ __device__ __forceinline__ void park_task_record(const swb_params& p, uint32_t w
   if (p.task_cache != nullptr && lane_id() < 4) tscratch->pres[lane_id()] = w;
 }
 
+// The task of the episode in pool entry `en` (wave-uniform).  Only the SETS builds (swb_cover_sets_kernel, swb_ms_state_sets_kernel) look a task set up (behind swb_params::ov_flag): the
+// others are the kernels of handles without task sets, and take the config block as constants of the launch.
+template <bool SETS>
+__device__ __forceinline__ task_view<SETS> task_view_of(const swb_params& p, int en) {
+  if constexpr (SETS) {
+    task_view<true> v{0, p.n_tasks, p.is_meta, p.meta_aggregator, p.meta_termination, p.max_episode_length, p.meta_terminate_bonus};
+    // (pointer, byte and record are the host's, written by no wave -- the pointer's line holds no flag --: uniform loads through
+    // the constant address space, the byte made a scalar as the mask's is)
+    const uint8_t* const p_set = *as_const(reinterpret_cast<const uint8_t* const*>(p.ov_flag + SWB_OV_SLOT(p.N)));
+    if (p_set != nullptr) {
+      const int g = min(rfl((int)as_const(p_set)[SWB_SET_TABLE_BYTES + (size_t)en]), SWB_MAX_TASK_SETS - 1);
+      static_assert(sizeof(swb_task_set) == 32 && offsetof(swb_task_set, meta_terminate_bonus) == 24, "six ints and a double");
+      const auto w = as_const(reinterpret_cast<const int32_t*>(p_set)) + 8 * g;
+      const double bonus = as_const(reinterpret_cast<const double*>(p_set))[4 * g + 3];
+      v = task_view<true>{w[0], w[1], w[2], w[3], w[4], w[5], bonus};
+    }
+    return v;
+  } else {
+    return task_view<false>{p};
+  }
+}
+
 // Task reward / success (spread over the lanes), out-of-frame, termination; the outputs of the step.  Returns the error
 // bits of the environment (lane 0; the caller stores them).
 // CACHE (swb_params::task_cache; the caller has run stage_task_record): a step that is no reset and moved no sprite takes the
 // task's reward, success and error bits from the environment's record when it carries the launch's epoch -- the error bits as
 // a fresh evaluation would return them (p.error is sticky and the caller may have cleared it); every other step evaluates and
 // leaves the record.  CACHE = false: a caller on forked parameter blocks (the rollout kernels) compiles all of it out.
-template <bool OV, bool CACHE = true, typename SC>
+template <bool OV, bool CACHE = true, bool SETS = false, typename SC>
 __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, const env_state& es, const step_cost& c, SC* tscratch) {
   const int l = lane_id(), S = p.S, n = es.n;
   const double px = es.px, py = es.py;
+  const task_view<SETS> tv = task_view_of<SETS>(p, es.en);
   wave_sync();
   // tasks.py:134-137, 196-205: `contains(sprite.factors)` is evaluated at every step and x / y are factors -- a task whose
   // filter keys on position takes every sprite's label from the cell of the task's grid the sprite stands in NOW (lanes =
@@ -895,7 +954,7 @@ __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, co
   if (p.p_cell_label != nullptr) {                     // (wave-uniform; no shipped configuration)
     const int8_t* cells = p.p_cell_label + (size_t)es.en * p.n_tasks * S * SWB_MAX_CELLS;
     if constexpr (OV) { if (es.ov && p.ov_cell_label) cells = p.ov_cell_label + (size_t)env * p.n_tasks * S * SWB_MAX_CELLS; }
-    for (int t = 0; t < p.n_tasks; ++t) {
+    for (int t = tv.first(); t < tv.first() + tv.n(); ++t) {
       const swb_task& tk = p.tasks[t];
       if (tk.n_xcuts + tk.n_ycuts == 0) continue;
       if (l < n) {
@@ -914,7 +973,7 @@ __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, co
   // has a run-time trip count already, so the kernel's control flow -- and with it the register allocation of the cover builds,
   // which a branch around the whole evaluation cost two spilled VGPRs each -- stays what it was.  No fence is needed between
   // the stamp's read and an evaluation's writes to `pres`: the loop is entered on a count that depends on the value read.)
-  int n_tasks = p.n_tasks;                              // (wave-uniform; -1: the record is reused)
+  int n_tasks = tv.n();                                 // (wave-uniform; -1: the record is reused)
   if constexpr (CACHE) {
     if (p.task_cache != nullptr) {
       // (every lane reads the same word and decides the same; the decision goes through a ballot so that the compiler KNOWS the
@@ -923,7 +982,7 @@ __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, co
       if (__ballot(stamp != p.task_epoch || c.changed || es.first) == 0ull) n_tasks = -1;
     }
   }
-  int terr = eval_task_wave(p, n_tasks, n, px, py, tscratch->labels, tscratch, &tr, &ok);
+  int terr = eval_task_wave(p, tv, n_tasks, n, px, py, tscratch->labels, tscratch, &tr, &ok);
   const bool reuse = CACHE && n_tasks < 0;
   if constexpr (CACHE) {
     if (reuse) {                                        // (no task ran: `pres` still holds the record)
@@ -955,10 +1014,15 @@ __device__ __forceinline__ uint32_t finish_step(const swb_params& p, int env, co
     } else {
       // :101 reward += task.reward.  A float32 cost plus a Python-float task reward (NoReward,
       // Clustering) stays float32 under NEP 50; np.float64 rewards promote to float64.
-      const bool task_is_pyfloat = !p.is_meta && p.tasks[0].kind != SWB_TASK_FIND_GOAL;
+      const bool task_is_pyfloat = !tv.is_meta() && p.tasks[tv.first()].kind != SWB_TASK_FIND_GOAL;
       const double rew = (c.cost_is_f32 && task_is_pyfloat) ? (double)__fadd_rn(c.cost_f32, (float)tr) : __dadd_rn(c.cost, tr);
       if (p.reward) p.reward[env] = rew;
-      const int timeout = c.step_count >= p.max_episode_length;          // :84
+      // (:84.  Two copies of one expression ON PURPOSE: behind the accessor the compiler hoists the plain builds' load of
+      // max_episode_length out of the short-circuit below, and they would no longer be, instruction for instruction, the kernels
+      // they were before task sets -- which is checked by diffing their assembly, profiles/r25_task_sets.md.  Do not fold.)
+      int timeout;
+      if constexpr (SETS) timeout = c.step_count >= tv.max_episode_length();
+      else timeout = c.step_count >= p.max_episode_length;
       const int last = ok || oof || timeout;                             // :104-106
       p.step_count[env] = c.step_count;
       if (last) p.reset_next[env] = 1;
@@ -2137,15 +2201,30 @@ __device__ __forceinline__ void spec_copy_group(const swb_params& p, uint32_t c)
 
 // --------------------------------------------------------------------------------------------
 // Kernel 1 of a step, "cover": P0 state, P1 geometry, P2 coverage -> run lists.  One wave = one environment.
+#endif                      // SWB_SETS_PASS
 // --------------------------------------------------------------------------------------------
 // OV = true: the build an engine switches to once swb_set_sprite_attr has been called (environments may carry
 // per-sprite overrides of shape / scale / centred path, see swb_params::ov_flag); OV = false compiles to exactly
 // the kernel without that feature.
 // PAINT = true: anti_aliasing = 1 and an image of up to 64 columns (the canvas fits NW = 2) -- the wave paints the frame itself,
 // there is no second kernel; a build of its own so that neither kernel carries the other's copy of the coverage code.
+// SETS = true (with OV = true): swb_cover_sets_kernel, the build of handles with task sets (swb_set_task_sets; DESIGN.md section
+// 31) -- finish_step looks the episode's task up by its pool entry.  A kernel of its own name, instantiated in swb_wide.hip: the
+// OV = false / true builds, and the code object they live in, stay byte for byte what they were before there were task sets.
+// How two kernels share one body without sharing a function (which changed the plain builds' code when it was tried): this file
+// includes ITSELF once more, in swb_wide.hip only, with SWB_SETS_PASS defined -- the pass compiles nothing but the two kernel
+// bodies marked for it, under the names and flags of the task-set builds.
+#ifdef SWB_SETS_PASS
+template <int NW, bool PAINT>
+__global__ void __launch_bounds__(SWB_WAVE, SWB_COVER_WAVES(NW))
+swb_cover_sets_kernel(const swb_params p) {
+  constexpr bool OV = true, SETS = true;
+#else
 template <int NW, bool OV = false, bool PAINT = false>
 __global__ void __launch_bounds__(SWB_WAVE, SWB_COVER_WAVES(NW))
 swb_cover_kernel(const swb_params p) {
+  constexpr bool SETS = false;
+#endif
   static_assert(!PAINT || NW == 2, "painting in the cover kernel: images of up to 64 columns at anti_aliasing = 1");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // The copy workgroups of a launch with a frame cache (swb_params::spec_copy, never in the painting builds): behind the N
@@ -2298,7 +2377,7 @@ swb_cover_kernel(const swb_params p) {
   const double px = es.px, py = es.py;
   SWB_HOOK_PHASE_END(4)
   if (p.render_only != 1 && es.active) {                // (no part in the step: no task, no outputs -- skipped, not masked)
-    err |= finish_step<OV>(p, env, es, sc, tscratch);
+    err |= finish_step<OV, true, SETS>(p, env, es, sc, tscratch);
     wave_sync();                                        // (the scratch aliases the span lists)
   }
   SWB_HOOK_PHASE_END(5)
@@ -2566,6 +2645,10 @@ swb_cover_kernel(const swb_params p) {
   if (l == 0 && p.list_epoch != 0u) hdr[SWB_RHDR_CYCLES] = own_cycles;
   }   // !PAINT
 }
+#ifndef SWB_SETS_PASS      // ---- (the rest of the file, down to the many-sprite state kernel, is not part of the pass)
+// the build of handles with task sets; defined by the pass, explicitly instantiated in swb_wide.hip at every width
+template <int NW, bool PAINT = false>
+__global__ void swb_cover_sets_kernel(const swb_params p);
 
 // --------------------------------------------------------------------------------------------
 // Kernel 2 of a step, "resample" (anti_aliasing > 1): P3 + P4 for one (environment, group of 64 output columns,
@@ -3264,9 +3347,17 @@ struct swb_ms_lds {
 };
 static_assert(SWB_MAX_SPRITES <= SWB_WAVE && SWB_MAX_SHAPE_VERTS <= SWB_WAVE, "one lane per sprite / per vertex");
 
+#endif                     // ---- SWB_SETS_PASS
+#ifdef SWB_SETS_PASS
+__global__ void __launch_bounds__(SWB_WAVE)
+swb_ms_state_sets_kernel(const swb_params p) {
+  constexpr bool OV = true, SETS = true;
+#else
 template <bool OV>
 __global__ void __launch_bounds__(SWB_WAVE)
 swb_ms_state_kernel(const swb_params p) {
+  constexpr bool SETS = false;
+#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int l = lane_id();
   const int env = blockIdx.x;
@@ -3300,10 +3391,29 @@ swb_ms_state_kernel(const swb_params p) {
   };
   const step_cost sc = act_and_move(p, env, es, hit);
   if (p.render_only != 1 && es.active) {
-    const uint32_t err = finish_step<OV>(p, env, es, sc, tscratch);
+    const uint32_t err = finish_step<OV, true, SETS>(p, env, es, sc, tscratch);
     if (l == 0 && p.error && err) p.error[env] |= (uint8_t)err;         // sticky: the caller clears
   }
 }
+#ifndef SWB_SETS_PASS      // ---- (to the end of the file)
+
+// The kernels of handles with task sets live in swb_wide.hip's code object: the one of swb.hip stays what it was.
+__global__ void swb_ms_state_sets_kernel(const swb_params p);
+__global__ void swb_env_task_sets_kernel(const int32_t* entry, const uint8_t* set_of_entry, int32_t* out, int N, int entries);
+#ifdef SWB_WIDE_TU
+#define SWB_SETS_PASS 1
+#include "swb_kernels.hip.inc"
+#undef SWB_SETS_PASS
+// swb_env_task_sets: the set of the entry every environment is in (entries: the pool's; an entry outside it -- none is ever
+// written -- reads entry 0)
+__global__ void __launch_bounds__(256)
+swb_env_task_sets_kernel(const int32_t* entry, const uint8_t* set_of_entry, int32_t* out, int N, int entries) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const int e = entry[n];
+  out[n] = (int32_t)set_of_entry[(e >= 0 && e < entries) ? e : 0];
+}
+#endif
 
 // --------------------------------------------------------------------------------------------
 // Rollouts (swb_rollout): what would M candidate action sequences of K steps earn from where every environment is NOW?
@@ -3673,3 +3783,4 @@ swb_rollout_guided_kernel(const swb_rollout_args a, int S, const swb_rollout_kee
   }
 }
 #endif  // SWB_WIDE_TU
+#endif  // SWB_SETS_PASS

@@ -90,7 +90,9 @@ class Engine(object):
   def _stream(self):
     return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-  def __init__(self, cfg, pool, device=0):
+  def __init__(self, cfg, pool, device=0, task_sets=None):
+    """task_sets: a list of _abi.SwbTaskSet (swb_set_task_sets), installed before the pool; `pool.task_set` then names the set
+    of every entry.  None: one task for the whole batch, the one `cfg` holds."""
     self.lib, self.device = self._open(device)
     self.cfg = cfg
     self.N, self.S = cfg.n_envs, cfg.max_sprites
@@ -110,6 +112,9 @@ class Engine(object):
         self._check(self.lib.swb_upload_resample(self._h, axis, out_size, coeffs.shape[1],
                                                  _ptr(bounds), _ptr(coeffs)))
     self.pool = None
+    self.task_set_table = None
+    if task_sets is not None:
+      self.set_task_sets(task_sets)
     if pool is not None:
       self.set_pool(pool)
     with self._device_scope():
@@ -149,11 +154,61 @@ class Engine(object):
     except Exception:  # pylint: disable=broad-except
       pass
 
+  def set_task_sets(self, task_sets):
+    """Installs the table of task sets (a list of _abi.SwbTaskSet; swb_set_task_sets): once, before any pool.  From then on
+    the task of an episode is the set its pool entry names (`Pool.task_set`, `set_entry_task_sets`); rollouts are refused."""
+    table = (_abi.SwbTaskSet * len(task_sets))(*task_sets)
+    self._check(self.lib.swb_set_task_sets(self._h, len(task_sets), table))
+    self.task_set_table = list(task_sets)
+
+  @property
+  def num_task_sets(self):
+    return len(self.task_set_table) if self.task_set_table is not None else 0
+
   def set_pool(self, pool):
+    if getattr(pool, 'task_set', None) is not None and self.task_set_table is None:
+      raise ValueError('the pool names a task set per entry (Pool.task_set) but the engine has no task sets (set_task_sets)')
     self.pool = pool
     cpool = pool.as_struct()
     self._check(self.lib.swb_set_pool(self._h, C.byref(cpool)))
     self._rendered = 0        # (a new pool restores the lists' full reservation: trimmed again after TRIM_AFTER launches)
+    if getattr(pool, 'task_set', None) is not None:       # (right after the pool: swb_set_pool put every entry in set 0)
+      self.set_entry_task_sets(pool.task_set)
+
+  def _n_pool_entries(self):
+    return self.pool.n_entries if self.pool is not None else getattr(self, '_pool_entries', 0)
+
+  def set_entry_task_sets(self, set_of_entry):
+    """The set of every pool entry (u8[P]; swb_set_entry_task_sets): takes effect at once, for running episodes too.
+    The labels are the pool's: an entry moved to another set is evaluated against the label rows of THAT set's sub-tasks as
+    the pool holds them.  `lowering.lower_task_sets` and the device samplers fill every row of every entry;
+    `lowering.merge_task_sets` (`workloads.build_task_sets`) fills only the rows of the set an entry was built for -- its scenes
+    come from different workloads --, the others are 0: on such a pool reassign only after filling those rows yourself."""
+    a = np.ascontiguousarray(set_of_entry)
+    if a.shape != (self._n_pool_entries(),) or a.dtype.kind not in 'iub':
+      raise ValueError('set_entry_task_sets takes an integer array of shape [%d], got %s %s' % (self._n_pool_entries(), a.dtype, a.shape))
+    if a.size and (a.min() < 0 or a.max() > 255):
+      raise ValueError('set_entry_task_sets: a task set index outside [0, 255]')
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    self._check(self.lib.swb_set_entry_task_sets(self._h, _ptr(a), self._stream()))
+    if self.pool is not None:
+      self.pool.task_set = a.copy()
+
+  def entry_task_sets(self):
+    """u8[P]: the set of every pool entry as the device holds it (swb_get_entry_task_sets; blocking)."""
+    a = np.zeros(self._n_pool_entries(), np.uint8)
+    self._check(self.lib.swb_get_entry_task_sets(self._h, _ptr(a)))
+    return a
+
+  def task_sets(self):
+    """i32[N] device tensor: the task set of the episode every environment is in (swb_env_task_sets: one small kernel,
+    asynchronous) -- what an agent trained on a mix of tasks conditions on.  The tensor is the engine's and is overwritten
+    by the next call."""
+    if getattr(self, '_env_sets', None) is None:
+      with self._device_scope():
+        self._env_sets = torch.zeros(self.N, dtype=torch.int32, device=self.device)
+    self._check(self.lib.swb_env_task_sets(self._h, C.c_void_p(self._env_sets.data_ptr()), self._stream()))
+    return self._env_sets
 
   def sample_pool(self, spec, n_entries, pool_base, pool_len, seed, first_entry=0):
     """Draws `n_entries` episodes on the device from an _abi.SwbSampler (swb_sample_pool)."""
@@ -202,6 +257,8 @@ class Engine(object):
       pool.cell_label = np.zeros((n, self.cfg.n_tasks, self.S, _abi.SWB_MAX_CELLS), np.int8)
     cpool = pool.as_struct()
     self._check(self.lib.swb_get_pool(self._h, C.byref(cpool)))
+    if self.task_set_table is not None:
+      pool.task_set = self.entry_task_sets()
     return pool
 
   def reset_all(self):

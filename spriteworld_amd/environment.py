@@ -120,10 +120,45 @@ class EnvironmentError_(RuntimeError):
 class BatchedEnvironment(object):
   """N independent Spriteworld environments stepped by the HIP engine (two kernels per step, csrc/swb_kernels.hip.inc)."""
 
+  @classmethod
+  def from_configs(cls, configs, num_envs, task_set_of_entry='cycle', **kwargs):
+    """One BatchedEnvironment whose episodes are played under the tasks of several reference-style config dicts (`task`,
+    `action_space`, `renderers`, `init_sprites`, optionally `keep_in_frame`, `max_episode_length`, `metadata`): multi-task
+    training in one batch.  The dicts must agree on the action space (class and parameters), the renderers and keep_in_frame
+    -- LoweringError names the field otherwise -- and may differ in `task`, `init_sprites` and `max_episode_length`.
+    task_set_of_entry: which config entry k of environment n is played under -- 'cycle': (n + k) mod G; 'per_env': n mod G; or
+    an int array [num_envs, episodes_per_env].
+    Where every config shares ONE `init_sprites` object the episodes are drawn on the device as for a single config
+    (`device_reset`: 'auto', True or 'tree'), the sampler lowered against the sub-tasks of all configs, and the pool is
+    refreshed as usual.  Otherwise entry (n, k) is drawn on the host from its own config's `init_sprites`: 'auto' does that
+    silently, True / 'tree' raise LoweringError.  Either way every entry is labelled for every config's task.
+    `task_sets()` says which config every environment is playing now, `set_task_set_of_entry()` changes the assignment;
+    resets, masked steps, snapshots, `fork` and `run_episodes` work unchanged, the rollouts and `plan_cem` raise.
+    kwargs: the other arguments of the constructor (episodes_per_env, device, check_errors, action_dtype, ...)."""
+    configs = [dict(c) for c in configs]
+    if not 1 <= len(configs) <= _abi.SWB_MAX_TASK_SETS:
+      raise lowering.LoweringError('between 1 and %d configs supported, got %d' % (_abi.SWB_MAX_TASK_SETS, len(configs)))
+    lowering.check_shared_config(configs)
+    first = configs[0]
+    device_reset = kwargs.pop('device_reset', 'auto')
+    if not all(c['init_sprites'] is first['init_sprites'] for c in configs):
+      if device_reset not in ('auto', False, None, 0):
+        raise lowering.LoweringError('device-side reset sampling under task sets needs every config to share one init_sprites '
+                                     'object; these draw from different ones (device_reset=\'auto\' samples them on the host)')
+      device_reset = False
+    which = lowering.task_set_assignment(task_set_of_entry, num_envs, int(kwargs.get('episodes_per_env', 8)), len(configs))
+    return cls(task=lowering.ConcatenatedTasks([c['task'] for c in configs]), action_space=first['action_space'],
+               renderers=first['renderers'], init_sprites=first['init_sprites'], keep_in_frame=first.get('keep_in_frame', True),
+               max_episode_length=max(c.get('max_episode_length', 1000) for c in configs), metadata=first.get('metadata'),
+               num_envs=num_envs, device_reset=device_reset, _task_sets=(configs, which), **kwargs)
+
   def __init__(self, task, action_space, renderers, init_sprites, keep_in_frame=True,
                max_episode_length=1000, metadata=None, num_envs=1, episodes_per_env=8,
                max_sprites=None, device=0, check_errors=32, action_dtype=np.float64,
-               global_env_offset=0, device_reset='auto', refresh_every='auto', seed=None):
+               global_env_offset=0, device_reset='auto', refresh_every='auto', seed=None, _task_sets=None):
+    # _task_sets (from_configs only; DESIGN.md section 31): (the config dicts, u8[N, episodes_per_env] the set of every pool
+    # entry); `task` is then lowering.ConcatenatedTasks of the configs' tasks -- what labels are lowered against
+    self._configs, self._set_of_entry = _task_sets if _task_sets is not None else (None, None)
     self._task = task
     self._action_space = action_space
     self._renderers = renderers
@@ -199,26 +234,71 @@ class BatchedEnvironment(object):
     ns = getattr(action_space, '_noise_scale', None)
     if ns:
       action_dtype = np.float64
-    self._cfg = lowering.lower_config(task, action_space, renderers, keep_in_frame,
-                                      max_episode_length, self._num_envs, S,
-                                      pos_is_f32=(pos_dt == np.float32), action_dtype=action_dtype)
+    if self._configs is None:
+      self._cfg, sets = lowering.lower_config(task, action_space, renderers, keep_in_frame, max_episode_length, self._num_envs, S,
+                                              pos_is_f32=(pos_dt == np.float32), action_dtype=action_dtype), None
+    else:                             # task sets: one sub-task table, one set per config
+      self._cfg, sets = lowering.merge_task_set_configs([
+          lowering.lower_config(c['task'], action_space, renderers, keep_in_frame, c.get('max_episode_length', 1000),
+                                self._num_envs, S, pos_is_f32=(pos_dt == np.float32), action_dtype=action_dtype)
+          for c in self._configs])
     self._noise_scale = None if not ns else torch.as_tensor(np.asarray(ns, dtype=np.float64))
     self._noise_gen = None
     self._action_seed, self._action_draws = None, 0      # device action sampling (seed_actions / _next_action_seed)
     if self._sampler is not None:
       self._sampler_spec = self._sampler.lower(task, renderers)
-      self._engine = _engine.Engine(self._cfg, None, device=device)
+      self._engine = self._new_engine(sets, device)
       self.refill_pool()
-    else:
-      pool = lowering.lower_episodes(episodes, task, renderers, max_sprites=S)
-      pool.assign_round_robin(self._num_envs, self._episodes_per_env)
-      self._engine = _engine.Engine(self._cfg, pool, device=device)
+    elif sets is None:
+      self._engine = _engine.Engine(self._cfg, self._lower_pool(episodes), device=device)
+    else:                             # (the sets go in before the pool, the pool's entry sets right behind it)
+      self._engine = self._new_engine(sets, device)
+      self._engine.set_pool(self._lower_pool(episodes))
     self._render = self._pil is not None
     self._attr_assigned = {}      # (env, sprite, 'angle' | 'scale') -> (episode, the assigned value was an np.float32)
 
   # ------------------------------------------------------------------ pool
   def _draw_episodes(self):
+    if self._configs is not None:     # entry (n, k) from the init_sprites of its own set
+      return [list(self._configs[g]['init_sprites']()) for g in self._set_of_entry.reshape(-1)]
     return [list(self._init_sprites()) for _ in range(self._num_envs * self._episodes_per_env)]
+
+  def _new_engine(self, sets, device):
+    """An engine without a pool yet, with its task sets installed (an engine stand-in need not know the keyword)."""
+    eng = _engine.Engine(self._cfg, None, device=device)
+    if sets is not None:
+      eng.set_task_sets(sets)
+    return eng
+
+  def _lower_pool(self, episodes):
+    """The host pool of `episodes`; with task sets every entry is labelled for the sub-tasks of every set and names its own."""
+    pool = lowering.lower_episodes(episodes, self._task, self._renderers, max_sprites=self._max_sprites)
+    pool.assign_round_robin(self._num_envs, self._episodes_per_env)
+    if self._configs is not None:
+      pool.task_set = np.ascontiguousarray(self._set_of_entry.reshape(-1), dtype=np.uint8)
+    return pool
+
+  # ------------------------------------------------------------------ task sets
+  @property
+  def num_task_sets(self):
+    """The number of task sets (configs of `from_configs`); 0: one task for the whole batch."""
+    return self._engine.num_task_sets
+
+  def task_sets(self):
+    """i32[N] device tensor: the task set (the index of the config) of the episode every environment is in -- what an agent
+    trained on the mix conditions on.  One small kernel, no host synchronisation."""
+    return self._engine.task_sets()
+
+  def set_task_set_of_entry(self, task_set_of_entry):
+    """Changes which task set the pool entries are played under ('cycle', 'per_env' or an int array [N, episodes_per_env]).
+    Takes effect at once, for running episodes too: every entry carries the labels of every set's sub-tasks.  Entries are
+    not redrawn: with configs that draw from different `init_sprites` an entry keeps the sprites of the config it was drawn
+    for (`refill_pool()` draws a fresh pool under the new assignment)."""
+    if self._configs is None:
+      raise lowering.LoweringError('set_task_set_of_entry: the environment has no task sets (BatchedEnvironment.from_configs)')
+    which = lowering.task_set_assignment(task_set_of_entry, self._num_envs, self._episodes_per_env, len(self._configs))
+    self._engine.set_entry_task_sets(which.reshape(-1))
+    self._set_of_entry = which
 
   def refill_pool(self):
     """Draws a fresh pool with init_sprites(); every environment restarts (next step is FIRST).
@@ -230,12 +310,10 @@ class BatchedEnvironment(object):
       sample = self._engine.sample_pool_tree if self._tree_sampled else self._engine.sample_pool
       sample(self._sampler_spec, self._num_envs * k, base, np.full(self._num_envs, k, np.int32), self._sampler.next_seed(),
              first_entry=self._global_env_offset * k)
+      if self._configs is not None:   # (a pool call puts every entry in set 0; refresh_pool -- swb_resample_pool -- keeps the sets)
+        self._engine.set_entry_task_sets(self._set_of_entry.reshape(-1))
       return
-    episodes = self._draw_episodes()
-    pool = lowering.lower_episodes(episodes, self._task, self._renderers,
-                                   max_sprites=self._max_sprites)
-    pool.assign_round_robin(self._num_envs, self._episodes_per_env)
-    self._engine.set_pool(pool)
+    self._engine.set_pool(self._lower_pool(self._draw_episodes()))
 
   @property
   def _tree_sampled(self):
@@ -664,6 +742,8 @@ class BatchedEnvironment(object):
     base, length = self._pool_ranges()
     child._ranges = (np.repeat(base, M), np.repeat(length, M))
     child._engine = _engine.Engine(child._cfg, None, device=self._engine.device.index or 0)
+    if self._engine.task_set_table is not None:          # (the sets first: swb_copy_pool refuses handles whose tables differ)
+      child._engine.set_task_sets(self._engine.task_set_table)
     child._engine.copy_pool_from(self._engine, *child._ranges)
     child._engine.load_state(self._engine.save_state(), torch.arange(N * M, device=self._engine.device) // M)
     return child

@@ -187,9 +187,17 @@ def cell_labels_of(sub, sprite, xcuts, ycuts, pos_dtype):
   return cells
 
 
+class ConcatenatedTasks(object):
+  """The sub-tasks of several tasks in the order of a handle's sub-task table (task sets): what the labels of a pool that
+  serves every set -- the device samplers' -- are lowered against.  Not a task: it has no reward."""
+
+  def __init__(self, task_list):
+    self._subtasks = [sub for t in task_list for sub in subtasks_of(t)]
+
+
 def subtasks_of(task):
-  """[sub-tasks] of a MetaAggregated task, or [task]."""
-  return list(task._subtasks) if _cls(task) == 'MetaAggregated' else [task]
+  """[sub-tasks] of a MetaAggregated task (or of ConcatenatedTasks), or [task]."""
+  return list(task._subtasks) if _cls(task) in ('MetaAggregated', 'ConcatenatedTasks') else [task]
 
 
 def find_pil_renderer(renderers):
@@ -288,6 +296,7 @@ class Pool(object):
     self.rgb = np.zeros((P, S, 4), np.uint8)
     self.label = np.zeros((P, T, S), np.int8)
     self.cell_label = None      # i8[P, T, S, SWB_MAX_CELLS] when a task keys on position (swb_task::n_xcuts), else None
+    self.task_set = None        # u8[P]: the task set of every entry (swb_set_entry_task_sets), or None: the engine has none
     self.pool_base = None
     self.pool_len = None
     # Not consumed by the kernels; kept for SpriteFactors-style observations.
@@ -395,3 +404,157 @@ def lower_episodes(episodes, task, renderers, max_sprites=None):
         if keyed[t]:       # membership by position: the label in every cell of the task's grid (looked up every step)
           pool.cell_label[e, t, s] = cell_labels_of(sub, sp, cuts[t][0], cuts[t][1], pos_dtype)
   return pool
+
+
+# --------------------------------------------------------------------------- #
+# Task sets (include/swb.h: swb_task_set)                #
+# --------------------------------------------------------------------------- #
+# what the configs of one batch must agree on: the kernels read it once per launch, not per episode
+_SHARED_FIELDS = ('image_h', 'image_w', 'anti_aliasing', 'action_space', 'action_scale', 'motion_cost', 'keep_in_frame',
+                  'pos_is_f32', 'action_is_f32')
+_POOL_SPRITE_ARRAYS = ('x', 'y', 'x_vel', 'y_vel', 'scale', 'cos_a', 'sin_a', 'shape', 'rgb', 'angle', 'color', 'attr_f32')
+
+
+def task_set_assignment(task_set_of_entry, num_envs, episodes_per_env, n_sets):
+  """u8[N, episodes_per_env]: the task set of entry k of environment n.  'cycle': (n + k) mod G; 'per_env': n mod G; or an
+  integer array of that shape with values in [0, G)."""
+  N, E, G = int(num_envs), int(episodes_per_env), int(n_sets)
+  n, k = np.arange(N)[:, None], np.arange(E)[None, :]
+  if isinstance(task_set_of_entry, str):
+    if task_set_of_entry == 'cycle':
+      return ((n + k) % G).astype(np.uint8)
+    if task_set_of_entry == 'per_env':
+      return np.ascontiguousarray(np.broadcast_to(n % G, (N, E)).astype(np.uint8))
+    raise LoweringError("task_set_of_entry is 'cycle', 'per_env' or an int array [%d, %d], got %r" % (N, E, task_set_of_entry))
+  a = np.asarray(task_set_of_entry)
+  if a.shape != (N, E) or a.dtype.kind not in 'iu':
+    raise LoweringError('task_set_of_entry must be an int array [%d, %d], got %s %s' % (N, E, a.dtype, a.shape))
+  if a.size and (a.min() < 0 or a.max() >= G):
+    raise LoweringError('task_set_of_entry names set %d, there are %d' % (int(a.max() if a.max() >= G else a.min()), G))
+  return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def task_set_of_config(cfg, first_task=0):
+  """The SwbTaskSet that stands for the task of a SwbConfig whose sub-tasks sit at first_task .. of the table."""
+  return _abi.SwbTaskSet(first_task=int(first_task), n_tasks=cfg.n_tasks, is_meta=cfg.is_meta,
+                         meta_aggregator=cfg.meta_aggregator if cfg.is_meta else 0,
+                         meta_termination=cfg.meta_termination if cfg.is_meta else 0,
+                         max_episode_length=cfg.max_episode_length,
+                         meta_terminate_bonus=cfg.meta_terminate_bonus if cfg.is_meta else 0.0)
+
+
+def merge_task_set_configs(cfgs):
+  """(SwbConfig, [SwbTaskSet]) of a handle that plays the tasks of `cfgs`: the sub-task tables concatenated in order, one set
+  per config, max_sprites the widest.  The configs have been checked to agree on what one batch shares (merge_task_sets)."""
+  T = sum(c.n_tasks for c in cfgs)
+  if T > _abi.SWB_MAX_TASKS:
+    raise LoweringError('%d sub-tasks over all task sets, at most %d supported' % (T, _abi.SWB_MAX_TASKS))
+  cfg = _abi.SwbConfig.from_buffer_copy(bytes(cfgs[0]))
+  cfg.max_sprites, cfg.n_tasks = max(c.max_sprites for c in cfgs), T
+  cfg.is_meta = cfg.meta_aggregator = cfg.meta_termination = 0       # (unused on a handle with task sets)
+  cfg.meta_terminate_bonus = 0.0
+  cfg.max_episode_length = max(c.max_episode_length for c in cfgs)
+  sets, first = [], 0
+  for c in cfgs:
+    for t in range(c.n_tasks):
+      cfg.tasks[first + t] = c.tasks[t]
+    sets.append(task_set_of_config(c, first))
+    first += c.n_tasks
+  for t in range(T, _abi.SWB_MAX_TASKS):
+    cfg.tasks[t] = _abi.SwbTask()
+  return cfg, sets
+
+
+def check_shared_config(configs):
+  """Raises LoweringError naming the field in which reference-style config dicts of one batch differ: they share the action
+  space (class and parameters), the renderers (names, classes, image size, anti-aliasing, background, colour map, factors)
+  and keep_in_frame.  A renderer attribute that is not listed here is not compared."""
+  def action_space_key(a):
+    return (type(a).__name__,) + tuple(sorted((k, repr(v)) for k, v in vars(a).items()))
+
+  def renderers_key(r):
+    return tuple(sorted((k, type(v).__name__, repr(getattr(v, '_image_size', None)), repr(getattr(v, '_anti_aliasing', None)),
+                         repr(_bg_of(v)) if hasattr(v, '_anti_aliasing') else '', repr(getattr(v, '_color_to_rgb', None)),
+                         repr(getattr(v, '_factors', None))) for k, v in r.items()))
+  first = configs[0]
+  for g, c in enumerate(configs):
+    for field, key, default in (('action_space', action_space_key, None), ('renderers', renderers_key, None),
+                                ('keep_in_frame', bool, True)):
+      if key(c.get(field, default)) != key(first.get(field, default)):
+        raise LoweringError('config %d differs from config 0 in %s: the configs of one batch share it' % (g, field))
+
+
+def merge_task_sets(parts, set_of_entry):
+  """One (SwbConfig, [SwbTaskSet], Pool) for a batch whose episodes are played under G different tasks.
+
+  parts: [(cfg_g, pool_g)], one lowered configuration per set -- the same environments, geometry and action space (a
+  LoweringError names the field that differs), pools of the same P entries and per-environment ranges; they may differ in the
+  task, its max_episode_length, the sprites and max_sprites (the narrower pools are padded with empty sprite slots).
+  set_of_entry: int[P], the set each entry of the merged pool is played under: entry e is entry e of pool_{set_of_entry[e]},
+  labelled for the sub-tasks of its own set ONLY -- the parts' scenes differ, so the label rows of the other sets stay 0: they
+  are never read while the entry keeps its set, and mean nothing if swb_set_entry_task_sets moves it (lower_task_sets, from one
+  list of episodes, fills every row).
+  The sub-task tables are concatenated in order; more than SWB_MAX_TASKS sub-tasks or SWB_MAX_TASK_SETS sets are refused."""
+  if not 1 <= len(parts) <= _abi.SWB_MAX_TASK_SETS:
+    raise LoweringError('between 1 and %d task sets supported, got %d' % (_abi.SWB_MAX_TASK_SETS, len(parts)))
+  cfg0, pool0 = parts[0]
+  for g, (c, pl) in enumerate(parts):
+    for f in _SHARED_FIELDS + ('n_envs',):
+      if getattr(c, f) != getattr(cfg0, f):
+        raise LoweringError('task set %d differs from set 0 in %s (%r / %r): one batch has one %s' % (
+            g, f, getattr(c, f), getattr(cfg0, f), f))
+    if bytes(c.bg_rgb) != bytes(cfg0.bg_rgb):
+      raise LoweringError('task set %d differs from set 0 in bg_rgb' % g)
+    if pl.n_entries != pool0.n_entries or not (np.array_equal(pl.pool_base, pool0.pool_base) and
+                                               np.array_equal(pl.pool_len, pool0.pool_len)):
+      raise LoweringError('task set %d: its pool has other entries or ranges than that of set 0' % g)
+  cfg, sets = merge_task_set_configs([c for c, _ in parts])
+  T = cfg.n_tasks
+  P, S = pool0.n_entries, cfg.max_sprites
+  which = np.asarray(set_of_entry)
+  if which.shape != (P,) or which.dtype.kind not in 'iu' or (which.size and (which.min() < 0 or which.max() >= len(parts))):
+    raise LoweringError('set_of_entry must be an int array [%d] with values in [0, %d)' % (P, len(parts)))
+  pool = Pool(P, S, T)
+  if any(pl.cell_label is not None for _, pl in parts):
+    pool.cell_label = np.zeros((P, T, S, _abi.SWB_MAX_CELLS), np.int8)
+  first = 0
+  for g, (c, pl) in enumerate(parts):
+    mine, Sg = which == g, pl.max_sprites
+    pool.n_sprites[mine] = pl.n_sprites[mine]
+    for name in _POOL_SPRITE_ARRAYS:
+      getattr(pool, name)[mine, :Sg] = getattr(pl, name)[mine]
+    pool.label[mine, first:first + c.n_tasks, :Sg] = pl.label[mine]
+    if pl.cell_label is not None:
+      pool.cell_label[mine, first:first + c.n_tasks, :Sg] = pl.cell_label[mine]
+    first += c.n_tasks
+  pool.pool_base, pool.pool_len = pool0.pool_base.copy(), pool0.pool_len.copy()
+  pool.task_set = np.ascontiguousarray(which, dtype=np.uint8)
+  return cfg, sets, pool
+
+
+def lower_task_sets(task_list, max_episode_lengths, action_space, renderers, keep_in_frame, episodes, set_of_entry, num_envs,
+                    episodes_per_env, max_sprites=None, action_dtype=np.float64):
+  """A list of tasks lowered into one concatenated sub-task table plus SwbTaskSet records, and the episodes (a list of sprite
+  lists, env-major: entry k of environment n at n * episodes_per_env + k) into one Pool.  Every entry is labelled for the
+  sub-tasks of EVERY set -- only the rows of its own set are read while it keeps it, and a reassignment
+  (swb_set_entry_task_sets) finds the rows of the new set filled.  Returns (SwbConfig, [SwbTaskSet], Pool).
+  More than SWB_MAX_TASKS sub-tasks over all tasks, or more than SWB_MAX_TASK_SETS tasks, raise LoweringError."""
+  if not 1 <= len(task_list) <= _abi.SWB_MAX_TASK_SETS:
+    raise LoweringError('between 1 and %d task sets supported, got %d' % (_abi.SWB_MAX_TASK_SETS, len(task_list)))
+  n_sub = sum(len(subtasks_of(t)) for t in task_list)
+  if n_sub > _abi.SWB_MAX_TASKS:
+    raise LoweringError('%d sub-tasks over all task sets, at most %d supported' % (n_sub, _abi.SWB_MAX_TASKS))
+  which = np.asarray(set_of_entry).reshape(-1)
+  if which.shape != (len(episodes),):
+    raise LoweringError('set_of_entry names %d entries, there are %d episodes' % (which.size, len(episodes)))
+  S = max_sprites or max([len(ep) for ep in episodes] + [1])
+  pos_is_f32 = position_dtype(episodes) == np.float32
+  cfgs = [lower_config(task, action_space, renderers, keep_in_frame, max_episode_lengths[g], num_envs, S, pos_is_f32, action_dtype)
+          for g, task in enumerate(task_list)]
+  cfg, sets = merge_task_set_configs(cfgs)
+  pool = lower_episodes(episodes, ConcatenatedTasks(task_list), renderers, max_sprites=S)
+  pool.assign_round_robin(num_envs, episodes_per_env)
+  if int(which.max(initial=0)) >= len(task_list) or int(which.min(initial=0)) < 0:
+    raise LoweringError('set_of_entry names a set outside [0, %d)' % len(task_list))
+  pool.task_set = np.ascontiguousarray(which, dtype=np.uint8)
+  return cfg, sets, pool

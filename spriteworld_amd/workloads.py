@@ -350,3 +350,24 @@ def build_protocol_8d(name, num_envs, episodes_per_env=4, anti_aliasing=5, env_o
   def actions_of_step(t):
     return np.ascontiguousarray(np.random.RandomState(2000 + int(t)).uniform(size=(total, 4))[env_offset:env_offset + num_envs])
   return cfg, pool, actions_of_step
+
+
+def build_task_sets(names, num_envs, episodes_per_env=4, seed=0, anti_aliasing=5, task_set_of_entry='cycle',
+                    max_episode_lengths=None):
+  """Workloads of `build()` that share geometry and action space merged into one batch whose episodes are played under the
+  task of one of them.  Returns (SwbConfig, [SwbTaskSet], Pool, sample_actions(rng) -> ndarray): entry k
+  of environment n is that entry of workload set[n, k] (drawn with seed + its index) -- `task_set_of_entry`: 'cycle' ((n + k)
+  mod G), 'per_env' (n mod G) or an int array [N, episodes_per_env].  Where max_sprites differs the narrower scenes are padded
+  with empty sprite slots.  max_episode_lengths: one per workload, in place of their own.
+  An entry is labelled for the sub-tasks of its own set only (its sprites are its workload's; the other label rows are 0):
+  `Engine.set_entry_task_sets` on this pool moves an entry to label rows that say nothing about it."""
+  parts, sample = [], None
+  for g, name in enumerate(names):
+    cfg, pool, smp = build(name, num_envs, episodes_per_env, seed + g, anti_aliasing)
+    if max_episode_lengths is not None:
+      cfg.max_episode_length = int(max_episode_lengths[g])
+    parts.append((cfg, pool))
+    sample = sample or smp
+  which = lowering.task_set_assignment(task_set_of_entry, num_envs, episodes_per_env, len(names))
+  cfg, sets, pool = lowering.merge_task_sets(parts, which.reshape(-1))
+  return cfg, sets, pool, sample

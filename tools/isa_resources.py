@@ -22,8 +22,11 @@ def kernels_of(asm):
     name = re.search(r'\.name:\s+(\S+)', block).group(1)
     if 'swb_' not in name:
       continue
+    ms = re.search(r'swb_cover_sets_kernelILi(\d+)ELb([01])E', name)
     m = re.search(r'swb_cover_kernelILi(\d+)ELb([01])ELb([01])E', name)
-    if m:
+    if ms:
+      key = 'swb_cover_sets_kernel<%s%s>' % (ms.group(1), ',PAINT' if ms.group(2) == '1' else '')
+    elif m:
       key = 'swb_cover_kernel<%s%s%s>' % (m.group(1), ',OV' if m.group(2) == '1' else '', ',PAINT' if m.group(3) == '1' else '')
     else:
       m = re.search(r'swb_resample_kernelILi(\d+)E', name)
